@@ -5,7 +5,10 @@ every rank samples its own B images; the only collective is the RCCL all-gather 
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+headline line; --dump-outputs DIR also writes what the last timed step returned (images, token ids, f_hat) as DIR/<name>.npy.
+--full adds the other readings (no-decode rate, decode alone, the other acceptance modes, plain AR, the public API path, the
+speculation gain by batch, the bf16x3 mode) and two extra objects:
   roofline      the dominant kernel class of the step (by HIP-event time on the launch stream), algorithmic
                 flops / bytes per launch from DESIGN.md section 4 vs the gfx950 peak
   cpu_baseline  the CPU oracle (oracle/var_oracle.py, the pinned restatement of the reference's
@@ -76,6 +79,8 @@ def main():
     ap.add_argument("--serial-decode", action="store_true", help="decode on the sampling stream instead of overlapping it with the next batch")
     ap.add_argument("--gemm-mode", default=None, choices=["f32", "bf16x3", "f16x2"], help="default: sdvar_amd.engine.DEFAULT_GEMM_MODE")
     ap.add_argument("--miopen-find", action="store_true", help="torch.backends.cudnn.benchmark for the VQVAE decoder convs")
+    ap.add_argument("--full", action="store_true", help="after the headline: the other modes, the roofline leg and the CPU baseline (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the images, token ids and f_hat of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     from sdvar_amd import dist as D
@@ -129,6 +134,7 @@ def main():
     def step(mode, seed, run_ahead=None):
         ra = (not args.no_run_ahead) if run_ahead is None else run_ahead
         res = smp.spec_decode(labels, CFG, args.gamma, 900, 0.96, E.Noise("device", seed, image_offset=lo), thr=thr[mode], run_ahead=ra)
+        state["res"] = res
         st = dict(res.stats); st["images"] = B
         if args.serial_decode:
             state["img"] = decode(res.f_hat).add_(1).mul_(0.5)                   # (B,3,256,256) in [0,1]  (var.py:215)
@@ -164,6 +170,32 @@ def main():
     dt, agg = timed(args.mode, args.steps, args.warmup)
     value = agg["images"] / dt
     log(f"timed region: {dt:.3f}s for {args.steps} steps -> {value:.2f} images/s")
+
+    if args.dump_outputs:          # what a caller of the timed path receives from its last step (complete: timed() drained both streams)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        for name, t in (("images", state["img"]), ("ids", state["res"].ids), ("f_hat", state["res"].f_hat)):
+            np.save(os.path.join(args.dump_outputs, name + sfx + ".npy"), t.float().cpu().numpy())
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    out = {
+        "metric": f"images/s (+ mean accepted tokens/step), {conf['name']}, per GPU",
+        "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32", "bf16x3": "f32 (GEMM operands split exactly into 3 bf16 planes, 6 bf16 MFMA products, fp32 accumulate)",
+                  "f16x2": "f32 (GEMM operands split into 2 fp16 planes to 2^-22, 3 fp16 MFMA products, fp32 accumulate)"}[tc.gemm_mode], "data": "synthetic (random-init weights, labels arange(B)%1000, device Philox noise)",
+        "config": {"workload": f"BASELINE.json {args.config}: VAR-d{args.depth_target} {conf['ladder']}^2 B={B}/GPU, d{args.depth_draft} draft + d{args.depth_target} verify, gamma={args.gamma}, "
+                               f"cfg={CFG} top_k=900 top_p=0.96, {'fp16 KV cache, ' if conf['kv_fp16'] else ''}acceptance={args.mode}, incl. VQVAE decode ({'serial' if args.serial_decode else 'overlapped with the next batch on a 2nd stream'}); "
+                               f"verifier {'in lock-step with' if args.no_run_ahead else 'one round behind'} the draft once gamma = 1", "parallelism": f"{world} independent batch shards"},
+        "mean_accepted_tokens_per_step": agg["mean_accepted_tokens_per_step"],
+        "target_calls": agg["target_calls"], "draft_stage_calls": agg["draft_stage_calls"], "forced_accepts": agg["forced_accepts"],
+        "per_rank_counters": dict(keys=list(D.COUNTER_KEYS), rows=agg["per_rank"], note="all-gathered over the process group (RCCL on the GPU box): one row per rank"),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        return
 
     # no-decode rate (sampler only), same mode, shorter
     def timed_nodecode(steps):
@@ -484,23 +516,12 @@ def main():
     class_ms = {k: round(v["ms"], 3) for k, v in classes.items()}
     log(f"profiled step: {class_ms}")
 
-    out = {
-        "metric": f"images/s (+ mean accepted tokens/step), {conf['name']}, per GPU",
-        "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": {"f32": "f32", "bf16x3": "f32 (GEMM operands split exactly into 3 bf16 planes, 6 bf16 MFMA products, fp32 accumulate)",
-                  "f16x2": "f32 (GEMM operands split into 2 fp16 planes to 2^-22, 3 fp16 MFMA products, fp32 accumulate)"}[tc.gemm_mode], "data": "synthetic (random-init weights, labels arange(B)%1000, device Philox noise)",
-        "config": {"workload": f"BASELINE.json {args.config}: VAR-d{args.depth_target} {conf['ladder']}^2 B={B}/GPU, d{args.depth_draft} draft + d{args.depth_target} verify, gamma={args.gamma}, "
-                               f"cfg={CFG} top_k=900 top_p=0.96, {'fp16 KV cache, ' if conf['kv_fp16'] else ''}acceptance={args.mode}, incl. VQVAE decode ({'serial' if args.serial_decode else 'overlapped with the next batch on a 2nd stream'}); "
-                               f"verifier {'in lock-step with' if args.no_run_ahead else 'one round behind'} the draft once gamma = 1", "parallelism": f"{world} independent batch shards"},
+    out.update({
         "value_bf16x3": extra.get("bf16x3", {}).get("images_per_s"),          # the same loop in the exact-split mode (no activation range limit): quote it beside `value`
-        "mean_accepted_tokens_per_step": agg["mean_accepted_tokens_per_step"],
-        "target_calls": agg["target_calls"], "draft_stage_calls": agg["draft_stage_calls"], "forced_accepts": agg["forced_accepts"],
-        "per_rank_counters": dict(keys=list(D.COUNTER_KEYS), rows=agg["per_rank"], note="all-gathered over the process group (RCCL on the GPU box): one row per rank"),
         "images_per_s_no_decode": B * world * nd_steps / dt_nd,
         "decode_ms_per_batch": dec_ms, "decoder_tflops_algorithmic": dec_tflops, "decoder": "pytorch-miopen" if args.torch_decode else "hip (csrc/conv.hip, csrc/vae.hip)",
         "modes": extra, "roofline_note": "roofline / kernel_class_ms_per_step come from one step with every kernel alone on the GPU (no draft/verify or decode overlap)", "roofline": roofline, "roofline_gemm_small_m": roofline_gemm_small, "roofline_verify_attention": roofline_attn, "roofline_verify_attention_short_stages": roofline_attn_small, "roofline_verify_attention_P4_fp16_kv": roofline_attn_p4, "kernel_class_ms_per_step": class_ms,
-    }
+    })
 
     # ---- CPU baseline (rank 0, N=1): the oracle's plain AR of the TARGET model on the host cores
     if world == 1 and not args.no_cpu_baseline:

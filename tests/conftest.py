@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -28,6 +29,14 @@ def dev():
 
 def golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+
+
+def golden_parts(name):
+    """A fixture stored as name.npz plus parts name.<part>.npz (each under the size limit of a committed file): one dict of every array."""
+    out = dict(golden(name))
+    for f in sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".*.npz"))):
+        out.update(np.load(f, allow_pickle=False))
+    return out
 
 
 def rnd(seed, shape, scale=1.0):

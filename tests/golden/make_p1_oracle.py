@@ -9,8 +9,11 @@ logits of the target (what acceptance reads): per token the 8 largest entries an
 still runs ONE seed against the live oracle with the full logit tensors.
 
     python tests/golden/make_p1_oracle.py          # writes tests/golden/p1_oracle.npz (about 15 minutes on 8 cores)
+
+The settings go to p1_oracle.npz and each (mode, seed) to p1_oracle.<mode>_<seed>.npz, so that no file exceeds the 1 MiB limit of a committed file
+(tests/conftest.py:golden_parts reads them back as one dict).
 """
-import os, sys, time
+import glob, os, sys, time
 import numpy as np
 import torch
 
@@ -61,8 +64,12 @@ def main():
                 out[k + f"r{ri}_idx"] = idx.numpy().astype(np.int16)
                 out[k + f"r{ri}_val"] = torch.gather(cl, -1, idx).numpy()
             print(f"{mode} seed {seed}: {len(st['rounds'])} rounds, min margin {min(tr.margins):.2e}, {time.time() - t0:.0f}s", flush=True)
-    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "p1_oracle.npz"), **out)
-    print("written", os.path.getsize(os.path.join(ROOT, "tests", "golden", "p1_oracle.npz")) / 1e6, "MB")
+    gdir = os.path.join(ROOT, "tests", "golden")
+    parts = {f"{m}_{s}": {k: v for k, v in out.items() if k.startswith(f"{m}_{s}_")} for m in MODES for s in SEEDS}
+    np.savez_compressed(os.path.join(gdir, "p1_oracle.npz"), **{k: v for k, v in out.items() if not any(k in p for p in parts.values())})
+    for name, arrays in parts.items():
+        np.savez_compressed(os.path.join(gdir, f"p1_oracle.{name}.npz"), **arrays)
+    print("written", sum(os.path.getsize(f) for f in glob.glob(os.path.join(gdir, "p1_oracle*.npz"))) / 1e6, "MB")
 
 
 if __name__ == "__main__":

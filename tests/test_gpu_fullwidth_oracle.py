@@ -119,12 +119,12 @@ def p1_host(dev):
 
 @pytest.mark.parametrize("mode,thr", [("accept_all", 0.0), ("natural", 0.5)])
 def test_P1_spec_decode_vs_oracle_fixture(dev, p1_host, mode, thr):
-    """Config P1 at full size in the BENCHED arithmetic against the oracle's golden vectors (tests/golden/p1_oracle.npz: 4 seeds x 2 acceptance modes): per seed the token
+    """Config P1 at full size in the BENCHED arithmetic against the oracle's golden vectors (tests/golden/p1_oracle*.npz: 4 seeds x 2 acceptance modes): per seed the token
     ids (bit-exact, or a first flip on a draw the oracle had within 1e-3 of a tie), the per-round CFG logits of the target at the sampled columns (the 8 largest and 8
     pseudo-random entries of every token: <= 1e-3), f_hat <= 1e-4, every counter and the per-round acceptance record; run-ahead == lock-step on every seed.
     The NUMBER of fully clean seeds is asserted (>= 3 of 4) and the per-seed record is printed, so a regression that turns a clean seed into a 'tie flip' shows."""
-    from conftest import golden
-    g = golden("p1_oracle")
+    from conftest import golden_parts
+    g = golden_parts("p1_oracle")
     smp = p1_host
     lad, B = smp.lad, int(g["B"])
     labels = torch.from_numpy(g["labels"]).long()

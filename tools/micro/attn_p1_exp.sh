@@ -11,7 +11,7 @@ timeout -k 10 500 python -m pytest tests/test_gpu_fullwidth_oracle.py tests/test
 echo "== logit error (P1 build)"
 for n in ar_d6_256_stress ar_d16_256_stress_B1 ar_d4_512_stress; do timeout -k 10 200 python tools/micro/logit_err.py $n 2>&1 | tail -1; done
 echo "== bench (P1 build)"
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra-modes 2>&1 >/dev/null | grep -E "timed region|no-decode|profiled"
+python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra-modes 2>&1 >/dev/null | grep -E "timed region|no-decode|profiled"
 cd sdvar_amd/csrc && make -B attention_f16x2.o > /dev/null 2>&1 && make > /dev/null 2>&1; cd ../..
 echo "== logit error (product build)"
 for n in ar_d6_256_stress ar_d16_256_stress_B1 ar_d4_512_stress; do timeout -k 10 200 python tools/micro/logit_err.py $n 2>&1 | tail -1; done

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """HBM-side bytes per launch and kernel class from two rocprofv3 counter passes (FETCH_SIZE and WRITE_SIZE cannot share a pass):
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_f --output-format csv -- python3 bench.py --steps 1 --warmup 0 ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_w --output-format csv -- python3 bench.py --steps 1 --warmup 0 ...
-    python tools/pmc_traffic.py gpurun_out/pmc_f gpurun_out/pmc_w profiles/pmc_traffic.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d prof/pmc_f --output-format csv -- python3 bench.py --steps 1 --warmup 0 --full ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d prof/pmc_w --output-format csv -- python3 bench.py --steps 1 --warmup 0 --full ...
+    python tools/pmc_traffic.py prof/pmc_f prof/pmc_w profiles/pmc_traffic.json
 Units and corrections as /opt/skills/guides/MI355X_MICROARCH.md prescribes: both counters are in KB; on gfx950 FETCH_SIZE tallies the 128-byte
 requests of wide streaming reads at 64 bytes and is doubled; WRITE_SIZE is exact for 16-byte-per-lane stores."""
 import csv, glob, json, sys, collections
@@ -35,7 +35,7 @@ def load(d, counter):
 def main():
     fd, wd, out = sys.argv[1:4]
     F, W = load(fd, "FETCH_SIZE"), load(wd, "WRITE_SIZE")
-    res = {"_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "
+    res = {"_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline "
                     "--no-extra-modes --serial-decode; KB units; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 counts 128-B requests at 64 B)"}
     for c, _ in CLASSES:
         if c in F and c in W and F[c][0]:

@@ -3,7 +3,7 @@
 set -e
 TAG=${1:-r02}
 R=$GRAFT_REPO_ROOT
-ARGS="--no-cpu-baseline --no-extra-modes --serial-decode --no-run-ahead"
+ARGS="--full --no-cpu-baseline --no-extra-modes --serial-decode --no-run-ahead"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${TAG}_stats --output-format csv -- python3 $R/bench.py --steps 5 --warmup 3 $ARGS > $R/gpurun_out/${TAG}_stats.log 2>&1
 echo stats done

@@ -7,7 +7,7 @@
 tag=${1:-prof}
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
-B="bench.py --no-cpu-baseline --no-extra-modes"
+B="bench.py --full --no-cpu-baseline --no-extra-modes"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_st -- python3 $B --steps 10 --warmup 3 > gpurun_out/${tag}_prof_bench.json 2> gpurun_out/${tag}_prof_bench.log || exit 1
 f=$(find gpurun_out/${tag}_st -name "*kernel_stats.csv" | head -1)
 if [ -n "$f" ]; then cp "$f" gpurun_out/${tag}_kernel_stats.csv; cut -c1-200 "$f" | head -45 > gpurun_out/${tag}_kernel_stats_top.txt; fi

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Matrix-pipe occupancy per kernel class from one rocprofv3 SQ counter pass (its own run: --kernel-trace --pmc only):
     rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE \\
-              -d gpurun_out/sq --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-modes --serial-decode --no-run-ahead
-    python tools/sq_counters.py gpurun_out/sq profiles/r02_sq_counters.json
+              -d prof/sq --output-format csv -- python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra-modes --serial-decode --no-run-ahead
+    python tools/sq_counters.py prof/sq profiles/r02_sq_counters.json
 Units (MI355X_MICROARCH.md): SQ_VALU_MFMA_BUSY_CYCLES counts shader cycles summed over the SIMDs (32 per v_mfma_f32_32x32x16_*); SQ_WAVE_CYCLES / SQ_WAIT_* /
 SQ_ACTIVE_INST_* count quad-cycles summed over waves; SQ_BUSY_CYCLES is summed over the 32 shader engines (32 SIMDs each), so the matrix-pipe
 occupancy of a class is  mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (32 x SQ_BUSY_CYCLES)  and the clock the chip held is SQ_BUSY_CYCLES / 32 / time.
@@ -25,7 +25,7 @@ for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
         if key not in n[c]:
             n[c].add(key)
             dur[c] += float(r["End_Timestamp"]) - float(r["Start_Timestamp"])
-res = {"_note": "rocprofv3 --kernel-trace --pmc <SQ counters> GRBM_GUI_ACTIVE over python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-modes --serial-decode "
+res = {"_note": "rocprofv3 --kernel-trace --pmc <SQ counters> GRBM_GUI_ACTIVE over python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra-modes --serial-decode "
                 "--no-run-ahead (every kernel alone on the GPU); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (32 * SQ_BUSY_CYCLES) (32 shader engines x 32 SIMDs); clock_ghz = SQ_BUSY_CYCLES / 32 / time; "
                 "wait_frac = SQ_WAIT_ANY / SQ_WAVE_CYCLES (share of wave lifetime parked in s_waitcnt / barriers); profiled passes run at a lower clock than unprofiled ones"}
 for c, _ in CLASSES:
