@@ -26,6 +26,7 @@ extern "C" {
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
 typedef struct sdvar_quant sdvar_quant_t;   /* VectorQuantizer2 inference side: codebook, Phi convs, resample tables */
 typedef struct sdvar_vae sdvar_vae_t;       /* VQVAE image decoder (fhat_to_img): conv weights as bf16x3 planes, activation workspaces */
+typedef struct sdvar_vae_enc sdvar_vae_enc_t; /* VQVAE image encoder (quant_conv(encoder(img))): same planes and workspaces as the decoder */
 
 typedef struct {
     int32_t depth;                          /* d: width C = 64 d, heads H = d   (models/__init__.py:26-27) */
@@ -124,6 +125,12 @@ int sdvar_quant_next_from(sdvar_quant_t* q, int32_t si, const int64_t* ids, int3
                           int32_t B, void* stream);
 /* the same from explicit feature vectors h (B, pn_si^2, cvae) instead of token ids (more_smooth=True, var.py:206-210) */
 int sdvar_quant_next_h(sdvar_quant_t* q, int32_t si, const float* h, float* f_hat, float* nxt, int32_t B, void* stream);
+/* f_to_idxBl_or_fhat (quant.py:135-166, using_znorm = False): multi-scale residual quantisation of f (B,cvae,HW,HW).  Per scale s:
+ * z = area_down(f_rest, pn_s) (f_rest itself at the last scale); ids = argmin_v |z|^2 + |e_v|^2 - 2 z.e_v in fp32, ties to the lowest index;
+ * h = Phi(bicubic_up(codebook[ids])); f_hat += h; f_rest -= h.  ids_out (B, L) int64 (L = sum pn^2, scales in order); f_hat_out (B,cvae,HW,HW)
+ * the final f_hat; f_hat_per_scale (S,B,cvae,HW,HW) or NULL: f_hat after every scale.  cvae = 32 only.  |e_v|^2 is computed once per bind,
+ * on the stream of the first call. */
+int sdvar_quant_encode(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, void* stream);
 /* more_smooth=True (var.py:206-208 + helpers.py:22-36): h (B,l,cvae) = softmax((masked * (1 + ratio) + g) / tau) @ codebook,
  * g = -log(E), E ~ Exp(1): e_noise (B,l,V) explicit, or NULL for the Philox stream at (seed, draw, image_offset).  `masked_logits`
  * (B,l,V) are the CFG logits as sample_with_top_k_top_p_ leaves them (helpers.py:10,15 mask in place): sdvar_cfg_sample's dbg_masked. */
@@ -154,6 +161,21 @@ int sdvar_vae_tensor_count(const sdvar_vae_desc* desc /*host*/);
 int sdvar_vae_bind(sdvar_vae_t* v, const float* const* tensors /*host*/, int32_t n_tensors, void* stream);
 /* vqvae.py:62-63: img (B,3,H,W) = clamp(decoder(post_quant_conv(f_hat (B,Cvae,h,w))), -1, 1), H = h << (n_mult-1) */
 int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream);
+
+/* ---- VQVAE encoder: image -> f = quant_conv(encoder(img)) (models/vqvae.py:65-67, models/basic_vae.py:99-161) ------------- */
+/* The decoder's descriptor: images are latent_hw << (n_mult-1) pixels square (256^2 -> latent 16^2, 512^2 -> 32^2), any B <= max_batch. */
+int sdvar_vae_enc_create(const sdvar_vae_desc* desc /*host*/, sdvar_vae_enc_t** out /*host*/);
+int sdvar_vae_enc_destroy(sdvar_vae_enc_t* e);
+/* number of tensors sdvar_vae_enc_bind expects for this descriptor */
+int sdvar_vae_enc_tensor_count(const sdvar_vae_desc* desc /*host*/);
+/* Host array of device pointers to the fp32 state_dict tensors, in execution order (weight then bias each):
+ * encoder.conv_in; for level = 0 .. n_mult-1: for i = 0 .. num_res_blocks-1: down.level.block.i {norm1, conv1, norm2, conv2,
+ * [nin_shortcut if the width changes]}, [down.level.attn.i {norm, qkv, proj_out} at the top level]; [down.level.downsample.conv for
+ * level < n_mult-1]; encoder.mid.block_1; encoder.mid.attn_1; encoder.mid.block_2; encoder.norm_out; encoder.conv_out; quant_conv.
+ * conv_in is zero-padded to 32 input channels and every Downsample2x weight is re-packed for the space-to-depth form at bind. */
+int sdvar_vae_enc_bind(sdvar_vae_enc_t* e, const float* const* tensors /*host*/, int32_t n_tensors, void* stream);
+/* f (B,z,h,h) = quant_conv(encoder(img (B,3,H,W))), H = W = h << (n_mult-1) */
+int sdvar_vae_enc_encode(sdvar_vae_enc_t* e, const float* img, int32_t B, float* f, void* stream);
 
 /* ---- sampling / acceptance -------------------------------------------------------------------------------------- */
 /* var.py:199-202 + helpers.py:6-19: CFG with t = cfg*si/(S-1), top-k, top-p, draw = argmax(p/q).
@@ -226,6 +248,15 @@ int sdvar_op_conv_weight_planes(const float* w, uint16_t* planes, int32_t Cout, 
  * mode bit 0: GroupNorm(32 groups) with stats (B,32,{mean,rstd}), gamma, beta; bit 1: SiLU. */
 int sdvar_op_vae_prep(const float* in, const float* stats, const float* gamma, const float* beta, uint16_t* planes, uint64_t plane_stride, int32_t plane_format, int32_t B,
                       int32_t C, int32_t H, int32_t W, int32_t up, int32_t mode, int32_t guard, void* stream);
+/* encoder conv_in operand: img (B,3,H,W) fp32 -> planes [npl][1][guard + B(H+2)(W+2) + guard][32] (channels 3..31 zero) */
+int sdvar_op_vae_img_planes(const float* img, uint16_t* planes, uint64_t plane_stride, int32_t plane_format, int32_t B, int32_t H, int32_t W, int32_t guard, void* stream);
+/* Downsample2x operand: rows [B H W][C] -> planes of the space-to-depth tensor (B, 4C, H/2, W/2), channel (2py+px)C + c = x[2y+py][2x+px][c] */
+int sdvar_op_vae_s2d_planes(const float* in, uint16_t* planes, uint64_t plane_stride, int32_t plane_format, int32_t B, int32_t C, int32_t H, int32_t W, int32_t guard,
+                            void* stream);
+/* Downsample2x weight (Cout, C, 3, 3) -> the 3x3 weight (Cout, 4C, 3, 3) over the space-to-depth tensor (fp32) */
+int sdvar_op_vae_s2d_weights(const float* w, float* w_s2d, int32_t Cout, int32_t C, void* stream);
+/* nearest code of z (N, cvae = 32) in codebook (V, cvae): ids (N) int64, ties to the lowest index; e2 (V floats) receives |e_v|^2 */
+int sdvar_op_quant_nearest(const float* z, int32_t N, const float* codebook, int32_t V, int32_t cvae, float* e2, int64_t* ids, void* stream);
 /* out[B H W][N] = conv(x planes of a (B,Cin,H,W) tensor, w planes) + bias (+ res[B H W][N]); taps = 9: 3x3 pad 1, taps = 1: 1x1.  x_row0 =
  * guard rows (>= W+3).  workspace: split-K slabs (may be NULL: no split); force_split > 0 overrides the heuristic. */
 int sdvar_op_conv_planes(const uint16_t* x_planes, uint64_t x_plane_stride, uint64_t x_rows, int32_t x_row0, const uint16_t* w_planes, uint64_t w_plane_stride,

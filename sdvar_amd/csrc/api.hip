@@ -68,6 +68,10 @@ int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const 
 int gumbel_mix(const float* masked, int B, int l, int V, float scale, float tau, const float* e, uint64_t seed, uint32_t draw, uint32_t image_offset,
                const float* codebook, int Cv, float* h, hipStream_t stream);
 void debug_set_gemm_cfg(int bm, int split);
+int quant_code_norms(const float* codebook, float* e2, int V, int Cv, hipStream_t stream);
+int quant_nearest(const float* z, int N, int P, const float* codebook, const float* e2, int V, int Cv, long long* ids, int ids_stride, hipStream_t stream);
+int quant_encode_stage(float* f_rest, float* f_hat, float* z, float* up_scratch, const float* codebook, const float* e2, const float* Wdn_si, const float* Wup_si,
+                       const float* phi_w, const float* phi_b, long long* ids, int ids_stride, int B, int pn, int HW, int V, int Cv, int last, hipStream_t stream);
 int quant_next(const long long* ids, int ids_stride, const float* hvec, const float* codebook, const float* Wup, const float* phi_w, const float* phi_b, const float* Wdn,
                float* up_scratch, const float* f_in, float* f_hat, float* nxt, int B, int pn, int pn_next, int HW, int Cv, int last, hipStream_t stream);
 
@@ -175,6 +179,9 @@ struct sdvar_quant {
     float* Wdn[SDVAR_MAX_STAGES];
     std::vector<std::vector<float>> hWup, hWdn;
     float* up_scratch;
+    float* Wenc0;        // encoding: area table HW -> pn_0 (scale s >= 1 uses Wdn[s - 1]: HW -> pn_s)
+    float *e2, *f_rest, *zrows;          // encoding: |e_v|^2, the residual (B,cvae,HW,HW), the rows of one scale's z
+    bool e2_ready;
     const float* codebook;
     const float* phi_w[SDVAR_MAX_STAGES];
     const float* phi_b[SDVAR_MAX_STAGES];
@@ -676,6 +683,20 @@ int sdvar_quant_create(int32_t S, const int32_t* patch_nums, int32_t cvae, int32
         }
     }
     SDVAR_TRY(dmalloc(&q->up_scratch, (size_t)max_batch * cvae * q->HW * q->HW));
+    q->Wenc0 = nullptr; q->e2 = q->f_rest = q->zrows = nullptr; q->e2_ready = false;
+    if (S > 1) {
+        const int HW = q->HW, p0 = q->pn[0];
+        std::vector<float> t((size_t)p0 * HW, 0.f);
+        for (int o = 0; o < p0; ++o) {
+            const int st = (o * HW) / p0, en = ((o + 1) * HW + p0 - 1) / p0;
+            for (int i = st; i < en; ++i) t[(size_t)o * HW + i] = 1.0f / (float)(en - st);
+        }
+        SDVAR_TRY(dmalloc(&q->Wenc0, t.size()));
+        SDVAR_HIP(hipMemcpy(q->Wenc0, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    SDVAR_TRY(dmalloc(&q->e2, (size_t)vocab));
+    SDVAR_TRY(dmalloc(&q->f_rest, (size_t)max_batch * cvae * q->HW * q->HW));
+    SDVAR_TRY(dmalloc(&q->zrows, (size_t)max_batch * cvae * q->HW * q->HW));
     *out = q;
     return SDVAR_OK;
 }
@@ -684,6 +705,8 @@ int sdvar_quant_destroy(sdvar_quant_t* q) {
     if (!q) return SDVAR_OK;
     for (int s = 0; s < q->S; ++s) { if (q->Wup[s]) (void)hipFree(q->Wup[s]); if (q->Wdn[s]) (void)hipFree(q->Wdn[s]); }
     if (q->up_scratch) (void)hipFree(q->up_scratch);
+    float* enc[] = {q->Wenc0, q->e2, q->f_rest, q->zrows};
+    for (float* p : enc) if (p) (void)hipFree(p);
     delete q;
     return SDVAR_OK;
 }
@@ -691,7 +714,7 @@ int sdvar_quant_destroy(sdvar_quant_t* q) {
 int sdvar_quant_bind(sdvar_quant_t* q, const float* codebook, const float* const* phi_w, const float* const* phi_b) {
     SDVAR_CHECK_ARG(q && codebook && phi_w && phi_b, "quant_bind: null argument");
     for (int k = 0; k < q->n_phi; ++k) { SDVAR_CHECK_ARG(phi_w[k] && phi_b[k], "quant_bind: null phi %d", k); q->phi_w[k] = phi_w[k]; q->phi_b[k] = phi_b[k]; }
-    q->codebook = codebook; q->bound = true;
+    q->codebook = codebook; q->bound = true; q->e2_ready = false;
     return SDVAR_OK;
 }
 
@@ -717,6 +740,36 @@ int sdvar_quant_next_from(sdvar_quant_t* q, int32_t si, const int64_t* ids, int3
 int sdvar_quant_next_h(sdvar_quant_t* q, int32_t si, const float* h, float* f_hat, float* nxt, int32_t B, void* stream) {
     SDVAR_CHECK_ARG(h, "quant_next_h: null feature vectors");
     return quant_next_impl(q, si, nullptr, 0, h, nullptr, f_hat, nxt, B, stream);
+}
+
+int sdvar_quant_encode(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, void* stream) {
+    SDVAR_CHECK_ARG(q && q->bound, "quant_encode: quantizer not bound");
+    SDVAR_CHECK_ARG(f && ids_out && f_hat_out, "quant_encode: null operand");
+    SDVAR_CHECK_ARG(B >= 1 && B <= q->maxB, "quant_encode: batch %d exceeds max_batch %d", B, q->maxB);
+    SDVAR_CHECK_ARG(q->Cv == 32, "quant_encode: Cvae %d (32 only)", q->Cv);
+    hipStream_t s = (hipStream_t)stream;
+    if (!q->e2_ready) { SDVAR_TRY(quant_code_norms(q->codebook, q->e2, q->V, q->Cv, s)); q->e2_ready = true; }     // once per bind, on the caller's stream
+    const size_t n = (size_t)B * q->Cv * q->HW * q->HW;
+    SDVAR_HIP(hipMemcpyAsync(q->f_rest, f, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SDVAR_HIP(hipMemsetAsync(f_hat_out, 0, n * sizeof(float), s));
+    int L = 0;
+    for (int si = 0; si < q->S; ++si) L += q->pn[si] * q->pn[si];
+    ProfScope ps(6, 2.0 * B * q->Cv * q->Cv * 9.0 * q->HW * q->HW * q->S, 4.0 * n * 4.0 * q->S, s);
+    int off = 0;
+    for (int si = 0; si < q->S; ++si) {
+        const int last = si == q->S - 1, k = q->phi_of[si];
+        const float* wdn = last ? nullptr : (si == 0 ? q->Wenc0 : q->Wdn[si - 1]);
+        SDVAR_TRY(quant_encode_stage(q->f_rest, f_hat_out, q->zrows, q->up_scratch, q->codebook, q->e2, wdn, q->Wup[si], q->phi_w[k], q->phi_b[k],
+                                     (long long*)ids_out + off, L, B, q->pn[si], q->HW, q->V, q->Cv, last, s));
+        if (f_hat_per_scale) SDVAR_HIP(hipMemcpyAsync(f_hat_per_scale + (size_t)si * n, f_hat_out, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        off += q->pn[si] * q->pn[si];
+    }
+    return SDVAR_OK;
+}
+
+int sdvar_op_quant_nearest(const float* z, int32_t N, const float* codebook, int32_t V, int32_t cvae, float* e2, int64_t* ids, void* stream) {
+    SDVAR_TRY(quant_code_norms(codebook, e2, V, cvae, (hipStream_t)stream));
+    return quant_nearest(z, N, N, codebook, e2, V, cvae, (long long*)ids, N, (hipStream_t)stream);
 }
 
 int sdvar_gumbel_mix(sdvar_quant_t* q, const float* masked_logits, int32_t B, int32_t l, double ratio, double tau, const float* e_noise, uint64_t seed,

@@ -14,6 +14,7 @@
 
 namespace sdvar {
 
+#define SDVAR_TRY_Q(call) do { int rc_ = (call); if (rc_ != SDVAR_OK) return rc_; } while (0)
 constexpr int QMAX_HW = 64;
 
 // up (b, c): tmp[Y][x] = sum_y Wup[Y][y] h[y][x];  out[Y][X] = sum_x tmp[Y][x] Wup[X][x]
@@ -140,6 +141,183 @@ int quant_next(const long long* ids, int ids_stride, const float* hvec, const fl
         hipLaunchKernelGGL(quant_down_kernel, dim3(Cv, B), dim3(256), lds_dn, stream, f_hat, Wdn, nxt, HW, pn_next, Cv);
         SDVAR_LAUNCH_CHECK();
     }
+    return SDVAR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- encoding (f_to_idxBl_or_fhat, quant.py:135-166)
+// Per scale si of the residual quantisation (using_znorm = False):
+//     z       = area_down(f_rest, pn_si) as rows (B pn^2, 32)      quant_down_kernel (the last scale: f_rest itself, quant_rows_kernel)
+//     idx     = argmin_v |z|^2 + |e_v|^2 - 2 z.e_v                   quant_nearest_kernel (fp32, ties -> lowest index as torch.argmin)
+//     h       = Phi(bicubic_up(codebook[idx]))                       quant_up_kernel + quant_phi_rest_kernel
+//     f_hat  += h,  f_rest -= h                                      (both in the phi launch; f_rest is its own tensor as quant.py:162-163)
+
+// |e_v|^2 (sequential fp32 chain over the channels), once at bind
+__global__ __launch_bounds__(256) void quant_code_norms_kernel(const float* __restrict__ codebook, float* __restrict__ e2, int V, int Cv) {
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
+        const float* e = codebook + (size_t)v * Cv;
+        float a = 0.f;
+        for (int c = 0; c < Cv; ++c) a = fmaf(e[c], e[c], a);
+        e2[v] = a;
+    }
+}
+
+// Nearest code for QN_ROWS rows of z (N, 32) per workgroup.  Thread t scans the codes t, t + 256, ... in increasing order (strict < keeps the
+// first of equal distances), holding the rows' |z|^2 and the 32 channels of the code in registers: 32 FMAs per row and code, the rows broadcast
+// from LDS.  The (d, v) pairs are reduced lexicographically across the wave (DPP-free shuffles) and the 4 waves (LDS).  Output row n = b P + p
+// goes to ids[b ids_stride + p].  The codebook (512 KB at V = 4096) is read from L2 by every workgroup.
+constexpr int QN_ROWS = 8;
+__device__ __forceinline__ void qn_better(float& d, int& v, float d2, int v2) {
+    if (d2 < d || (d2 == d && v2 < v) || (d != d && d2 == d2)) { d = d2; v = v2; }     // NaN distances lose to any number
+}
+__global__ __launch_bounds__(256) void quant_nearest_kernel(const float* __restrict__ z, const float* __restrict__ codebook, const float* __restrict__ e2,
+                                                            long long* __restrict__ ids, int N, int P, int ids_stride, int V) {
+    __shared__ __attribute__((aligned(16))) float zs[QN_ROWS][32];
+    __shared__ float z2s[QN_ROWS];
+    __shared__ float rd[4][QN_ROWS];
+    __shared__ int rv[4][QN_ROWS];
+    const int n0 = blockIdx.x * QN_ROWS, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nr = N - n0 < QN_ROWS ? N - n0 : QN_ROWS;
+    for (int i = tid; i < QN_ROWS * 32; i += 256) zs[i >> 5][i & 31] = (i >> 5) < nr ? z[(size_t)(n0 + (i >> 5)) * 32 + (i & 31)] : 0.f;
+    __syncthreads();
+    if (tid < QN_ROWS) {
+        float a = 0.f;
+        for (int c = 0; c < 32; ++c) a = fmaf(zs[tid][c], zs[tid][c], a);
+        z2s[tid] = a;
+    }
+    __syncthreads();
+    float bd[QN_ROWS]; int bv[QN_ROWS];
+#pragma unroll
+    for (int r = 0; r < QN_ROWS; ++r) { bd[r] = INFINITY; bv[r] = 0x7fffffff; }
+    for (int v = tid; v < V; v += 256) {
+        f32x4 e[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) e[k] = *reinterpret_cast<const f32x4*>(codebook + (size_t)v * 32 + 4 * k);
+        const float ev = e2[v];
+#pragma unroll
+        for (int r = 0; r < QN_ROWS; ++r) {
+            float dot = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const f32x4 zq = *reinterpret_cast<const f32x4*>(&zs[r][4 * k]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dot = fmaf(zq[j], e[k][j], dot);
+            }
+            const float d = (z2s[r] + ev) - 2.0f * dot;
+            if (d < bd[r] || (bd[r] != bd[r] && d == d) || bv[r] == 0x7fffffff) { bd[r] = d; bv[r] = v; }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < QN_ROWS; ++r) {
+        float d = bd[r]; int vv = bv[r];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float d2 = __shfl_xor(d, off, 64);
+            const int v2 = __shfl_xor(vv, off, 64);
+            qn_better(d, vv, d2, v2);
+        }
+        if (lane == 0) { rd[wave][r] = d; rv[wave][r] = vv; }
+    }
+    __syncthreads();
+    if (tid < nr) {
+        float d = rd[0][tid]; int vv = rv[0][tid];
+        for (int w = 1; w < 4; ++w) qn_better(d, vv, rd[w][tid], rv[w][tid]);
+        const int n = n0 + tid, b = n / P, p = n - b * P;
+        ids[(size_t)b * ids_stride + p] = vv;
+    }
+}
+
+// f_rest (B, Cv, HW, HW) -> rows (B HW^2, Cv)
+__global__ __launch_bounds__(256) void quant_rows_kernel(const float* __restrict__ f, float* __restrict__ z, int B, int HW, int Cv) {
+    const size_t total = (size_t)B * HW * HW * Cv;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % Cv);
+        const size_t row = i / Cv;
+        const int p = (int)(row % ((size_t)HW * HW)), b = (int)(row / ((size_t)HW * HW));
+        z[i] = f[((size_t)b * Cv + c) * HW * HW + p];
+    }
+}
+
+// quant_phi_kernel with both accumulators: h = 0.5 up + 0.5 (conv3x3(up) + bias); f_hat += h; f_rest -= h (same multiply-add order as quant_phi_kernel)
+template <bool STAGED>
+__global__ __launch_bounds__(256) void quant_phi_rest_kernel(const float* __restrict__ up, const float* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ f_hat, float* __restrict__ f_rest, int HW, int Cv) {
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    const int co = blockIdx.x, b = blockIdx.y;
+    const float* ub = up + (size_t)b * Cv * HW * HW;
+    const float* wc = w + (size_t)co * Cv * 9;
+    if (STAGED) {
+        const int n4 = Cv * HW * HW / 4;
+        for (int i = threadIdx.x; i < n4; i += blockDim.x) reinterpret_cast<f32x4*>(psm)[i] = reinterpret_cast<const f32x4*>(ub)[i];
+        for (int i = threadIdx.x; i < 9 * Cv; i += blockDim.x) psm[Cv * HW * HW + i] = wc[i];
+        __syncthreads();
+        ub = psm; wc = psm + Cv * HW * HW;
+    }
+    for (int e = threadIdx.x; e < HW * HW; e += blockDim.x) {
+        const int Y = e / HW, X = e % HW;
+        float acc = 0.f;
+        for (int ci = 0; ci < Cv; ++ci) {
+            const float* uc = ub + (size_t)ci * HW * HW;
+            const float* wk = wc + ci * 9;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const int yy = Y + dy - 1;
+                if (yy < 0 || yy >= HW) continue;
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    const int xx = X + dx - 1;
+                    if (xx < 0 || xx >= HW) continue;
+                    acc = fmaf(wk[dy * 3 + dx], uc[yy * HW + xx], acc);
+                }
+            }
+        }
+        const float h = ub[(size_t)co * HW * HW + e];
+        const float mixed = h * 0.5f + (acc + bias[co]) * 0.5f;
+        const size_t o = ((size_t)b * Cv + co) * HW * HW + e;
+        f_hat[o] = f_hat[o] + mixed;
+        f_rest[o] = f_rest[o] - mixed;
+    }
+}
+
+int quant_code_norms(const float* codebook, float* e2, int V, int Cv, hipStream_t stream) {
+    SDVAR_CHECK_ARG(codebook && e2 && V >= 1 && Cv >= 1, "quant_code_norms: bad arguments");
+    hipLaunchKernelGGL(quant_code_norms_kernel, dim3((V + 255) / 256), dim3(256), 0, stream, codebook, e2, V, Cv);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+int quant_nearest(const float* z, int N, int P, const float* codebook, const float* e2, int V, int Cv, long long* ids, int ids_stride, hipStream_t stream) {
+    SDVAR_CHECK_ARG(z && codebook && e2 && ids && N >= 1 && P >= 1 && V >= 1, "quant_nearest: bad arguments (N %d V %d)", N, V);
+    SDVAR_CHECK_ARG(Cv == 32, "quant_nearest: Cvae %d (the kernel holds 32 channels per code)", Cv);
+    SDVAR_CHECK_ARG(((uintptr_t)codebook % 16) == 0, "quant_nearest: the codebook must be 16-byte aligned");
+    hipLaunchKernelGGL(quant_nearest_kernel, dim3((N + QN_ROWS - 1) / QN_ROWS), dim3(256), 0, stream, z, codebook, e2, ids, N, P, ids_stride, V);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// one scale of the residual quantisation.  Wdn_si: area table HW -> pn (null at the last scale, pn == HW).  ids: this scale's first id, row stride ids_stride.
+int quant_encode_stage(float* f_rest, float* f_hat, float* z, float* up_scratch, const float* codebook, const float* e2, const float* Wdn_si, const float* Wup_si,
+                       const float* phi_w, const float* phi_b, long long* ids, int ids_stride, int B, int pn, int HW, int V, int Cv, int last, hipStream_t stream) {
+    SDVAR_CHECK_ARG(f_rest && f_hat && z && up_scratch && codebook && e2 && phi_w && phi_b && ids, "quant_encode: null operand");
+    SDVAR_CHECK_ARG(B > 0 && pn > 0 && pn <= HW && HW <= QMAX_HW && (!last || pn == HW) && (last || (Wdn_si && Wup_si)), "quant_encode: bad sizes pn=%d HW=%d", pn, HW);
+    if (last) {
+        const size_t total = (size_t)B * HW * HW * Cv;
+        hipLaunchKernelGGL(quant_rows_kernel, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)), dim3(256), 0, stream, f_rest, z, B, HW, Cv);
+    } else {
+        const size_t lds_dn = (size_t)(HW * HW + pn * HW) * sizeof(float);
+        hipLaunchKernelGGL(quant_down_kernel, dim3(Cv, B), dim3(256), lds_dn, stream, f_rest, Wdn_si, z, HW, pn, Cv);
+    }
+    SDVAR_LAUNCH_CHECK();
+    SDVAR_TRY_Q(quant_nearest(z, B * pn * pn, pn * pn, codebook, e2, V, Cv, ids, ids_stride, stream));
+    const size_t lds_up = (size_t)(pn * pn + HW * pn) * sizeof(float);
+    hipLaunchKernelGGL(quant_up_kernel, dim3(Cv, B), dim3(256), lds_up, stream, ids, ids_stride, codebook, nullptr, Wup_si, up_scratch, pn, HW, Cv, last);
+    SDVAR_LAUNCH_CHECK();
+    const size_t lds_phi = ((size_t)Cv * HW * HW + 9 * (size_t)Cv) * sizeof(float);
+    if ((HW * HW) % 4 == 0 && lds_phi <= 140 * 1024 && ((uintptr_t)up_scratch % 16) == 0) {
+        static LdsOptIn opt_in;
+        SDVAR_LDS_OPT_IN(opt_in, 140 * 1024, (const void*)quant_phi_rest_kernel<true>);
+        hipLaunchKernelGGL(quant_phi_rest_kernel<true>, dim3(Cv, B), dim3(256), lds_phi, stream, up_scratch, phi_w, phi_b, f_hat, f_rest, HW, Cv);
+    } else hipLaunchKernelGGL(quant_phi_rest_kernel<false>, dim3(Cv, B), dim3(256), 0, stream, up_scratch, phi_w, phi_b, f_hat, f_rest, HW, Cv);
+    SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
 

@@ -812,3 +812,339 @@ int sdvar_op_conv_planes(const uint16_t* x_planes, uint64_t x_plane_stride, uint
 }
 
 }  // extern "C"
+
+// ======================================================================================================== encoder
+// VQVAE image -> f = quant_conv(encoder(img)) (models/vqvae.py:65-67 img_to_idxBl / img_to_reconstructed_img; Encoder at models/basic_vae.py:99-161,
+// Downsample2x :31-37).  Same layouts, kernels and Runner as the decoder; what is new are three operand producers and two weight repacks:
+//     conv_in (Cin = 3)     img_planes_kernel writes the NCHW image as 32-channel planes (channels 3..31 zero); the weights are zero-padded to Cin = 32
+//     Downsample2x          pad (0,1,0,1) + 3x3 stride 2 = a stride-1 3x3 convolution on the space-to-depth tensor X'[oy][ox][(py,px,c)] =
+//                           X[2oy+py][2ox+px][c] (H/2 x W/2 x 4C, s2d_planes_kernel) with the weights W'[ty][tx][(py,px,c)] = W[2ty+py][2tx+px][c]
+//                           at tap offsets (ty, tx) in {0, 1}^2 where 2ty+py <= 2 and 2tx+px <= 2, zero elsewhere and at every offset -1
+//                           (s2d_weight_kernel).  The pad row / column (index H) falls on X''s zero frame.  conv.hip runs unchanged (taps 9, Cin 4C).
+//     f                     rows -> NCHW (nchw_from_rows_kernel)
+namespace sdvar {
+
+// (B, 3, H, W) fp32 image -> planes [npl][1][G + B(H+2)(W+2) + G][32]: channels 0..2 the image, 3..31 zero.  Thread = (padded row, 8 channels).
+__global__ __launch_bounds__(256) void img_planes_kernel(const float* __restrict__ img, uint16_t* __restrict__ outp, size_t ops, int B, int H, int W, int G, int pfmt) {
+    const int w2 = W + 2, h2 = H + 2;
+    const size_t R = (size_t)B * h2 * w2 + 2 * (size_t)G, total = R * 4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i >> 2;
+        const int c8 = (int)(i & 3);
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (c8 == 0 && r >= (size_t)G && r < (size_t)G + (size_t)B * h2 * w2) {
+            const size_t row = r - G;
+            const int x = (int)(row % w2) - 1, y = (int)((row / w2) % h2) - 1, b = (int)(row / ((size_t)w2 * h2));
+            if (x >= 0 && x < W && y >= 0 && y < H) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] = img[(((size_t)b * 3 + c) * H + y) * W + x];
+            }
+        }
+        const size_t o = r * 32 + 8 * c8;
+        store_planes4(outp, ops, o, v, pfmt);
+        store_planes4(outp, ops, o + 4, v + 4, pfmt);
+    }
+}
+
+// rows [B H W][C] of X -> planes [npl][4C/32][G + B(H/2+2)(W/2+2) + G][32] of X' (above), channel k = (2 py + px) C + c.  H, W even, C % 8 == 0.
+__global__ __launch_bounds__(256) void s2d_planes_kernel(const float* __restrict__ in, uint16_t* __restrict__ outp, size_t ops, int B, int C, int H, int W, int G, int pfmt) {
+    const int Ho = H >> 1, Wo = W >> 1, w2 = Wo + 2, h2 = Ho + 2, C4 = 4 * C, c8n = C4 >> 3;
+    const size_t Mo = (size_t)B * h2 * w2, R = Mo + 2 * (size_t)G, total = R * c8n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / c8n;
+        const int c8 = (int)(i - r * c8n);
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (r >= (size_t)G && r < (size_t)G + Mo) {
+            const size_t row = r - G;
+            const int x = (int)(row % w2) - 1, y = (int)((row / w2) % h2) - 1, b = (int)(row / ((size_t)w2 * h2));
+            if (x >= 0 && x < Wo && y >= 0 && y < Ho) {
+                const int k = 8 * c8, ph = k / C, c = k - ph * C, py = ph >> 1, px = ph & 1;
+                const float* p = in + (((size_t)b * H + 2 * y + py) * W + 2 * x + px) * C + c;
+                const f32x4 a0 = *reinterpret_cast<const f32x4*>(p), a1 = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { v[e] = a0[e]; v[4 + e] = a1[e]; }
+            }
+        }
+        const size_t o = ((size_t)(c8 >> 2) * R + r) * 32 + 8 * (c8 & 3);
+        store_planes4(outp, ops, o, v, pfmt);
+        store_planes4(outp, ops, o + 4, v + 4, pfmt);
+    }
+}
+
+// Downsample2x weight (Cout, C, 3, 3) -> the 3x3 weight (Cout, 4C, 3, 3) over X' (above)
+__global__ __launch_bounds__(256) void s2d_weight_kernel(const float* __restrict__ w, float* __restrict__ w2, int Cout, int C) {
+    const size_t total = (size_t)Cout * 4 * C * 9;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int tap = (int)(i % 9), dy = tap / 3 - 1, dx = tap % 3 - 1;
+        const int k = (int)((i / 9) % (4 * (size_t)C)), ph = k / C, c = k - ph * C, py = ph >> 1, px = ph & 1;
+        const size_t co = i / ((size_t)9 * 4 * C);
+        const int ky = 2 * dy + py, kx = 2 * dx + px;
+        w2[i] = (dy >= 0 && dx >= 0 && ky <= 2 && kx <= 2) ? w[((co * C + c) * 3 + ky) * 3 + kx] : 0.f;
+    }
+}
+
+// (Cout, cin, 3, 3) -> (Cout, cin_pad, 3, 3), zero channels appended
+__global__ __launch_bounds__(256) void pad_cin_weight_kernel(const float* __restrict__ w, float* __restrict__ w2, int Cout, int cin, int cin_pad) {
+    const size_t total = (size_t)Cout * cin_pad * 9;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int tap = (int)(i % 9), c = (int)((i / 9) % cin_pad);
+        const size_t co = i / ((size_t)9 * cin_pad);
+        w2[i] = c < cin ? w[(co * cin + c) * 9 + tap] : 0.f;
+    }
+}
+
+// channel-last rows [B H W][C] -> (B, C, H, W)
+__global__ __launch_bounds__(256) void nchw_from_rows_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int C, int H, int W) {
+    const size_t total = (size_t)B * C * H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W), y = (int)((i / W) % H), c = (int)((i / ((size_t)W * H)) % C), b = (int)(i / ((size_t)W * H * C));
+        out[i] = in[(((size_t)b * H + y) * W + x) * C + c];
+    }
+}
+
+static unsigned grid_of(size_t total) { const size_t g = (total + 255) / 256; return (unsigned)(g < 8192 ? (g ? g : 1) : 8192); }
+
+static int launch_img_planes(const float* img, uint16_t* outp, size_t ops, int B, int H, int W, int G, int pfmt, hipStream_t s) {
+    SDVAR_CHECK_ARG(img && outp && B >= 1 && H >= 1 && W >= 1 && G >= W + 3, "img_planes: bad arguments (B %d H %d W %d guard %d)", B, H, W, G);
+    SDVAR_CHECK_ARG(pfmt == PLANES_F16X2 || pfmt == PLANES_BF16X3, "img_planes: plane format %d", pfmt);
+    SDVAR_CHECK_ARG(ops >= (size_t)B * (H + 2) * (W + 2) * 32 + 64 * (size_t)G, "img_planes: plane stride %zu too small", ops);
+    hipLaunchKernelGGL(img_planes_kernel, dim3(grid_of(((size_t)B * (H + 2) * (W + 2) + 2 * (size_t)G) * 4)), dim3(256), 0, s, img, outp, ops, B, H, W, G, pfmt);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+static int launch_s2d_planes(const float* in, uint16_t* outp, size_t ops, int B, int C, int H, int W, int G, int pfmt, hipStream_t s) {
+    SDVAR_CHECK_ARG(in && outp && B >= 1 && C >= 8 && C % 8 == 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && G >= W / 2 + 3,
+                    "s2d_planes: bad arguments (B %d C %d H %d W %d guard %d)", B, C, H, W, G);
+    SDVAR_CHECK_ARG(pfmt == PLANES_F16X2 || pfmt == PLANES_BF16X3, "s2d_planes: plane format %d", pfmt);
+    const size_t R = (size_t)B * (H / 2 + 2) * (W / 2 + 2) + 2 * (size_t)G;
+    SDVAR_CHECK_ARG(ops >= R * 4 * C, "s2d_planes: plane stride %zu too small (need %zu)", ops, R * 4 * C);
+    hipLaunchKernelGGL(s2d_planes_kernel, dim3(grid_of(R * (4 * C / 8))), dim3(256), 0, s, in, outp, ops, B, C, H, W, G, pfmt);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+int s2d_weights(const float* w, float* w2, int Cout, int C, hipStream_t s) {
+    SDVAR_CHECK_ARG(w && w2 && Cout >= 1 && C >= 1, "s2d_weights: bad arguments");
+    hipLaunchKernelGGL(s2d_weight_kernel, dim3(grid_of((size_t)Cout * 4 * C * 9)), dim3(256), 0, s, w, w2, Cout, C);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+}  // namespace sdvar
+
+namespace {
+
+struct EncLevel { std::vector<ResW> blocks; std::vector<AttnW> attns; ConvW down; bool has_down = false; };
+
+}  // namespace
+
+struct sdvar_vae_enc {
+    sdvar_vae* w = nullptr;               // workspaces, plane format and owned weight copies (the decoder object's fields; its layer lists stay empty)
+    sdvar_vae_desc d;
+    int nlev = 0, Himg = 0;
+    ConvW conv_in, conv_out, quant_conv;
+    std::vector<EncLevel> levels;          // level 0 (image resolution) first
+    ResW mid1, mid2; AttnW mid_attn;
+    NormW norm_out;
+    bool bound = false;
+};
+
+extern "C" {
+
+int sdvar_vae_enc_create(const sdvar_vae_desc* desc, sdvar_vae_enc_t** out) {
+    SDVAR_CHECK_ARG(desc && out, "vae_enc_create: null argument");
+    *out = nullptr;
+    SDVAR_CHECK_ARG(desc->n_mult >= 1 && desc->n_mult <= 8 && desc->num_res_blocks >= 1 && desc->max_batch >= 1 && desc->latent_hw >= 1, "vae_enc_create: bad descriptor");
+    SDVAR_CHECK_ARG(desc->z_channels % 32 == 0 && desc->ch % 32 == 0, "vae_enc_create: channel counts must be multiples of 32 (ch=%d z=%d)", desc->ch, desc->z_channels);
+    for (int i = 0; i < desc->n_mult; ++i) {
+        const int c = desc->ch * desc->ch_mult[i];
+        SDVAR_CHECK_ARG(c <= 640 * 2 && 320 % (c / 4) == 0, "vae_enc_create: width %d unsupported by the GroupNorm kernel ((C/4) must divide 320)", c);
+    }
+    SDVAR_CHECK_ARG(desc->plane_format == 0 || desc->plane_format == PLANES_F16X2 || desc->plane_format == PLANES_BF16X3, "vae_enc_create: plane_format %d (0 / 2 = f16x2, 3 = bf16x3)", desc->plane_format);
+    const int B = desc->max_batch, Himg = desc->latent_hw << (desc->n_mult - 1);
+    SDVAR_CHECK_ARG((size_t)B * (Himg + 2) * (Himg + 2) * 640 < ((size_t)1 << 31), "vae_enc_create: batch %d at %d^2 exceeds the 32-bit index range of the plane producers", B, Himg);
+    sdvar_vae_enc* e = new sdvar_vae_enc();
+    e->d = *desc; e->nlev = desc->n_mult; e->Himg = Himg;
+    sdvar_vae* v = e->w = new sdvar_vae();
+    v->d = *desc; v->nlev = desc->n_mult; v->H0 = desc->latent_hw;
+    v->pfmt = desc->plane_format == PLANES_BF16X3 ? PLANES_BF16X3 : PLANES_F16X2; v->npl = v->pfmt == PLANES_BF16X3 ? 3 : 2;
+    // largest fp32 activation / plane tensors: level lv runs at Himg >> lv with width ch*mult[lv]; its first block reads the previous width, its
+    // downsample convolution reads the space-to-depth planes (4C channels at half the side); the deepest level holds the qkv rows (3C)
+    size_t fmax_ = 0, pmax = (size_t)plane_rows(B, Himg, Himg) * 32;
+    int cprev = desc->ch;
+    for (int lv = 0; lv < desc->n_mult; ++lv) {
+        const int H = Himg >> lv, c = desc->ch * desc->ch_mult[lv], cm = c > cprev ? c : cprev;
+        const size_t M = (size_t)B * H * H;
+        const size_t cf = (lv == desc->n_mult - 1) ? (size_t)3 * cm : (size_t)cm;
+        if (M * cf > fmax_) fmax_ = M * cf;
+        if (plane_rows(B, H, H) * cm > pmax) pmax = plane_rows(B, H, H) * cm;
+        if (lv != desc->n_mult - 1 && plane_rows(B, H / 2, H / 2) * 4 * c > pmax) pmax = plane_rows(B, H / 2, H / 2) * 4 * c;
+        cprev = c;
+    }
+    v->f_floats = fmax_; v->p1_elems = v->npl * pmax; v->p2_elems = v->npl * pmax;
+    v->ws_floats = (size_t)64 << 20;
+    if (vmalloc(&v->fa, v->f_floats) || vmalloc(&v->fb, v->f_floats) || vmalloc(&v->fc, v->f_floats) || vmalloc(&v->p1, v->p1_elems) ||
+        vmalloc(&v->p2, v->p2_elems) || vmalloc(&v->ws, v->ws_floats) || vmalloc(&v->stats, (size_t)B * 64) ||
+        vmalloc(&v->part, (size_t)B * ((size_t)Himg * Himg / 256 + 64) * 32 * 2)) {
+        sdvar_vae_enc_destroy(e);
+        return SDVAR_ERR_HIP;
+    }
+    *out = e;
+    return SDVAR_OK;
+}
+
+int sdvar_vae_enc_destroy(sdvar_vae_enc_t* e) {
+    if (!e) return SDVAR_OK;
+    if (e->w) sdvar_vae_destroy(e->w);
+    delete e;
+    return SDVAR_OK;
+}
+
+int sdvar_vae_enc_tensor_count(const sdvar_vae_desc* d) {
+    if (!d || d->n_mult < 1 || d->n_mult > 8) return -1;
+    int n = 2;                                             // encoder.conv_in
+    int cprev = d->ch;
+    for (int lv = 0; lv < d->n_mult; ++lv) {
+        const int c = d->ch * d->ch_mult[lv];
+        for (int i = 0; i < d->num_res_blocks; ++i) {
+            n += 8 + (cprev != c ? 2 : 0);
+            cprev = c;
+            if (lv == d->n_mult - 1) n += 6;
+        }
+        if (lv != d->n_mult - 1) n += 2;
+    }
+    n += 8 + 6 + 8;                                        // mid.block_1, mid.attn_1, mid.block_2
+    return n + 2 + 2 + 2;                                  // norm_out, conv_out, quant_conv
+}
+
+}  // extern "C"
+
+namespace {
+
+struct EncBinder : Binder {
+    void conv_in(ConvW& c, int cout) {                     // (cout, 3, 3, 3) -> zero-padded to 32 input channels
+        const float* w = next(); const float* b = next();
+        if (rc || !w || !b) { rc = SDVAR_ERR_ARG; return; }
+        float* w32 = nullptr;
+        if (hipMalloc((void**)&w32, (size_t)cout * 32 * 9 * sizeof(float)) != hipSuccess) { rc = SDVAR_ERR_HIP; return; }
+        v->owned.push_back(w32);
+        hipLaunchKernelGGL(pad_cin_weight_kernel, dim3(grid_of((size_t)cout * 32 * 9)), dim3(256), 0, s, w, w32, cout, 3, 32);
+        if (hipGetLastError() != hipSuccess) { rc = SDVAR_ERR_HIP; return; }
+        packed(c, w32, b, 32, cout);
+    }
+    void down(ConvW& c, int ch) {                          // Downsample2x: the space-to-depth weight (above)
+        const float* w = next(); const float* b = next();
+        if (rc || !w || !b) { rc = SDVAR_ERR_ARG; return; }
+        float* w4 = nullptr;
+        if (hipMalloc((void**)&w4, (size_t)ch * 4 * ch * 9 * sizeof(float)) != hipSuccess) { rc = SDVAR_ERR_HIP; return; }
+        v->owned.push_back(w4);
+        const int r = s2d_weights(w, w4, ch, ch, s);
+        if (r) { rc = r; return; }
+        packed(c, w4, b, 4 * ch, ch);
+    }
+    void packed(ConvW& c, const float* w, const float* b, int cin, int cout) {     // a 3x3 weight already in device fp32 -> planes
+        c.cin = cin; c.cout = cout; c.taps = 9; c.bias = b;
+        c.wps = (size_t)9 * cin * cout;
+        uint16_t* p = nullptr;
+        if (hipMalloc((void**)&p, v->npl * c.wps * sizeof(uint16_t)) != hipSuccess) { rc = SDVAR_ERR_HIP; return; }
+        v->owned.push_back(p);
+        c.wp = p;
+        int r = scale_of(c, w, c.wps);
+        if (!r) r = conv_weight_planes(w, p, cout, cin, 9, c.wps, v->pfmt, c.wsc, s);
+        if (r) rc = r;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int sdvar_vae_enc_bind(sdvar_vae_enc_t* e, const float* const* tensors, int32_t n_tensors, void* stream) {
+    SDVAR_CHECK_ARG(e && tensors, "vae_enc_bind: null argument");
+    SDVAR_CHECK_ARG(n_tensors == sdvar_vae_enc_tensor_count(&e->d), "vae_enc_bind: expected %d tensors, got %d", sdvar_vae_enc_tensor_count(&e->d), n_tensors);
+    for (int i = 0; i < n_tensors; ++i) SDVAR_CHECK_ARG(tensors[i], "vae_enc_bind: tensor %d is null", i);
+    sdvar_vae* v = e->w;
+    for (void* p : v->owned) (void)hipFree(p);
+    v->owned.clear(); e->levels.clear(); e->bound = false;
+    const sdvar_vae_desc& d = e->d;
+    EncBinder b{};
+    b.v = v; b.t = tensors; b.n = n_tensors; b.pos = 0; b.s = (hipStream_t)stream; b.rc = SDVAR_OK;
+    b.conv_in(e->conv_in, d.ch);
+    int cprev = d.ch;
+    for (int lv = 0; lv < d.n_mult; ++lv) {
+        EncLevel L;
+        const int c = d.ch * d.ch_mult[lv];
+        for (int i = 0; i < d.num_res_blocks; ++i) {
+            ResW r; b.res(r, cprev, c); L.blocks.push_back(r); cprev = c;
+            if (lv == d.n_mult - 1) { AttnW a; b.attn(a, c); L.attns.push_back(a); }
+        }
+        L.has_down = lv != d.n_mult - 1;
+        if (L.has_down) b.down(L.down, c);
+        e->levels.push_back(L);
+    }
+    b.res(e->mid1, cprev, cprev); b.attn(e->mid_attn, cprev); b.res(e->mid2, cprev, cprev);
+    b.norm(e->norm_out, cprev);
+    b.conv(e->conv_out, cprev, d.z_channels, 9);
+    b.conv(e->quant_conv, d.z_channels, d.z_channels, 9);
+    if (b.rc) { set_error("vae_enc_bind: failed while binding tensor %d", b.pos); return b.rc; }
+    e->bound = true;
+    return SDVAR_OK;
+}
+
+// f (B, z, h, h) = quant_conv(encoder(img (B, 3, h << (n_mult-1), same)))          models/vqvae.py:66 + basic_vae.py:144-161
+int sdvar_vae_enc_encode(sdvar_vae_enc_t* e, const float* img, int32_t B, float* f, void* stream) {
+    SDVAR_CHECK_ARG(e && img && f, "vae_enc_encode: null argument");
+    SDVAR_CHECK_ARG(e->bound, "vae_enc_encode: weights not bound");
+    SDVAR_CHECK_ARG(B >= 1 && B <= e->d.max_batch, "vae_enc_encode: batch %d exceeds max_batch %d", B, e->d.max_batch);
+    sdvar_vae* v = e->w;
+    hipStream_t s = (hipStream_t)stream;
+    Runner r{v, B, s, e->Himg, v->fa, v->fb, v->fc};
+    size_t ops, rows; int G;
+    {                                                                                      // conv_in on the 32-channel image planes
+        G = guard_rows(r.H); rows = plane_rows(B, r.H, r.H); ops = rows * 32;
+        SDVAR_CHECK_ARG(v->npl * ops <= v->p1_elems, "vae_enc: plane buffer too small");
+        VAE_TRY(launch_img_planes(img, v->p1, ops, B, r.H, r.H, G, v->pfmt, s));
+        VAE_TRY(r.conv(e->conv_in, v->p1, ops, rows, G, nullptr, r.x));
+    }
+    for (const EncLevel& L : e->levels) {
+        for (size_t i = 0; i < L.blocks.size(); ++i) {
+            VAE_TRY(r.resblock(L.blocks[i]));
+            if (i < L.attns.size()) VAE_TRY(r.attnblock(L.attns[i]));
+        }
+        if (L.has_down) {                                                                  // Downsample2x on the space-to-depth planes
+            const int C = L.down.cout, Ho = r.H / 2;
+            G = guard_rows(Ho); rows = plane_rows(B, Ho, Ho); ops = rows * (size_t)(4 * C);
+            SDVAR_CHECK_ARG(v->npl * ops <= v->p1_elems, "vae_enc: plane buffer too small");
+            VAE_TRY(launch_s2d_planes(r.x, v->p1, ops, B, C, r.H, r.H, G, v->pfmt, s));
+            r.stats_src = nullptr;
+            r.H = Ho;
+            VAE_TRY(r.conv(L.down, v->p1, ops, rows, G, nullptr, r.h));
+            float* tmp = r.x; r.x = r.h; r.h = tmp;
+        }
+    }
+    VAE_TRY(r.resblock(e->mid1)); VAE_TRY(r.attnblock(e->mid_attn)); VAE_TRY(r.resblock(e->mid2));
+    const int z = e->d.z_channels;
+    VAE_TRY(r.prep(r.x, e->norm_out.C, &e->norm_out, 1, 0, v->p1, v->p1_elems, &ops, &rows, &G));       // norm_out + SiLU + conv_out
+    VAE_TRY(r.conv(e->conv_out, v->p1, ops, rows, G, nullptr, r.h));
+    VAE_TRY(r.prep(r.h, z, nullptr, 0, 0, v->p1, v->p1_elems, &ops, &rows, &G));                       // quant_conv
+    VAE_TRY(r.conv(e->quant_conv, v->p1, ops, rows, G, nullptr, r.t));
+    const size_t total = r.M() * z;
+    hipLaunchKernelGGL(nchw_from_rows_kernel, dim3(grid_of(total)), dim3(256), 0, s, r.t, f, B, z, r.H, r.H);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+/* single operators for the parity tests */
+int sdvar_op_vae_img_planes(const float* img, uint16_t* planes, uint64_t plane_stride, int32_t plane_format, int32_t B, int32_t H, int32_t W, int32_t guard, void* stream) {
+    return launch_img_planes(img, planes, (size_t)plane_stride, B, H, W, guard, plane_format, (hipStream_t)stream);
+}
+int sdvar_op_vae_s2d_planes(const float* in, uint16_t* planes, uint64_t plane_stride, int32_t plane_format, int32_t B, int32_t C, int32_t H, int32_t W, int32_t guard,
+                            void* stream) {
+    return launch_s2d_planes(in, planes, (size_t)plane_stride, B, C, H, W, guard, plane_format, (hipStream_t)stream);
+}
+int sdvar_op_vae_s2d_weights(const float* w, float* w_s2d, int32_t Cout, int32_t C, void* stream) {
+    return s2d_weights(w, w_s2d, Cout, C, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -78,12 +78,18 @@ _SIGNATURES = {
     "sdvar_quant_next": (_I, [_P, _I, _P, _I, _P, _P, _I, _P]),
     "sdvar_quant_next_from": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P]),
     "sdvar_quant_next_h": (_I, [_P, _I, _P, _P, _P, _I, _P]),
+    "sdvar_quant_encode": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "sdvar_gumbel_mix": (_I, [_P, _P, _I, _I, _D, _D, _P, _U64, _U32, _U32, _P, _P]),
     "sdvar_vae_create": (_I, [C.POINTER(_VaeDesc), C.POINTER(_P)]),
     "sdvar_vae_destroy": (_I, [_P]),
     "sdvar_vae_tensor_count": (_I, [C.POINTER(_VaeDesc)]),
     "sdvar_vae_bind": (_I, [_P, C.POINTER(_P), _I, _P]),
     "sdvar_vae_decode": (_I, [_P, _P, _I, _P, _P]),
+    "sdvar_vae_enc_create": (_I, [C.POINTER(_VaeDesc), C.POINTER(_P)]),
+    "sdvar_vae_enc_destroy": (_I, [_P]),
+    "sdvar_vae_enc_tensor_count": (_I, [C.POINTER(_VaeDesc)]),
+    "sdvar_vae_enc_bind": (_I, [_P, C.POINTER(_P), _I, _P]),
+    "sdvar_vae_enc_encode": (_I, [_P, _P, _I, _P, _P]),
     "sdvar_cfg_sample": (_I, [_P, _I, _I, _I, _D, _I, _D, _P, _U64, _U32, _U32, _P, _I, _P, _P]),
     "sdvar_verify_accept": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _P, _P, _P]),
     "sdvar_cfg_combine": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _P]),
@@ -99,6 +105,10 @@ _SIGNATURES = {
     "sdvar_op_conv_weight_planes": (_I, [_P, _P, _I, _I, _I, _U64, _I, _P, _P]),
     "sdvar_op_vae_prep": (_I, [_P, _P, _P, _P, _P, _U64, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sdvar_op_conv_planes": (_I, [_P, _U64, _U64, _I, _P, _U64, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _U64, _I, _P]),
+    "sdvar_op_vae_img_planes": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P]),
+    "sdvar_op_vae_s2d_planes": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _I, _P]),
+    "sdvar_op_vae_s2d_weights": (_I, [_P, _P, _I, _I, _P]),
+    "sdvar_op_quant_nearest": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     "sdvar_op_noise_fill": (_I, [_P, _I, _I, _I, _U64, _U32, _U32, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
     "sdvar_debug_set_gemm_stamps": (_I, [_P]),
@@ -300,6 +310,20 @@ class QuantCtx:
         """The same from feature vectors h (B, pn^2, Cvae) instead of ids (more_smooth=True, var.py:206-210)."""
         _check(self.lib.sdvar_quant_next_h(self.h, si, _ptr(h), _ptr(f_hat), _ptr(nxt) if nxt is not None else None, B, _stream()))
 
+    def encode(self, f: torch.Tensor, per_scale: bool = False):
+        """f_to_idxBl_or_fhat (quant.py:135-166, using_znorm=False) of f (B, Cvae, HW, HW) on the device -> (ids (B, L) int64, final f_hat,
+        f_hat after every scale (S, B, Cvae, HW, HW) or None)."""
+        B, HW = f.shape[0], self.lad.patch_nums[-1]
+        if f.dtype != torch.float32 or not f.is_contiguous() or f.device != self.device:
+            f = f.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(f.shape[1:]) != (self.Cv, HW, HW) or B > self.max_batch:
+            raise SdvarError(f"encode: f {tuple(f.shape)} does not fit (max_batch {self.max_batch}, {self.Cv} x {HW}^2)")
+        ids = torch.empty(B, self.lad.L, device=self.device, dtype=torch.int64)
+        f_hat = torch.empty_like(f)
+        ps = torch.empty(self.lad.S, *f.shape, device=self.device, dtype=torch.float32) if per_scale else None
+        _check(self.lib.sdvar_quant_encode(self.h, _ptr(f), B, _ptr(ids), _ptr(f_hat), _ptr(ps), _stream()))
+        return ids, f_hat, ps
+
     def gumbel_mix(self, masked: torch.Tensor, B: int, l: int, ratio: float, tau: float, e: Optional[torch.Tensor], seed: int, draw: int, image_offset: int,
                    h_out: torch.Tensor):
         """var.py:206-208 + helpers.py:22-36: soft codebook mix of the masked CFG logits under gumbel noise -> h (B, l, Cvae)."""
@@ -381,6 +405,80 @@ class VaeCtx:
     def close(self):
         if self.h:
             self.lib.sdvar_vae_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VaeEncCtx:
+    """sdvar_vae_enc_t from the VQVAE state_dict: f = quant_conv(encoder(img)) (vqvae.py:66) as hand-written HIP (csrc/conv.hip, csrc/vae.hip)."""
+
+    def __init__(self, vae_sd: Dict[str, torch.Tensor], max_batch: int, device, latent_hw: int = 16, ch: Optional[int] = None,
+                 ch_mult: Sequence[int] = (1, 1, 2, 2, 4), num_res_blocks: int = 2, conv_mode: Optional[str] = None):
+        self.lib = load_library()
+        self.device = torch.device(device)
+        if "encoder.conv_in.weight" not in vae_sd:
+            raise SdvarError("VaeEncCtx: the state_dict holds no encoder (a VQVAE built with with_encoder=False)")
+        z = vae_sd["quant_conv.weight"].shape[0]
+        ch = ch if ch is not None else vae_sd["encoder.conv_in.weight"].shape[0]
+        d = _VaeDesc()
+        d.ch, d.z_channels, d.n_mult, d.num_res_blocks, d.max_batch, d.latent_hw = ch, z, len(ch_mult), num_res_blocks, max_batch, latent_hw
+        self.conv_mode = conv_mode or os.environ.get("SDVAR_CONV_MODE", DEFAULT_GEMM_MODE if DEFAULT_GEMM_MODE != "f32" else "f16x2")   # as VaeCtx
+        if self.conv_mode not in ("bf16x3", "f16x2"):
+            raise SdvarError(f"conv_mode {self.conv_mode!r}: expected 'bf16x3' or 'f16x2'")
+        d.plane_format = 3 if self.conv_mode == "bf16x3" else 2
+        for i, m in enumerate(ch_mult):
+            d.ch_mult[i] = m
+        self.desc, self.max_batch, self.latent_hw, self.z = d, max_batch, latent_hw, z
+        self.img_hw = latent_hw << (len(ch_mult) - 1)
+        names = self.tensor_names(vae_sd, ch_mult, num_res_blocks)
+        self.tensors = []                                   # keeps the device copies alive: biases and GroupNorm affine stay borrowed
+        for n in names:
+            self.tensors += [_f32(vae_sd[n + ".weight"], self.device), _f32(vae_sd[n + ".bias"], self.device)]
+        want = self.lib.sdvar_vae_enc_tensor_count(C.byref(d))
+        if want != len(self.tensors):
+            raise SdvarError(f"VQVAE encoder layout mismatch: the library expects {want} tensors, the state_dict walk found {len(self.tensors)}")
+        self.h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib.sdvar_vae_enc_create(C.byref(d), C.byref(self.h)))
+            arr = (_P * len(self.tensors))(*[t.data_ptr() for t in self.tensors])
+            _check(self.lib.sdvar_vae_enc_bind(self.h, arr, len(self.tensors), _stream()))
+
+    @staticmethod
+    def tensor_names(vae_sd, ch_mult: Sequence[int] = (1, 1, 2, 2, 4), num_res_blocks: int = 2):
+        """Module prefixes (each contributes .weight then .bias) in the order sdvar_vae_enc_bind consumes them (include/sdvar_hip.h)."""
+        names = ["encoder.conv_in"]
+        res = lambda p, sc: [p + ".norm1", p + ".conv1", p + ".norm2", p + ".conv2"] + ([p + ".nin_shortcut"] if sc else [])
+        att = lambda p: [p + ".norm", p + ".qkv", p + ".proj_out"]
+        for lv in range(len(ch_mult)):
+            for i in range(num_res_blocks):
+                p = f"encoder.down.{lv}.block.{i}"
+                names += res(p, p + ".nin_shortcut.weight" in vae_sd)
+                if lv == len(ch_mult) - 1:
+                    names += att(f"encoder.down.{lv}.attn.{i}")
+            if lv != len(ch_mult) - 1:
+                names.append(f"encoder.down.{lv}.downsample.conv")
+        names += res("encoder.mid.block_1", False) + att("encoder.mid.attn_1") + res("encoder.mid.block_2", False)
+        return names + ["encoder.norm_out", "encoder.conv_out", "quant_conv"]
+
+    def encode(self, img: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img (B, 3, H, W) fp32 on the device -> f (B, Cvae, H/16, W/16); runs on torch's current stream."""
+        B = img.shape[0]
+        if img.dtype != torch.float32 or not img.is_contiguous() or img.device != self.device:
+            img = img.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(img.shape[1:]) != (3, self.img_hw, self.img_hw) or B > self.max_batch:
+            raise SdvarError(f"encode: img {tuple(img.shape)} does not fit (max_batch {self.max_batch}, 3 x {self.img_hw}^2)")
+        if out is None:
+            out = torch.empty(B, self.z, self.latent_hw, self.latent_hw, device=self.device, dtype=torch.float32)
+        _check(self.lib.sdvar_vae_enc_encode(self.h, _ptr(img), B, _ptr(out), _stream()))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.sdvar_vae_enc_destroy(self.h); self.h = C.c_void_p()
 
     def __del__(self):
         try:

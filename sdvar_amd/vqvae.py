@@ -4,11 +4,16 @@ The quantizer tensors (codebook, shared Phi convs) feed sdvar_amd/csrc/quant.hip
 (/root/reference/models/vqvae.py:62-63, models/basic_vae.py:163-226) runs as hand-written HIP
 (csrc/conv.hip, csrc/vae.hip) through engine.VaeCtx.  The nn.Module tree below exists for the parameter names only - they follow
 the upstream checkpoint `vae_ch160v4096z32.pth` so it loads unchanged.  No module here has a forward(): there is no torch math in this package
-(the PyTorch decoder the GPU parity tests compare against lives in tests/torch_ref.py).  The encoder is parameters only (sampling never encodes).
+(the PyTorch decoder the GPU parity tests compare against lives in tests/torch_ref.py).
+
+The image side (vqvae.py:65-90, quant.py:107-184: img_to_idxBl, img_to_reconstructed_img, idxBl_to_img, embed_to_img,
+f_to_idxBl_or_fhat, embed_to_fhat, idxBl_to_var_input) runs on HIP as well: the encoder + quant_conv through engine.VaeEncCtx
+(csrc/vae.hip), the multi-scale residual quantisation through engine.QuantCtx.encode (csrc/quant.hip).  GPU tensors only.  Not supported
+(SdvarError): using_znorm=True, non-square (ph, pw) patch tuples, all_to_max_scale=False, a VQVAE built with with_encoder=False.
 """
 from __future__ import annotations
 
-from typing import Sequence
+from typing import List, Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
@@ -68,7 +73,7 @@ class Decoder(nn.Module):
 
 
 class Encoder(nn.Module):
-    """Parameters only (state_dict compatibility); sampling never encodes."""
+    """Parameters only (state_dict names); the arithmetic is engine.VaeEncCtx (csrc/vae.hip)."""
     def __init__(self, ch, ch_mult, nrb, z):
         super().__init__()
         nres = len(ch_mult)
@@ -107,9 +112,11 @@ class _PhiOne(nn.Module):           # PhiShared (quant.py:209-216): quant_resi.q
 class Quantizer(nn.Module):
     """quantize.* tensors of the checkpoint (models/quant.py:15-43) in the layout `share_quant_resi` selects there (quant.py:27-32): 0 = one Phi per scale
     (PhiNonShared, an nn.ModuleList: quant_resi.<k>), 1 = one Phi for all (PhiShared), >= 2 = partially shared.  The arithmetic lives in csrc/quant.hip."""
-    def __init__(self, vocab_size, Cvae, v_patch_nums, share_quant_resi=4):
+    def __init__(self, vocab_size, Cvae, v_patch_nums, share_quant_resi=4, using_znorm=False):
         super().__init__()
         self.vocab_size, self.Cvae, self.v_patch_nums = vocab_size, Cvae, tuple(v_patch_nums)
+        self.using_znorm = bool(using_znorm)
+        self._hip_q = None
         if share_quant_resi == 0:
             self.quant_resi = nn.ModuleList([nn.Conv2d(Cvae, Cvae, 3, 1, 1) for _ in range(len(v_patch_nums))])
         elif share_quant_resi == 1:
@@ -119,20 +126,123 @@ class Quantizer(nn.Module):
         self.register_buffer("ema_vocab_hit_SV", torch.zeros(len(v_patch_nums), vocab_size))
         self.embedding = nn.Embedding(vocab_size, Cvae)
 
+    # ------------------------------------------------------------------------------------------- image side on HIP (quant.py:107-184)
+    def _err(self, msg):
+        from . import engine as E
+        return E.SdvarError(msg)
+
+    def _ladder(self, v_patch_nums) -> tuple:
+        out = []
+        for pn in (v_patch_nums or self.v_patch_nums):
+            if not isinstance(pn, int):
+                ph, pw = pn
+                if ph != pw:
+                    raise self._err(f"Quantizer: non-square patch ({ph}, {pw}) is not supported (square ladders only)")
+                pn = ph
+            out.append(int(pn))
+        return tuple(out)
+
+    def _ctx(self, device, B: int, pns: tuple):
+        from . import engine as E
+        if self.using_znorm:
+            raise self._err("Quantizer: using_znorm=True is not supported on HIP (the released checkpoint uses the L2 distance)")
+        ctx = self._hip_q
+        if ctx is None or ctx.device != device or ctx.max_batch < B or tuple(ctx.lad.patch_nums) != pns:
+            if ctx is not None:
+                ctx.close()
+            ctx = self._hip_q = E.QuantCtx(self.state_dict(), pns, B, device, prefix="")
+        return ctx
+
+    def refresh_hip(self):
+        """Drop the HIP quantizer's binding (call after changing the codebook or the Phi convolutions in place)."""
+        if self._hip_q is not None:
+            self._hip_q.close()
+        self._hip_q = None
+
+    def _need_gpu(self, t: torch.Tensor, what: str):
+        if not t.is_cuda:
+            raise self._err(f"Quantizer.{what} runs on HIP and needs GPU tensors")
+
+    @torch.no_grad()
+    def f_to_idxBl_or_fhat(self, f_BChw: torch.Tensor, to_fhat: bool, v_patch_nums=None) -> List[torch.Tensor]:       # quant.py:135-166
+        """Multi-scale residual quantisation of f (B, Cvae, H, W): per scale the (B, pn^2) int64 ids, or (to_fhat) f_hat after that scale."""
+        self._need_gpu(f_BChw, "f_to_idxBl_or_fhat")
+        pns = self._ladder(v_patch_nums)
+        B, _, H, W = f_BChw.shape
+        if pns[-1] != H or pns[-1] != W:
+            raise self._err(f"Quantizer.f_to_idxBl_or_fhat: last patch {pns[-1]} != (H={H}, W={W})")
+        ctx = self._ctx(f_BChw.device, B, pns)
+        ids, _, per_scale = ctx.encode(f_BChw, per_scale=to_fhat)
+        if to_fhat:
+            return [per_scale[si] for si in range(len(pns))]
+        return [ids[:, ctx.lad.begin(si):ctx.lad.cum[si]].contiguous() for si in range(len(pns))]
+
+    @torch.no_grad()
+    def embed_to_fhat(self, ms_h_BChw: List[torch.Tensor], all_to_max_scale=True, last_one=False) -> Union[List[torch.Tensor], torch.Tensor]:   # quant.py:98-123
+        if not all_to_max_scale:
+            raise self._err("Quantizer.embed_to_fhat: all_to_max_scale=False (experimental in the reference) is not supported")
+        self._need_gpu(ms_h_BChw[0], "embed_to_fhat")
+        pns = self.v_patch_nums
+        B, dev = ms_h_BChw[0].shape[0], ms_h_BChw[0].device
+        ctx = self._ctx(dev, B, pns)
+        H = pns[-1]
+        f_hat = torch.zeros(B, self.Cvae, H, H, device=dev, dtype=torch.float32)
+        out = []
+        for si, pn in enumerate(pns):
+            h = ms_h_BChw[si]
+            if tuple(h.shape) != (B, self.Cvae, pn, pn):
+                raise self._err(f"Quantizer.embed_to_fhat: scale {si} has shape {tuple(h.shape)}, expected {(B, self.Cvae, pn, pn)}")
+            h_rows = h.to(dtype=torch.float32).permute(0, 2, 3, 1).contiguous()               # (B, pn^2, Cvae) rows
+            nxt = torch.empty(B, pns[si + 1] ** 2, self.Cvae, device=dev) if si < len(pns) - 1 else None
+            ctx.next_h(si, h_rows, f_hat, nxt, B)
+            if not last_one:
+                out.append(f_hat.clone())
+        return f_hat if last_one else out
+
+    def _ids_fhat(self, ms_idx_Bl: List[torch.Tensor], keep: bool, want_nxt: bool):
+        """f_hat from per-scale ids (quant_next): the list of f_hat after every scale (keep) and / or the next-scale inputs (want_nxt)."""
+        self._need_gpu(ms_idx_Bl[0], "idxBl")
+        pns = self.v_patch_nums
+        B, dev = ms_idx_Bl[0].shape[0], ms_idx_Bl[0].device
+        ctx = self._ctx(dev, B, pns)
+        f_hat = torch.zeros(B, self.Cvae, pns[-1], pns[-1], device=dev, dtype=torch.float32)
+        fs, nxts = [], []
+        n = len(ms_idx_Bl) if keep else len(pns) - 1
+        for si in range(n):
+            ids = ms_idx_Bl[si].to(dtype=torch.int64).contiguous()
+            if tuple(ids.shape) != (B, pns[si] ** 2):
+                raise self._err(f"Quantizer: ids of scale {si} have shape {tuple(ids.shape)}, expected {(B, pns[si] ** 2)}")
+            nxt = torch.empty(B, pns[si + 1] ** 2, self.Cvae, device=dev) if si < len(pns) - 1 else None
+            ctx.next(si, ids, pns[si] ** 2, f_hat, nxt, B)
+            if keep:
+                fs.append(f_hat.clone())
+            if want_nxt:
+                nxts.append(nxt)
+        return fs, nxts
+
+    @torch.no_grad()
+    def idxBl_to_var_input(self, gt_ms_idx_Bl: List[torch.Tensor]) -> Optional[torch.Tensor]:     # quant.py:169-184
+        """Teacher-forcing input: area_down(f_hat, pn_{s+1}) after scales 0 .. S-2, concatenated -> (B, L - pn_0^2, Cvae)."""
+        if len(self.v_patch_nums) < 2:
+            return None
+        _, nxts = self._ids_fhat(gt_ms_idx_Bl, keep=False, want_nxt=True)
+        return torch.cat(nxts, dim=1)
+
 
 class VQVAE(nn.Module):
     def __init__(self, vocab_size=4096, z_channels=32, ch=128, share_quant_resi=4, v_patch_nums: Sequence[int] = (1, 2, 3, 4, 5, 6, 8, 10, 13, 16),
-                 test_mode=True, with_encoder=True, **_unused):
+                 test_mode=True, with_encoder=True, using_znorm=False, **_unused):
         super().__init__()
         self.V = self.vocab_size = vocab_size
         self.Cvae = z_channels
         ch_mult, nrb = (1, 1, 2, 2, 4), 2
-        self._ch_mult, self._nrb, self._hip_ctx = ch_mult, nrb, None
+        self._ch_mult, self._nrb, self._hip_ctx, self._hip_enc = ch_mult, nrb, None, None
+        self.with_encoder = bool(with_encoder)
         if with_encoder:
             self.encoder = Encoder(ch, ch_mult, nrb, z_channels)
         self.decoder = Decoder(ch, ch_mult, nrb, z_channels)
         self.downsample = 2 ** (len(ch_mult) - 1)
-        self.quantize = Quantizer(vocab_size, z_channels, v_patch_nums, share_quant_resi)
+        self.quantize = Quantizer(vocab_size, z_channels, v_patch_nums, share_quant_resi, using_znorm)
         self.quant_conv = nn.Conv2d(z_channels, z_channels, 3, 1, 1)
         self.post_quant_conv = nn.Conv2d(z_channels, z_channels, 3, 1, 1)
         if test_mode:
@@ -155,11 +265,55 @@ class VQVAE(nn.Module):
             ctx = self._hip_ctx = E.VaeCtx(sd, B, f_hat.device, latent_hw=hw, ch_mult=self._ch_mult, num_res_blocks=self._nrb)
         return ctx.decode(f_hat)
 
+    @torch.no_grad()
+    def img_to_f(self, img: torch.Tensor) -> torch.Tensor:
+        """quant_conv(encoder(img)) (vqvae.py:66): (B, 3, H, W) in [-1, 1] -> (B, Cvae, H/16, W/16) on the HIP encoder."""
+        from . import engine as E
+        if not self.with_encoder:
+            raise E.SdvarError("VQVAE: built with with_encoder=False, so it cannot encode images")
+        if not img.is_cuda:
+            raise E.SdvarError("VQVAE image encoding runs on the HIP encoder and needs a GPU tensor (tests/torch_ref_encode.py holds the PyTorch test reference)")
+        B, H, W = img.shape[0], img.shape[-2], img.shape[-1]
+        if img.dim() != 4 or img.shape[1] != 3 or H != W or H % self.downsample:
+            raise E.SdvarError(f"VQVAE: image of shape {tuple(img.shape)}: expected (B, 3, H, H) with H a multiple of {self.downsample}")
+        hw = H // self.downsample
+        ctx = self._hip_enc
+        if ctx is None or ctx.device != img.device or ctx.max_batch < B or ctx.latent_hw != hw:
+            if ctx is not None:
+                ctx.close()
+            sd = {k: v for k, v in self.state_dict().items() if k.startswith(("encoder.", "quant_conv."))}
+            ctx = self._hip_enc = E.VaeEncCtx(sd, B, img.device, latent_hw=hw, ch_mult=self._ch_mult, num_res_blocks=self._nrb)
+        return ctx.encode(img)
+
+    @torch.no_grad()
+    def img_to_idxBl(self, inp_img_no_grad: torch.Tensor, v_patch_nums=None) -> List[torch.Tensor]:           # vqvae.py:65-67
+        return self.quantize.f_to_idxBl_or_fhat(self.img_to_f(inp_img_no_grad), to_fhat=False, v_patch_nums=v_patch_nums)
+
+    @torch.no_grad()
+    def idxBl_to_img(self, ms_idx_Bl: List[torch.Tensor], same_shape: bool, last_one=False) -> Union[List[torch.Tensor], torch.Tensor]:   # vqvae.py:69-76
+        if not same_shape:
+            raise self.quantize._err("VQVAE.idxBl_to_img: same_shape=False (all_to_max_scale=False, experimental in the reference) is not supported")
+        fs, _ = self.quantize._ids_fhat(ms_idx_Bl, keep=True, want_nxt=False)
+        return self.fhat_to_img(fs[-1]) if last_one else [self.fhat_to_img(f) for f in fs]
+
+    @torch.no_grad()
+    def embed_to_img(self, ms_h_BChw: List[torch.Tensor], all_to_max_scale: bool, last_one=False) -> Union[List[torch.Tensor], torch.Tensor]:   # vqvae.py:78-82
+        fs = self.quantize.embed_to_fhat(ms_h_BChw, all_to_max_scale=all_to_max_scale, last_one=last_one)
+        return self.fhat_to_img(fs) if last_one else [self.fhat_to_img(f) for f in fs]
+
+    @torch.no_grad()
+    def img_to_reconstructed_img(self, x: torch.Tensor, v_patch_nums=None, last_one=False) -> Union[List[torch.Tensor], torch.Tensor]:   # vqvae.py:84-90
+        fs = self.quantize.f_to_idxBl_or_fhat(self.img_to_f(x), to_fhat=True, v_patch_nums=v_patch_nums)
+        return self.fhat_to_img(fs[-1]) if last_one else [self.fhat_to_img(f) for f in fs]
+
     def refresh_hip(self):
-        """Drop the HIP decoder's copy of the weights (call after changing decoder parameters in place)."""
+        """Drop the HIP copies of the weights (decoder, encoder, quantizer; call after changing parameters in place)."""
         if self._hip_ctx is not None:
             self._hip_ctx.close()
-        self._hip_ctx = None
+        if self._hip_enc is not None:
+            self._hip_enc.close()
+        self._hip_ctx = self._hip_enc = None
+        self.quantize.refresh_hip()
 
     def load_state_dict(self, state_dict, strict=True, assign=False):  # vqvae.py:92-95
         key = "quantize.ema_vocab_hit_SV"
