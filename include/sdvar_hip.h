@@ -75,6 +75,10 @@ int sdvar_model_begin(sdvar_model_t* m, int32_t B, const int64_t* labels, void* 
 /* The same prologue from the conditioning rows themselves: cond (2B, C) device = `sos` / `cond_BD` as SDVAR.init_param returned it
  * (var.py:580-601) and VAR.autoregressive_infer_cfg_sd_helper1 receives it (var.py:319-345) - no label lookup. */
 int sdvar_model_begin_cond(sdvar_model_t* m, int32_t B, const float* cond, void* stream);
+/* The prologue for R UNPAIRED rows (teacher-forced VAR.forward, var.py:217-259): row r is conditioned on labels[r] (int64 device; num_classes =
+ * unconditional), adaLN rows from the per-class table or, for shared_aln models, the GEMM path.  R <= 2 * max_batch.  Resets the KV cache; the
+ * call's sdvar_stage_forward / sdvar_head_forward / export_prologue then work on R rows, and sdvar_embed_next (the CFG pair) is refused. */
+int sdvar_model_begin_rows(sdvar_model_t* m, int32_t R, const int64_t* labels, void* stream);
 /* the tensors SDVAR.init_param returns (var.py:580-601), copied out of the model object: cond (2B,C), lvl_pos (L,C),
  * first-token map (2B,C); any pointer may be NULL */
 int sdvar_model_export_prologue(sdvar_model_t* m, float* cond, float* lvl_pos, float* first, void* stream);
@@ -93,6 +97,9 @@ int sdvar_embed_next(sdvar_model_t* m, const float* nxt, int32_t s_next, float* 
  * `cur_L` from the stage it is resumed at (var.py:352, 369-371, 385, 389: the skipped stages never advance it), so a call resumed at stage c
  * embeds stage s with the rows begin(s) - begin(c); the mirror of that entry point reproduces it through this call. */
 int sdvar_embed_next_at(sdvar_model_t* m, const float* nxt, int32_t s_next, int32_t pos_begin, float* x, int32_t ltot, int32_t tok_off, void* stream);
+/* Teacher-forcing input of the current call (var.py:230-235), x (R, L, C): token 0 = (class_emb[label] + pos_start) + lvl_pos[0] from the prologue,
+ * token t >= 1 = word_embed(xv[r][t-1]) + lvl_pos[t] with xv (R, L-1, cvae) = VectorQuantizer2.idxBl_to_var_input.  Two launches. */
+int sdvar_embed_teacher(sdvar_model_t* m, const float* xv, float* x, void* stream);
 /* All blocks + head over the stages s0 .. s0+n_stages-1 in ONE pass (var.py:195-197; verify chunk var.py:1051-1055
  * with the mask rows of var.py:108-113 derived from the stage table).  x (R, lsum, C) is the input and is CLOBBERED
  * (it is the residual stream); logits (R, lsum, V).  Requires kv_len == begin(s0); appends lsum keys. */
@@ -205,6 +212,13 @@ int sdvar_verify_accept_ex(const float* logits, int32_t B, int32_t lsum, int32_t
  * scalar ops): the per-stage CFG logits SDVAR.target_verify_batch returns to a caller that drives the reference's step functions itself. */
 int sdvar_cfg_combine(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n_stages, const int32_t* stage_lens /*host*/, const double* t /*host*/,
                       float* out, void* stream);
+/* Validation statistics of VARTrainer.eval_ep (trainer.py:66-75) on logits (B, L, V) fp32 against targets (B, L) int64, one wave64 per token:
+ * nll = lse - logit[target] (fp32; a target outside [0, V) gives NaN and is never read), argmax with the lowest index on ties.  nll_out (B*L) fp32 and
+ * argmax_out (B*L) int64 may be NULL.  sums (4 doubles) = {sum nll, sum nll of the last `tail` tokens of each image, #argmax == target, #tail
+ * correct}, overwritten or (accumulate != 0) added to.  Fixed-order reduction, no atomics: repeated calls are bit-identical.  V % 4 == 0, logits
+ * 16-byte aligned.  Uses a per-host-thread scratch of 4 doubles per 4 tokens (grown on demand). */
+int sdvar_xent_stats(const float* logits, const int64_t* targets, int32_t B, int32_t L, int32_t V, int32_t tail, float* nll_out, int64_t* argmax_out,
+                     double* sums, int32_t accumulate, void* stream);
 
 /* ---- single operators (kernel-level parity tests and micro-benchmarks) ---------------------------------------------- */
 /* out[M,N] = epi(X[M,K] W[N,K]^T + bias); epi 0 bias, 1 bias+GELU(tanh), 2 res + (.)*gate[row / rows_per_gate] */

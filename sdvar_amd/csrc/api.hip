@@ -32,11 +32,13 @@ int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* 
 void debug_set_rowblk(int v);
 int silu_rows(const float* x, float* y, int n, hipStream_t stream);
 int add_row_vector(const float* src, const float* vec, float* out, int rows, int cols, hipStream_t stream);
-int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int B, int num_classes,
+int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int R, int nlab, int num_classes,
                hipStream_t stream);
-int prologue(const long long* labels, const float* cond_in, const float* class_emb, const float* pos_start, const float* lvl_pos, float* cond, float* x0, int B, int C, int num_classes, hipStream_t stream);
+int prologue(const long long* labels, const float* cond_in, const float* class_emb, const float* pos_start, const float* lvl_pos, float* cond, float* x0, int R, int nlab, int C, int num_classes, hipStream_t stream);
 int build_lvl_pos(const float* lvl_embed, const float* pos, const int* stage_of_tok, float* out, int L, int C, hipStream_t stream);
-int embed_next(const float* nxt, const float* Ww, const float* bw, const float* lvl_pos, float* x, int B, int l, int C, int t0, int ltot, int tok_off, hipStream_t stream);
+int embed_next(const float* nxt, const float* Ww, const float* bw, const float* lvl_pos, float* x, int B, int l, int C, int t0, int ltot, int tok_off, int pair, hipStream_t stream);
+int xent_stats(const float* logits, const long long* targets, int B, int L, int V, int tail, float* nll_out, long long* argmax_out, double* sums, int accumulate,
+               hipStream_t stream);
 int attention_f32(const float* q, const void* kc, const void* vc, int kv_f16, float* out, uint16_t* outp, size_t ops, int pfmt, int R, int H, int l, int Lmax, int Ktot, int n_chunk, const int* qbeg, const int* vis, hipStream_t stream);
 int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -167,7 +169,7 @@ struct sdvar_model {
     size_t act_ps;                                // plane stride of xn_p / att_p (elements); hid_p uses 4x
     int* stage_of_tok;
     // run state
-    int B, kv_len;
+    int B, R, kv_len;    // R rows in the current call: 2B (the CFG pair of sdvar_model_begin / _begin_cond; B images) or the unpaired rows of sdvar_model_begin_rows (B = 0)
     int kv_origin;       // token position of the cache's first key (0 except in the hand-off sampler: sdvar_kv_set_origin)
     bool begun;
 };
@@ -246,7 +248,7 @@ int sdvar_model_create(const sdvar_model_desc* desc, sdvar_model_t** out) {
     m->blk.resize(desc->depth);
     for (auto& b : m->blk) memset(&b, 0, sizeof(b));
     m->embed_bound = m->head_bound = m->begun = false;
-    m->B = 0; m->kv_len = 0; m->kv_origin = 0;
+    m->B = 0; m->R = 0; m->kv_len = 0; m->kv_origin = 0;
     const size_t C = m->C, R = m->Rmax, M = R * (size_t)m->lmax;
     std::vector<int> sot(m->L);
     for (int s = 0, t = 0; s < m->S; ++s) for (int i = 0; i < m->lens[s]; ++i) sot[t++] = s;
@@ -375,25 +377,36 @@ static int check_bound(const sdvar_model* m) {
     return SDVAR_OK;
 }
 
-static int model_begin_impl(sdvar_model_t* m, int32_t B, const int64_t* labels, const float* cond_in, void* stream);
+// R rows; rows r < nlab are conditioned on labels[r], the others on the unconditional class (the CFG pair: R = 2B, nlab = B)
+static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int64_t* labels, const float* cond_in, void* stream);
 int sdvar_model_begin(sdvar_model_t* m, int32_t B, const int64_t* labels, void* stream) {
     SDVAR_CHECK_ARG(labels, "model_begin: null labels");
-    return model_begin_impl(m, B, labels, nullptr, stream);
+    SDVAR_CHECK_ARG(m && B >= 1 && B <= m->d.max_batch, "model_begin: B=%d (max %d)", B, m ? m->d.max_batch : 0);
+    SDVAR_TRY(model_begin_impl(m, 2 * B, B, labels, nullptr, stream));
+    m->B = B;
+    return SDVAR_OK;
 }
 int sdvar_model_begin_cond(sdvar_model_t* m, int32_t B, const float* cond, void* stream) {
     SDVAR_CHECK_ARG(cond, "model_begin_cond: null cond");
-    return model_begin_impl(m, B, nullptr, cond, stream);
+    SDVAR_CHECK_ARG(m && B >= 1 && B <= m->d.max_batch, "model_begin: B=%d (max %d)", B, m ? m->d.max_batch : 0);
+    SDVAR_TRY(model_begin_impl(m, 2 * B, B, nullptr, cond, stream));
+    m->B = B;
+    return SDVAR_OK;
 }
-static int model_begin_impl(sdvar_model_t* m, int32_t B, const int64_t* labels, const float* cond_in, void* stream) {
+int sdvar_model_begin_rows(sdvar_model_t* m, int32_t R, const int64_t* labels, void* stream) {
+    SDVAR_CHECK_ARG(labels, "model_begin_rows: null labels");
+    SDVAR_CHECK_ARG(m && R >= 1 && R <= 2 * m->d.max_batch, "model_begin_rows: R=%d rows (max 2 * max_batch = %d)", R, m ? 2 * m->d.max_batch : 0);
+    return model_begin_impl(m, R, R, labels, nullptr, stream);
+}
+static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int64_t* labels, const float* cond_in, void* stream) {
     SDVAR_TRY(check_bound(m));
-    SDVAR_CHECK_ARG(B >= 1 && B <= m->d.max_batch, "model_begin: B=%d (max %d)", B, m->d.max_batch);
     hipStream_t s = (hipStream_t)stream;
     WsScope wsg(m->ws_own);
-    const int C = m->C, R = 2 * B;
-    m->B = B; m->kv_len = 0; m->kv_origin = 0;
+    const int C = m->C;
+    m->B = 0; m->R = R; m->kv_len = 0; m->kv_origin = 0;
     {
         ProfScope ps(7, 0, 0, s);
-        SDVAR_TRY(prologue((const long long*)labels, cond_in, m->class_emb, m->pos_start, m->lvl_pos, m->cond, m->x0, B, C, m->d.num_classes, s));
+        SDVAR_TRY(prologue((const long long*)labels, cond_in, m->class_emb, m->pos_start, m->lvl_pos, m->cond, m->x0, R, nlab, C, m->d.num_classes, s));
         SDVAR_TRY(silu_rows(m->cond, m->cond_silu, R * C, s));
     }
     // adaLN parameters of every block: stage-invariant, computed once per call instead of once per stage - or, for label-conditioned calls, once per BIND:
@@ -412,7 +425,7 @@ static int model_begin_impl(sdvar_model_t* m, int32_t B, const int64_t* labels, 
             m->ada_tab_ready = true;
         }
         ProfScope ps(7, 0, 8.0 * R * (double)row, s);
-        SDVAR_TRY(ada_gather((const long long*)labels, m->ada_tab, row, m->d.depth, C, m->ada, (size_t)m->Rmax * 6 * C, m->ada_head, B, m->d.num_classes, s));
+        SDVAR_TRY(ada_gather((const long long*)labels, m->ada_tab, row, m->d.depth, C, m->ada, (size_t)m->Rmax * 6 * C, m->ada_head, R, nlab, m->d.num_classes, s));
         m->begun = true;
         return SDVAR_OK;
     }
@@ -436,7 +449,7 @@ static int model_begin_impl(sdvar_model_t* m, int32_t B, const int64_t* labels, 
 
 int sdvar_model_place_first(sdvar_model_t* m, float* x, int32_t ltot, void* stream) {
     SDVAR_CHECK_ARG(m && m->begun && x && ltot >= 1, "place_first: model not begun or bad args");
-    SDVAR_HIP(hipMemcpy2DAsync(x, (size_t)ltot * m->C * sizeof(float), m->x0, (size_t)m->C * sizeof(float), (size_t)m->C * sizeof(float), 2 * m->B,
+    SDVAR_HIP(hipMemcpy2DAsync(x, (size_t)ltot * m->C * sizeof(float), m->x0, (size_t)m->C * sizeof(float), (size_t)m->C * sizeof(float), m->R,
                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SDVAR_OK;
 }
@@ -444,7 +457,7 @@ int sdvar_model_place_first(sdvar_model_t* m, float* x, int32_t ltot, void* stre
 int sdvar_model_export_prologue(sdvar_model_t* m, float* cond, float* lvl_pos, float* first, void* stream) {
     SDVAR_CHECK_ARG(m && m->begun, "export_prologue: model not begun");
     hipStream_t s = (hipStream_t)stream;
-    const size_t rc = (size_t)2 * m->B * m->C * sizeof(float);
+    const size_t rc = (size_t)m->R * m->C * sizeof(float);
     if (cond) SDVAR_HIP(hipMemcpyAsync(cond, m->cond, rc, hipMemcpyDeviceToDevice, s));
     if (first) SDVAR_HIP(hipMemcpyAsync(first, m->x0, rc, hipMemcpyDeviceToDevice, s));
     if (lvl_pos) SDVAR_HIP(hipMemcpyAsync(lvl_pos, m->lvl_pos, (size_t)m->L * m->C * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -468,15 +481,35 @@ int sdvar_kv_set_origin(sdvar_model_t* m, int32_t stage) {
 
 int sdvar_embed_next_at(sdvar_model_t* m, const float* nxt, int32_t s_next, int32_t pos_begin, float* x, int32_t ltot, int32_t tok_off, void* stream) {
     SDVAR_CHECK_ARG(m && m->begun && nxt && x, "embed_next: model not begun or null");
+    SDVAR_CHECK_ARG(m->B >= 1, "embed_next: the current call has unpaired rows (sdvar_model_begin_rows): embed them with sdvar_embed_teacher");
     SDVAR_CHECK_ARG(s_next >= 1 && s_next < m->S && tok_off >= 0 && tok_off + m->lens[s_next] <= ltot, "embed_next: stage %d off %d ltot %d", s_next, tok_off, ltot);
     SDVAR_CHECK_ARG(pos_begin >= 0 && pos_begin + m->lens[s_next] <= m->L, "embed_next: position rows %d .. %d outside the table (%d)", pos_begin, pos_begin + m->lens[s_next], m->L);
     ProfScope ps(7, 2.0 * m->B * m->lens[s_next] * 32.0 * m->C, 4.0 * m->lens[s_next] * m->C * (2.0 * m->B + 1.0), (hipStream_t)stream);
-    return embed_next(nxt, m->word_w, m->word_b, m->lvl_pos, x, m->B, m->lens[s_next], m->C, pos_begin, ltot, tok_off, (hipStream_t)stream);
+    return embed_next(nxt, m->word_w, m->word_b, m->lvl_pos, x, m->B, m->lens[s_next], m->C, pos_begin, ltot, tok_off, 1, (hipStream_t)stream);
 }
 
 int sdvar_embed_next(sdvar_model_t* m, const float* nxt, int32_t s_next, float* x, int32_t ltot, int32_t tok_off, void* stream) {
     SDVAR_CHECK_ARG(m && s_next >= 1 && s_next < m->S, "embed_next: stage %d", s_next);
     return sdvar_embed_next_at(m, nxt, s_next, begin_of(m, s_next), x, ltot, tok_off, stream);
+}
+
+int sdvar_embed_teacher(sdvar_model_t* m, const float* xv, float* x, void* stream) {
+    SDVAR_CHECK_ARG(m && m->begun && x && (xv || m->L == 1), "embed_teacher: model not begun or null buffers");
+    hipStream_t s = (hipStream_t)stream;
+    const int R = m->R, L = m->L, C = m->C;
+    ProfScope ps(7, 2.0 * R * (L - 1) * 32.0 * C, 4.0 * (R * (double)L * C + (L - 1.0) * C + R * (L - 1.0) * 32.0), s);
+    // token 0: the prologue's (class_emb[label] + pos_start) + lvl_pos[0] of every row (var.py:230-235)
+    SDVAR_HIP(hipMemcpy2DAsync(x, (size_t)L * C * sizeof(float), m->x0, (size_t)C * sizeof(float), (size_t)C * sizeof(float), R, hipMemcpyDeviceToDevice, s));
+    if (L == 1) return SDVAR_OK;
+    // tokens 1 .. L-1: word_embed(xv[r, t-1]) + lvl_pos[t], one row per image (no CFG pair)
+    return embed_next(xv, m->word_w, m->word_b, m->lvl_pos, x, R, L - 1, C, 1, L, 1, 0, s);
+}
+
+int sdvar_xent_stats(const float* logits, const int64_t* targets, int32_t B, int32_t L, int32_t V, int32_t tail, float* nll_out, int64_t* argmax_out, double* sums,
+                     int32_t accumulate, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(5, 6.0 * B * (double)L * V, 4.0 * B * (double)L * V + 20.0 * B * L, s);
+    return xent_stats(logits, (const long long*)targets, B, L, V, tail, nll_out, (long long*)argmax_out, sums, accumulate, s);
 }
 
 static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream);
@@ -497,7 +530,7 @@ static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n,
     if (m->kv_len != begin_of(m, s0) - m->kv_origin) { set_error("stage_forward: KV cache holds %d keys, stage %d needs %d", m->kv_len, s0, begin_of(m, s0) - m->kv_origin); return SDVAR_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
     WsScope wsg(m->ws_own);
-    const int C = m->C, H = m->H, R = 2 * m->B, V = m->d.vocab;
+    const int C = m->C, H = m->H, R = m->R, V = m->d.vocab;
     int qbeg[SDVAR_MAX_STAGES], vis[SDVAR_MAX_STAGES], lsum = 0;
     double lk = 0;
     for (int j = 0; j < n; ++j) { qbeg[j] = lsum; lsum += m->lens[s0 + j]; vis[j] = m->cum[s0 + j] - m->kv_origin; lk += (double)m->lens[s0 + j] * vis[j]; }
@@ -606,7 +639,7 @@ int sdvar_head_forward(sdvar_model_t* m, const float* x, int32_t l, float* logit
     SDVAR_CHECK_ARG(m->begun && x && logits && l >= 1 && l <= m->lmax, "head_forward: model not begun, null buffers or l=%d > %d", l, m->lmax);
     hipStream_t s = (hipStream_t)stream;
     WsScope wsg(m->ws_own);
-    const int C = m->C, R = 2 * m->B, V = m->d.vocab, M = R * l;
+    const int C = m->C, R = m->R, V = m->d.vocab, M = R * l;
     const double dM = M, dC = C;
     const int GC = M >= 1024 ? 0 : 9;
     const bool P = m->d.gemm_mode >= 1;

@@ -571,16 +571,17 @@ int add_row_vector(const float* src, const float* vec, float* out, int rows, int
     return SDVAR_OK;
 }
 
-// cond (2B, C) = class_emb[label_b] for rows < B, class_emb[num_classes] for rows >= B - or, with cond_in, the caller's rows (VAR.autoregressive_infer_cfg_sd_helper1
-// is handed `sos`, var.py:344-345);  x0 (2B,1,C) = cond + pos_start + lvl_pos[0]
+// cond (R, C) = class_emb[label_r] for rows r < nlab, class_emb[num_classes] for the others (the CFG pair: R = 2B, nlab = B; the unpaired rows of
+// VAR.forward: nlab = R) - or, with cond_in, the caller's rows (VAR.autoregressive_infer_cfg_sd_helper1 is handed `sos`, var.py:344-345);
+// x0 (R,1,C) = cond + pos_start + lvl_pos[0]
 __global__ void prologue_kernel(const long long* __restrict__ labels, const float* __restrict__ cond_in, const float* __restrict__ class_emb, const float* __restrict__ pos_start,
-                                const float* __restrict__ lvl_pos, float* __restrict__ cond, float* __restrict__ x0, int B, int C, int num_classes) {
+                                const float* __restrict__ lvl_pos, float* __restrict__ cond, float* __restrict__ x0, int nlab, int C, int num_classes) {
     const int r = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     float e;
     if (cond_in) e = cond_in[(size_t)r * C + c];
     else {
-        long long lab = (r < B) ? labels[r] : (long long)num_classes;
+        long long lab = (r < nlab) ? labels[r] : (long long)num_classes;
         if (lab < 0 || lab > num_classes) lab = num_classes;
         e = class_emb[(size_t)lab * C + c];
     }
@@ -589,17 +590,18 @@ __global__ void prologue_kernel(const long long* __restrict__ labels, const floa
 }
 
 int prologue(const long long* labels, const float* cond_in, const float* class_emb, const float* pos_start, const float* lvl_pos, float* cond, float* x0,
-             int B, int C, int num_classes, hipStream_t stream) {
-    hipLaunchKernelGGL(prologue_kernel, dim3((C + 255) / 256, 2 * B), dim3(256), 0, stream, labels, cond_in, class_emb, pos_start, lvl_pos, cond, x0, B, C, num_classes);
+             int R, int nlab, int C, int num_classes, hipStream_t stream) {
+    hipLaunchKernelGGL(prologue_kernel, dim3((C + 255) / 256, R), dim3(256), 0, stream, labels, cond_in, class_emb, pos_start, lvl_pos, cond, x0, nlab, C, num_classes);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
 
-// adaLN parameters of a call from the per-class table (api.hip: model_begin): row r of block i = tab[label(r)][i * 6C ..], head row = tab[label(r)][depth * 6C ..]
+// adaLN parameters of a call from the per-class table (api.hip: model_begin): row r of block i = tab[label(r)][i * 6C ..], head row = tab[label(r)][depth * 6C ..];
+// label(r) = labels[r] for r < nlab, else the unconditional class (grid: one workgroup per row)
 __global__ __launch_bounds__(256) void ada_gather_kernel(const long long* __restrict__ labels, const float* __restrict__ tab, size_t row_floats, int depth, int C,
-                                                         float* __restrict__ ada, size_t blk_stride, float* __restrict__ ada_head, int B, int num_classes) {
+                                                         float* __restrict__ ada, size_t blk_stride, float* __restrict__ ada_head, int nlab, int num_classes) {
     const int r = blockIdx.x, i = blockIdx.y;
-    long long lab = (r < B) ? labels[r] : (long long)num_classes;
+    long long lab = (r < nlab) ? labels[r] : (long long)num_classes;
     if (lab < 0 || lab > num_classes) lab = num_classes;
     const int n4 = (i < depth ? 6 * C : 2 * C) / 4;
     const float4* src = reinterpret_cast<const float4*>(tab + (size_t)lab * row_floats + (size_t)i * 6 * C);
@@ -607,9 +609,9 @@ __global__ __launch_bounds__(256) void ada_gather_kernel(const long long* __rest
     for (int c = threadIdx.x; c < n4; c += 256) dst[c] = src[c];
 }
 
-int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int B, int num_classes,
+int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int R, int nlab, int num_classes,
                hipStream_t stream) {
-    hipLaunchKernelGGL(ada_gather_kernel, dim3(2 * B, depth + 1), dim3(256), 0, stream, labels, tab, row_floats, depth, C, ada, blk_stride, ada_head, B, num_classes);
+    hipLaunchKernelGGL(ada_gather_kernel, dim3(R, depth + 1), dim3(256), 0, stream, labels, tab, row_floats, depth, C, ada, blk_stride, ada_head, nlab, num_classes);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
@@ -627,11 +629,12 @@ int build_lvl_pos(const float* lvl_embed, const float* pos, const int* stage_of_
     return SDVAR_OK;
 }
 
-// x[b][t][:] = x[B+b][t][:] = nxt[b][t][0:32] . Ww[:, 0:32]^T + bw + lvl_pos[t0 + t]       (Cvae = 32)
+// x[b][t][:] (and, with pair, x[B+b][t][:]) = nxt[b][t][0:32] . Ww[:, 0:32]^T + bw + lvl_pos[t0 + t]       (Cvae = 32)
 // one workgroup per (token, image): the 32 inputs are broadcast from LDS, each thread owns output channels.
+// pair = 1: the CFG duplication of the sampler (var.py:186-188); 0: one row per image (teacher forcing, var.py:233-235).
 __global__ __launch_bounds__(256) void embed_next_kernel(const float* __restrict__ nxt, const float* __restrict__ Ww, const float* __restrict__ bw,
                                                          const float* __restrict__ lvl_pos, float* __restrict__ x, int B, int l, int C, int t0,
-                                                         int ltot, int tok_off) {
+                                                         int ltot, int tok_off, int pair) {
     __shared__ float in[32];
     const int t = blockIdx.x, b = blockIdx.y;
     if (threadIdx.x < 32) in[threadIdx.x] = nxt[((size_t)b * l + t) * 32 + threadIdx.x];
@@ -647,14 +650,14 @@ __global__ __launch_bounds__(256) void embed_next_kernel(const float* __restrict
         }
         const float v = (acc + bw[c]) + lvl_pos[(size_t)(t0 + t) * C + c];
         x[((size_t)b * ltot + tok_off + t) * C + c] = v;
-        x[((size_t)(B + b) * ltot + tok_off + t) * C + c] = v;
+        if (pair) x[((size_t)(B + b) * ltot + tok_off + t) * C + c] = v;
     }
 }
 
-int embed_next(const float* nxt, const float* Ww, const float* bw, const float* lvl_pos, float* x, int B, int l, int C, int t0, int ltot, int tok_off,
+int embed_next(const float* nxt, const float* Ww, const float* bw, const float* lvl_pos, float* x, int B, int l, int C, int t0, int ltot, int tok_off, int pair,
                hipStream_t stream) {
     SDVAR_CHECK_ARG(B > 0 && l > 0 && tok_off >= 0 && tok_off + l <= ltot, "embed_next: bad placement");
-    hipLaunchKernelGGL(embed_next_kernel, dim3(l, B), dim3(256), 0, stream, nxt, Ww, bw, lvl_pos, x, B, l, C, t0, ltot, tok_off);
+    hipLaunchKernelGGL(embed_next_kernel, dim3(l, B), dim3(256), 0, stream, nxt, Ww, bw, lvl_pos, x, B, l, C, t0, ltot, tok_off, pair);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }

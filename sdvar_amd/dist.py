@@ -2,7 +2,8 @@
 
 The sampling path has no data-path exchange: images are independent, every rank holds full weight replicas and private
 KV caches, and the acceptance decision is taken per shard (`accept_scope="shard"`).  The only collective is ONE
-all-gather of per-rank counters (accepted tokens, target calls, ...) after the run - RCCL over xGMI on the GPU box
+all-gather of per-rank counters (accepted tokens, target calls, ...) after the run (and, for validation, one all-reduce of
+the loss / accuracy sums: sdvar_amd.evaluate) - RCCL over xGMI on the GPU box
 (`backend="nccl"`), gloo in the CPU tests.  Noise is keyed by the GLOBAL image index (sdvar_amd/noise.py), so a shard
 produces exactly the tokens the same images would get in a single-process run of the whole batch with shard scope.
 The reference has no counterpart (its inference is single-device; dist.py there only serves training).
@@ -86,6 +87,17 @@ def global_accept(matched: Sequence[int], totals: Sequence[int], thr: float, dev
     v = vec.cpu().tolist()
     g = len(matched)
     return leading_accepted(v[:g], v[g:], thr), v[:g], v[g:]
+
+
+def allreduce_eval_sums(sums: torch.Tensor, tot: int) -> Tuple[float, ...]:
+    """Validation statistics (VARTrainer.eval_ep, trainer.py:77-78): the four per-rank sums {sum nll, sum tail nll, #correct, #tail correct} (float64,
+    on the device) plus the rank's image count, summed over the ranks in ONE all-reduce when a process group is initialised.  Returns the five
+    global values (identical on every rank)."""
+    dev = _coll_device(sums.device)
+    vec = torch.cat((sums.detach().to(device=dev, dtype=torch.float64).reshape(4), torch.tensor([float(tot)], dtype=torch.float64, device=dev)))
+    if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+        tdist.all_reduce(vec, op=tdist.ReduceOp.SUM)
+    return tuple(vec.cpu().tolist())
 
 
 def max_over_ranks(value: float, device) -> float:

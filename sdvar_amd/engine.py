@@ -62,6 +62,8 @@ _SIGNATURES = {
     "sdvar_model_bind_head": (_I, [_P] * 6),
     "sdvar_model_begin": (_I, [_P, _I, _P, _P]),
     "sdvar_model_begin_cond": (_I, [_P, _I, _P, _P]),
+    "sdvar_model_begin_rows": (_I, [_P, _I, _P, _P]),
+    "sdvar_embed_teacher": (_I, [_P, _P, _P, _P]),
     "sdvar_model_export_prologue": (_I, [_P, _P, _P, _P, _P]),
     "sdvar_model_place_first": (_I, [_P, _P, _I, _P]),
     "sdvar_kv_len": (_I, [_P]),
@@ -93,6 +95,7 @@ _SIGNATURES = {
     "sdvar_cfg_sample": (_I, [_P, _I, _I, _I, _D, _I, _D, _P, _U64, _U32, _U32, _P, _I, _P, _P]),
     "sdvar_verify_accept": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _P, _P, _P]),
     "sdvar_cfg_combine": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _P]),
+    "sdvar_xent_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "sdvar_verify_accept_ex": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "sdvar_op_gemm": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P]),
     "sdvar_op_ln_modulate": (_I, [_P, _P, _P, _P, _P, _U64, _I, _I, _I, _I, _I, _P]),
@@ -216,19 +219,30 @@ class ModelCtx:
     # thin wrappers ----------------------------------------------------------------------------------------------
     def begin(self, labels: torch.Tensor):
         assert labels.dtype == torch.int64 and labels.is_cuda
-        self.B = labels.shape[0]
+        self.B = labels.shape[0]; self.R = 2 * self.B
         _check(self.lib.sdvar_model_begin(self.h, self.B, _ptr(labels), _stream()))
 
     def begin_cond(self, cond: torch.Tensor):
         """The prologue from the conditioning rows (2B, C) themselves (`sos` of var.py:319-345) instead of labels."""
         assert cond.dtype == torch.float32 and cond.is_cuda and cond.dim() == 2 and cond.shape[1] == self.Cw and cond.shape[0] % 2 == 0
-        self.B = cond.shape[0] // 2
+        self.B = cond.shape[0] // 2; self.R = 2 * self.B
         _check(self.lib.sdvar_model_begin_cond(self.h, self.B, _ptr(cond.contiguous()), _stream()))
 
+    def begin_rows(self, labels: torch.Tensor):
+        """The prologue for R unpaired rows (teacher forcing): row r conditioned on labels[r], num_classes = unconditional.  R <= 2 max_batch."""
+        assert labels.dtype == torch.int64 and labels.is_cuda and labels.dim() == 1
+        self.B, self.R = 0, labels.shape[0]
+        _check(self.lib.sdvar_model_begin_rows(self.h, labels.shape[0], _ptr(labels.contiguous()), _stream()))
+
+    def embed_teacher(self, xv: Optional[torch.Tensor], x: torch.Tensor):
+        """Teacher-forcing input x (R, L, C) of the current begin_rows call from xv (R, L-1, Cvae) (var.py:230-235)."""
+        _check(self.lib.sdvar_embed_teacher(self.h, _ptr(xv), _ptr(x), _stream()))
+
     def export_prologue(self):
-        """(cond (2B,C), lvl_pos (1,L,C), first_token_map (2B,1,C)) of the current call, as SDVAR.init_param returns them."""
+        """(cond (R,C), lvl_pos (1,L,C), first_token_map (R,1,C)) of the current call (R = 2B for a CFG call), as SDVAR.init_param returns them."""
         f = dict(device=self.device, dtype=torch.float32)
-        cond, lvl, first = torch.empty(2 * self.B, self.Cw, **f), torch.empty(1, self.lad.L, self.Cw, **f), torch.empty(2 * self.B, 1, self.Cw, **f)
+        R = self.R
+        cond, lvl, first = torch.empty(R, self.Cw, **f), torch.empty(1, self.lad.L, self.Cw, **f), torch.empty(R, 1, self.Cw, **f)
         _check(self.lib.sdvar_model_export_prologue(self.h, _ptr(cond), _ptr(lvl), _ptr(first), _stream()))
         return cond, lvl, first
 
@@ -581,6 +595,19 @@ def cfg_combine(logits: torch.Tensor, B: int, lens: Sequence[int], V: int, ts: S
     out = torch.empty(B, lsum, V, dtype=torch.float32, device=logits.device)
     _check(load_library().sdvar_cfg_combine(_ptr(logits), B, lsum, V, n, (_I * n)(*lens), (_D * n)(*[float(t) for t in ts]), _ptr(out), _stream()))
     return list(out.split([int(x) for x in lens], dim=1))
+
+
+def xent_stats(logits: torch.Tensor, targets: torch.Tensor, tail: int, sums: torch.Tensor, accumulate: bool = False, nll_out: Optional[torch.Tensor] = None,
+               argmax_out: Optional[torch.Tensor] = None):
+    """sdvar_xent_stats: logits (B, L, V) fp32, targets (B, L) int64 -> sums (4,) float64 {sum nll, sum tail nll, #correct, #tail correct} over the
+    last `tail` tokens of each image (VARTrainer.eval_ep, trainer.py:66-75); optional per-token nll (B, L) fp32 and argmax (B, L) int64."""
+    B, L, V = logits.shape
+    assert logits.dtype == torch.float32 and targets.dtype == torch.int64 and tuple(targets.shape) == (B, L)
+    assert sums.dtype == torch.float64 and sums.numel() == 4
+    assert nll_out is None or (nll_out.dtype == torch.float32 and nll_out.numel() == B * L)
+    assert argmax_out is None or (argmax_out.dtype == torch.int64 and argmax_out.numel() == B * L)
+    load_library()
+    _check(_lib.sdvar_xent_stats(_ptr(logits), _ptr(targets), B, L, V, tail, _ptr(nll_out), _ptr(argmax_out), _ptr(sums), int(bool(accumulate)), _stream()))
 
 
 def last_gemm_cfg() -> Dict[str, int]:

@@ -3,8 +3,9 @@
 Same constructor arguments, attribute names, sampler signatures and state_dict keys as
 /root/reference/models/var.py:22-215 (VAR) and :535-1383 (SDVAR), so existing callers and upstream checkpoints work
 unchanged - but the modules here only HOLD parameters; every sampler call runs on the gfx950 kernels through
-sdvar_amd.engine (C ABI).  Training-side methods (VAR.forward with teacher forcing, progressive training) are outside
-the scope table and raise NotImplementedError.
+sdvar_amd.engine (C ABI).  VAR.forward is the teacher-forced pass of var.py:217-259 for scoring (validation loss and
+accuracy, sdvar_amd.evaluate); it returns logits without an autograd graph.  Training (backward, dropout, progressive
+training) is outside the scope table.
 """
 from __future__ import annotations
 
@@ -17,6 +18,10 @@ import torch.nn as nn
 from . import engine as E
 from .ladder import as_ladder
 from .vqvae import VQVAE
+
+# images per pass of VAR.forward (M = L * TF_PASS_IMAGES rows per GEMM), from tools/eval_bench.py: at 256^2 a d16 pass
+# runs 915 / 1012 / 1119 images/s at 8 / 16 / 32 images (f16x2), d30 195 / 201 / 203
+TF_PASS_IMAGES = 32
 
 
 class _SelfAttention(nn.Module):                   # parameter names of basic_var.py:58-87
@@ -77,6 +82,9 @@ class VAR(nn.Module):
         self.begin_ends = [(lad.begin(s), lad.cum[s]) for s in range(lad.S)]
         self.num_stages_minus_1 = lad.S - 1
         self.num_classes = num_classes
+        self.cond_drop_rate = cond_drop_rate
+        self.drop_rate, self.attn_drop_rate, self.drop_path_rate = drop_rate, attn_drop_rate, drop_path_rate
+        self.prog_si = -1                           # progressive training is not supported (quant.py:42: "prog_si always -1")
         self.vae_proxy, self.vae_quant_proxy = (vae_local,), (vae_local.quantize,)
         C = embed_dim
         self.word_embed = nn.Linear(self.Cvae, C)
@@ -101,6 +109,9 @@ class VAR(nn.Module):
         self._ctx: Optional[E.ModelCtx] = None
         self._sampler: Optional[E.Sampler] = None
         self._quant: Optional[E.QuantCtx] = None
+        self._tf_ctx: Optional[E.ModelCtx] = None   # VAR.forward's own model object (teacher forcing): the sampler's context stays untouched
+        self.tf_pass_images = TF_PASS_IMAGES
+        self.tf_gemm_mode: Optional[str] = None     # GEMM arithmetic of VAR.forward (engine.GEMM_MODES; None = the engine default)
         self.noise_kind = "device"                  # 'device' | 'host' | 'torch' (sdvar_amd.engine.Noise)
         self.last_result: Optional[E.SampleResult] = None
 
@@ -114,7 +125,7 @@ class VAR(nn.Module):
 
     def invalidate_engine(self):
         """Call after changing parameters in place (load_state_dict does it automatically)."""
-        self._ctx = self._sampler = self._quant = None
+        self._ctx = self._sampler = self._quant = self._tf_ctx = None
 
     def load_state_dict(self, *a, **kw):
         out = super().load_state_dict(*a, **kw)
@@ -209,8 +220,59 @@ class VAR(nn.Module):
         return self._sampler.resume_ar(sos.to(device=dev, dtype=torch.float32).contiguous(), current_step, step, nm, f_hat, cfg, top_k, top_p, noise,
                                        more_smooth=bool(more_smooth))
 
-    def forward(self, *a, **kw):
-        raise NotImplementedError("teacher-forced training forward (var.py:217-259) is outside the sampling hot path")
+    def tf_ctx(self, images: int) -> E.ModelCtx:
+        """The model object of VAR.forward: passes of up to `images` unpaired rows over all S stages at once (max_batch = ceil(images / 2),
+        max_chunk = S).  A second weight-plane copy beside the sampler's, so sampling state is never disturbed."""
+        dev, S = self._device(), len(self.patch_nums)
+        c, mb = self._tf_ctx, (images + 1) // 2
+        if c is None or c.max_batch < mb or c.device != dev or c.gemm_mode != (self.tf_gemm_mode or c.gemm_mode):
+            if c is not None:
+                c.close()
+            self._tf_ctx = c = E.ModelCtx(self.state_dict(), self.depth, self.patch_nums, mb, S, dev, self.num_classes, gemm_mode=self.tf_gemm_mode)
+        return c
+
+    @torch.no_grad()
+    def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor) -> torch.Tensor:
+        """Teacher-forced logits (var.py:217-259): label_B (B,) int64, x_BLCv_wo_first_l (B, L-1, Cvae) fp32 (VectorQuantizer2.idxBl_to_var_input)
+        -> logits (B, L, V) fp32 on the model's device.  Token 0 is (class_emb[label'] + pos_start) + lvl_pos[0], token t >= 1 is
+        word_embed(x[:, t-1]) + lvl_pos[t]; every block runs under the block-causal mask, then head(head_nm(x, cond)).
+
+        Condition dropout as in the reference, in eval mode too: label' = where(torch.rand(B, device=label_B.device) < cond_drop_rate,
+        num_classes, label_B) - one draw from that device's global generator, even at rate 0.  Set `cond_drop_rate = 0` for deterministic
+        validation numbers.  The returned logits carry NO autograd graph (no backward on the HIP path).  Images run in passes of at most
+        `tf_pass_images` rows, each through sdvar_model_begin_rows / sdvar_embed_teacher / sdvar_stage_forward over all stages.
+
+        Raises SdvarError for prog_si != -1, for training mode with a non-zero drop_rate / attn_drop_rate / drop_path_rate (the HIP path has no
+        dropout: call .eval()), for wrong shapes or dtypes, and for CPU tensors."""
+        if self.prog_si != -1:
+            raise E.SdvarError(f"VAR.forward: prog_si={self.prog_si}: progressive training is not supported (prog_si must be -1)")
+        if self.training and (self.drop_rate or self.attn_drop_rate or self.drop_path_rate):
+            raise E.SdvarError("VAR.forward: the module is in training mode with dropout (drop_rate / attn_drop_rate / drop_path_rate), which the HIP "
+                               "path does not apply: call .eval() first")
+        if not isinstance(label_B, torch.Tensor) or label_B.dim() != 1 or label_B.dtype not in (torch.int64, torch.int32):
+            raise E.SdvarError(f"VAR.forward: label_B must be a (B,) integer tensor, got {getattr(label_B, 'shape', type(label_B))}")
+        B, Lm1 = label_B.shape[0], self.L - self.first_l
+        x = x_BLCv_wo_first_l
+        if B < 1 or not isinstance(x, torch.Tensor) or tuple(x.shape) != (B, Lm1, self.Cvae) or not x.is_floating_point():
+            raise E.SdvarError(f"VAR.forward: x_BLCv_wo_first_l must be a float ({B}, {Lm1}, {self.Cvae}) tensor, got {tuple(getattr(x, 'shape', ()))}")
+        dev = self._device()
+        if dev.type != "cuda" or not label_B.is_cuda or not x.is_cuda:
+            raise E.SdvarError("VAR.forward runs on an MI355X: the model, label_B and x_BLCv_wo_first_l must be on a cuda (HIP) device; there is no CPU path")
+        drop = torch.rand(B, device=label_B.device) < self.cond_drop_rate            # var.py:231, the reference's single draw
+        labels = label_B.to(torch.int64).masked_fill(drop, self.num_classes).to(dev).contiguous()
+        xv = x.to(device=dev, dtype=torch.float32).contiguous()
+        P = max(1, int(self.tf_pass_images))
+        ctx = self.tf_ctx(min(B, P))
+        L, C = self.L, self.C
+        out = torch.empty(B, L, self.V, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            xb = torch.empty(min(B, P), L, C, device=dev, dtype=torch.float32)
+            for lo in range(0, B, P):
+                n = min(P, B - lo)
+                ctx.begin_rows(labels[lo:lo + n])
+                ctx.embed_teacher(xv[lo:lo + n], xb[:n])
+                ctx.forward(xb[:n], 0, len(self.patch_nums), out[lo:lo + n])
+        return out
 
     def init_weights(self, init_adaln=0.5, init_adaln_gamma=1e-5, init_head=0.02, init_std=0.02, conv_std_or_gain=0.02, seed: int = 1234):
         """Distributions of var.py:261-311 drawn from a seeded generator (sdvar_amd.weights 'perf' init): trunc-normal(init_std; < 0 =
