@@ -276,6 +276,30 @@ int sdvar_op_quant_nearest(const float* z, int32_t N, const float* codebook, int
 int sdvar_op_conv_planes(const uint16_t* x_planes, uint64_t x_plane_stride, uint64_t x_rows, int32_t x_row0, const uint16_t* w_planes, uint64_t w_plane_stride,
                          int32_t plane_format, const float* w_scale, const float* bias, const float* res, float* out, int32_t B, int32_t H, int32_t W, int32_t N,
                          int32_t Cin, int32_t taps, float* workspace, uint64_t workspace_floats, int32_t force_split, void* stream);
+/* sdvar_op_conv_planes with the decoder's two extras.  up_phase >= 0 (taps = 4, no res, no split): the convolution of the nearest-2x up-sampled
+ * (B, Cin, 2H, 2W) tensor into out[B 2H 2W][N], from the x planes of the (B, Cin, H, W) input and four phase weight sets (sdvar_op_upconv_weights),
+ * w_phase_stride elements apart.  gn_part (device, B (H W / 256) 64 doubles, x4 with up_phase; may be NULL): when the convolution can fuse the
+ * GroupNorm statistics of its output into the epilogue (no split-K, H W % 256 == 0, N % 32 == 0 and (N / 32) | 160), it does, finalises them into
+ * stats (device, (B, 32, {mean, rstd}), eps 1e-6) and sets *gn_done (host) = 1; else *gn_done = 0 and stats is untouched. */
+int sdvar_op_conv_planes_ex(const uint16_t* x_planes, uint64_t x_plane_stride, uint64_t x_rows, int32_t x_row0, const uint16_t* w_planes, uint64_t w_plane_stride,
+                            int32_t plane_format, const float* w_scale, const float* bias, const float* res, float* out, int32_t B, int32_t H, int32_t W, int32_t N,
+                            int32_t Cin, int32_t taps, float* workspace, uint64_t workspace_floats, int32_t force_split, int32_t up_phase, uint64_t w_phase_stride,
+                            double* gn_part, float* stats, int32_t* gn_done, void* stream);
+/* Upsample2x weight (Cout, Cin, 3, 3) -> weff [4 phases (py, px)][Cout][Cin][4 taps (ty, tx)] fp32: the 2x2 convolution of each output phase on the
+ * input grid.  The decoder packs phase p with conv weight planes (taps = 4, plane stride wps = 4 Cin Cout) at planes + p * npl * wps (npl = 3 bf16x3 |
+ * 2 f16x2 planes), so w_phase_stride = npl * wps; in f16x2 one weight scale (sdvar_op_split_planes_f16 over all of weff) serves all four phases. */
+int sdvar_op_upconv_weights(const float* w, float* weff, int32_t Cout, int32_t Cin, void* stream);
+/* The decoder's stand-alone GroupNorm statistics of rows [B H W][C] ((C/4) | 320): stats (B, 32, {mean, rstd}), eps 1e-6.  part_ws: B min(H, 64) 64 doubles. */
+int sdvar_op_vae_gn_stats(const float* x_rows, int32_t B, int32_t C, int32_t H, int32_t W, double* part_ws, float* stats, void* stream);
+/* AttnBlock core of the decoder: qkv rows [B N][3C] (q | k | v) -> out rows [B N][C] = softmax(q k^T / sqrt(C)) v.  kernel: -1 = the decoder's choice
+ * (1 for N in {256, 1024} and C % 64 == 0, else 0 while its LDS fits, else 2); 0 = fp32 FMA, probabilities in LDS (N <= 1612); 1 = fp32 matrix cores
+ * (N in {256, 1024}, C % 64 == 0); 2 = probabilities in workspace (ceil(N / 16) N 20 floats per image; as many images per launch as ws_floats holds).
+ * A forced kernel that cannot take the shape returns SDVAR_ERR_ARG. */
+int sdvar_op_vae_attn(const float* qkv, float* out, int32_t B, int32_t C, int32_t N, float* workspace, uint64_t ws_floats, int32_t kernel, void* stream);
+/* norm_out + SiLU + conv_out (3 x C x 3 x 3, pad 1) + bias, clamped to [-1, 1]: x rows [B H W][C], stats (B, 32, {mean, rstd}) -> img (B, 3, H, W).
+ * workspace: (C + B H W) 28 floats. */
+int sdvar_op_vae_conv_out(const float* x_rows, const float* stats, const float* gamma, const float* beta, const float* w, const float* bias, float* img, int32_t B,
+                          int32_t C, int32_t H, int32_t W, float* workspace, void* stream);
 /* tuning / test aid (tools/gemm_bench.py --sweep): force the GEMM row tile (32/64/128/256) and K-slice count; 0 = automatic.  f16x2 mode only: bm 512 = the
  * 256 x 256 tile kernel; bm 256 with split = -T forces the hybrid tail split T ways on shapes that have a partial last round. */
 int sdvar_debug_set_gemm_cfg(int32_t bm, int32_t split);

@@ -55,6 +55,24 @@ struct ConvArgs {
     int dbg;                                       // timing experiments (SDVAR_CONV_DBG, results wrong): bit 0 = no epilogue, bit 1 = no GroupNorm statistics, bit 2 = no output stores
 };
 
+// per group of the tile: the fp32 column sums around the column pivots (red, piv) -> {sum, M2} in fp64, the columns merged as in vae.hip gn_partial_kernel
+// (gn_finalize_kernel merges the tiles)
+__device__ __forceinline__ void conv_gn_store(const ConvArgs& a, const float* red, const float* piv, int n0, int tm, int phase, int tid) {
+    const int col0 = tid * a.cpg;
+    if (col0 < CBN && n0 + col0 < a.N) {
+        const double n = 256.0, in = 1.0 / 256.0;      // rows per tile (exact reciprocal: no fp64 division in the loop)
+        double s = 0.0, m = 0.0;
+        for (int c = col0; c < col0 + a.cpg; ++c) {
+            double s1 = 0.0, s2 = 0.0;
+            for (int w = 0; w < 8; ++w) { s1 += (double)red[w * 160 + c]; s2 += (double)red[1280 + w * 160 + c]; }
+            const double sc = n * (double)piv[c] + s1;
+            s += sc; m += s2 + (sc * sc - s1 * s1) * in;
+        }
+        double* o = a.gn_part + ((size_t)(a.up_phase >= 0 ? 4 * tm + phase : tm) * 32 + (n0 + col0) / a.cpg) * 2;
+        o[0] = s; o[1] = m - s * s / (n * a.cpg);
+    }
+}
+
 // Shared epilogue of both convolution kernels: (acc * wsi) + bias (+ residual), the up-sampling phase scatter, split-K slabs, and the
 // fused GroupNorm statistics of the tile just written.
 template <int EPI>
@@ -97,16 +115,23 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[5
     }
     // GroupNorm statistics of the tile just written (the next layer's norm): per column sum / sum of squares over the 256 rows
     // (all of one image: the host enables this only when H W is a multiple of 256), reduced lane -> wave -> workgroup through
-    // LDS in a fixed order, then per group in fp64.  Saves a full read of the activation tensor per normalisation.
+    // LDS in a fixed order, then per group in fp64.  Saves a full read of the activation tensor per normalisation.  The sums are
+    // taken around a pivot per column (its value in the tile's first row) and stored as {sum, M2} (vae.hip: GroupNorm statistics).
     if (EPI != CEPI_PARTIAL && a.gn_part && !SDVAR_CDBG(a, 2)) {
         float* red = reinterpret_cast<float*>(csm);          // [2][8][160]
-        __syncthreads();                                     // every wave is done with the operand stages
+        __shared__ float piv[CBN];                           // the pivots: row m0 of the tile (outside the operand ring: written before the barrier)
+        if (wave == 0 && lh == 0) {                          // row m0: r = 0 of lanes 0-31 of wave 0
+#pragma unroll
+            for (int j = 0; j < 5; ++j) piv[j * 32 + li] = acc[j][0];
+        }
+        __syncthreads();                                     // every wave is done with the operand stages; the pivots are in
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             float s1 = 0.f, s2 = 0.f;
             if (n0 + j * 32 + li < a.N) {
+                const float K = piv[j * 32 + li];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { s1 += acc[j][r]; s2 += acc[j][r] * acc[j][r]; }
+                for (int r = 0; r < 16; ++r) { const float d = acc[j][r] - K; s1 += d; s2 += d * d; }
             }
             const auto w1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s1), __float_as_uint(s1), false, false);
             const auto w2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s2), __float_as_uint(s2), false, false);
@@ -116,14 +141,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[5
             }
         }
         __syncthreads();
-        const int gl = tid, col0 = gl * a.cpg;
-        if (col0 < CBN && n0 + col0 < a.N) {
-            double a1 = 0.0, a2 = 0.0;
-            for (int w = 0; w < 8; ++w)
-                for (int c = 0; c < a.cpg; ++c) { a1 += (double)red[w * 160 + col0 + c]; a2 += (double)red[1280 + w * 160 + col0 + c]; }
-            double* o = a.gn_part + ((size_t)(a.up_phase >= 0 ? 4 * tm + phase : tm) * 32 + (n0 + col0) / a.cpg) * 2;
-            o[0] = a1; o[1] = a2;
-        }
+        conv_gn_store(a, red, piv, n0, tm, phase, tid);
     }
 }
 
@@ -180,25 +198,25 @@ __device__ __forceinline__ void conv_epilogue16(const ConvArgs& a, cf32x4 (&acc)
     }
     if (EPI != CEPI_PARTIAL && a.gn_part && !SDVAR_CDBG(a, 2)) {          // GroupNorm statistics of the tile just written (M % 256 == 0 when enabled: every row is real)
         float* red = reinterpret_cast<float*>(csm);          // [2][8][160]
-        __syncthreads();                                     // every wave is done with the operand stages
+        __shared__ __attribute__((aligned(16))) float piv[CBN];          // the pivots (conv_epilogue)
+        if (wave == 0 && l15 == 0) {                         // row m0 of the tile: mt = 0 of lanes 0, 16, 32, 48 of wave 0
 #pragma unroll
-        for (int nt = 0; nt < 10; ++nt)
+            for (int nt = 0; nt < 10; ++nt) *reinterpret_cast<cf32x4*>(piv + 16 * nt + 4 * lq) = acc[0][nt];
+        }
+        __syncthreads();                                     // every wave is done with the operand stages; the pivots are in
+#pragma unroll
+        for (int nt = 0; nt < 10; ++nt) {
+            const bool in = n0 + 16 * nt + 4 * lq < a.N;
+            const cf32x4 K = *reinterpret_cast<const cf32x4*>(piv + 16 * nt + 4 * lq);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const bool in = n0 + 16 * nt + 4 * lq < a.N;
-                const float x0 = in ? acc[0][nt][e] : 0.f, x1 = in ? acc[1][nt][e] : 0.f;
+                const float x0 = in ? acc[0][nt][e] - K[e] : 0.f, x1 = in ? acc[1][nt][e] - K[e] : 0.f;
                 const float s1 = dpp_row_sum16(x0 + x1), s2 = dpp_row_sum16(x0 * x0 + x1 * x1);
                 if (l15 == 15) { red[wave * 160 + 16 * nt + 4 * lq + e] = s1; red[1280 + wave * 160 + 16 * nt + 4 * lq + e] = s2; }
             }
-        __syncthreads();
-        const int gl = tid, col0 = gl * a.cpg;
-        if (col0 < CBN && n0 + col0 < a.N) {
-            double a1 = 0.0, a2 = 0.0;
-            for (int w = 0; w < 8; ++w)
-                for (int c = 0; c < a.cpg; ++c) { a1 += (double)red[w * 160 + col0 + c]; a2 += (double)red[1280 + w * 160 + col0 + c]; }
-            double* o = a.gn_part + ((size_t)(a.up_phase >= 0 ? 4 * tm + phase : tm) * 32 + (n0 + col0) / a.cpg) * 2;
-            o[0] = a1; o[1] = a2;
         }
+        __syncthreads();
+        conv_gn_store(a, red, piv, n0, tm, phase, tid);
     }
 }
 
@@ -689,6 +707,7 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
     SDVAR_CHECK_ARG(X && W && out, "conv: null operand");
     SDVAR_CHECK_ARG(M > 0 && N > 0 && Cin > 0 && Cin % 32 == 0 && (taps == 1 || taps == 9 || (taps == 4 && up_phase >= 0)) && (taps == 4 || up_phase < 0), "conv: M=%d N=%d Cin=%d taps=%d", M, N, Cin, taps);
     SDVAR_CHECK_ARG(B > 0 && H > 0 && Wd > 0 && x_row0 >= w2 + 1, "conv: guard rows %d < row pitch %d + 1", x_row0, w2);
+    SDVAR_CHECK_ARG(up_phase < 0 || !res, "conv: no residual with the fused up-sampling");
     SDVAR_CHECK_ARG(x_rows >= (size_t)x_row0 + Mp + w2 + 1, "conv: plane rows %zu too few", x_rows);
     SDVAR_CHECK_ARG(((uintptr_t)X % 16) == 0 && ((uintptr_t)W % 16) == 0 && xps % 8 == 0 && wps % 8 == 0, "conv: planes must be 16-byte aligned");
     SDVAR_CHECK_ARG(pfmt == PLANES_BF16X3 || pfmt == PLANES_F16X2, "conv: plane format %d", pfmt);

@@ -3,7 +3,7 @@
 //
 // Layouts as in conv.hip: fp32 activations are dense channel-last rows [B H W][C]; GEMM operands are K-blocked bf16x3 planes over
 // padded pixel rows (zero frame, guard rows).  Per layer:
-//     GroupNorm statistics      gn_partial_kernel + gn_finalize_kernel  (fp32 partial sums per thread, fp64 across threads)
+//     GroupNorm statistics      gn_partial_kernel + gn_finalize_kernel  (fp32 sums around a pivot per thread, fp64 {sum, M2} merges across threads)
 //     GN * gamma + beta, SiLU, optional nearest 2x up-sampling, exact split into planes      prep_planes_kernel (one pass)
 //     3x3 / 1x1 convolution + bias (+ residual)                                              conv.hip
 //     single-head attention over the H W tokens of the 16x16 levels                          vae_attn_kernel
@@ -38,18 +38,25 @@ __global__ __launch_bounds__(256) void rows_from_nchw_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------- GroupNorm statistics
-// 32 groups, eps 1e-6 (basic_vae.py:20).  Grid (chunks, B), 320 threads: thread = (pixel lane, channel quad); requires (C/4) | 320.
+// 32 groups, eps 1e-6 (basic_vae.py:20).  Both producers of partials (gn_partial_kernel here, the conv epilogue in conv.hip) accumulate in fp32 around a pivot
+// per channel, K_c = the partial's first value of channel c: sum (x - K_c) and sum (x - K_c)^2.  Per channel they become, in fp64, sum x = n K_c + sum (x - K_c)
+// and M2_c = sum (x - K_c)^2 - (sum (x - K_c))^2 / n, and per (partial, group) {sum x, M2} with the channels merged by Chan's formula.  The textbook one-pass
+// form E[x^2] - E[x]^2 in fp32 loses the variance when a group's mean is large next to its spread (|mean| / std = 30 already costs ~4e-5 of the normalised
+// value at 256^2: tests/test_vae_gn_emulation.py); the shifted sums leave the float storage of the mean.  gn_finalize_kernel merges the partials (fp64).
+// Grid (chunks, B), 320 threads: thread = (pixel lane, channel quad); requires (C/4) | 320.
 __global__ __launch_bounds__(320) void gn_partial_kernel(const float* __restrict__ x, double* __restrict__ part, int C, int H, int W, int rows_per_chunk) {
     __shared__ float sm[2 * 1280];               // [sum | sumsq][pixel lane][channel]: lanes * C = 320 * 4
     const int b = blockIdx.y, chunk = blockIdx.x, nq = C >> 2, npl = 320 / nq;
     const int q = threadIdx.x % nq, pl = threadIdx.x / nq;
     const int y0 = chunk * rows_per_chunk, y1 = min(H, y0 + rows_per_chunk);
+    const float* x0 = x + ((size_t)b * H + y0) * W * C;          // the chunk's first pixel: the pivots
+    const f32x4 K = *reinterpret_cast<const f32x4*>(x0 + 4 * q);
     float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
     const int npix = (y1 - y0) * W;
     for (int p = pl; p < npix; p += npl) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((size_t)b * H + y0) * W + p) * C + 4 * q);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x0 + (size_t)p * C + 4 * q);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { s[e] += v[e]; ss[e] += v[e] * v[e]; }
+        for (int e = 0; e < 4; ++e) { const float d = v[e] - K[e]; s[e] += d; ss[e] += d * d; }
     }
     const int NL = npl * C;
 #pragma unroll
@@ -57,26 +64,60 @@ __global__ __launch_bounds__(320) void gn_partial_kernel(const float* __restrict
     __syncthreads();
     if (threadIdx.x < 32) {
         const int g = threadIdx.x, cpg = C / 32;
-        double a = 0.0, a2 = 0.0;
-        for (int l = 0; l < npl; ++l)
-            for (int c = g * cpg; c < (g + 1) * cpg; ++c) { a += (double)sm[l * C + c]; a2 += (double)sm[NL + l * C + c]; }
+        const double n = (double)npix, in = 1.0 / n;
+        double a = 0.0, m = 0.0;                 // sum x, sum_c (M2_c + (sum_c x)^2 / n)
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+            double s1 = 0.0, s2 = 0.0;
+            for (int l = 0; l < npl; ++l) { s1 += (double)sm[l * C + c]; s2 += (double)sm[NL + l * C + c]; }
+            const double sc = n * (double)x0[c] + s1;
+            a += sc; m += s2 + (sc * sc - s1 * s1) * in;
+        }
         double* o = part + (((size_t)b * gridDim.x + chunk) * 32 + g) * 2;
-        o[0] = a; o[1] = a2;
+        o[0] = a; o[1] = m - a * a / (n * cpg);
     }
 }
 
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats, int nchunk, double count, double eps) {
+// partials {sum, M2} of nchunk chunks per image (every chunk n_full values, the last n_last) -> stats [B][32][mean, rstd].  Chan's merge in one pass:
+// M2 = sum M2_c + sum sum_c^2 / n_c - (sum sum_c)^2 / n, in fp64 (the cancellation costs |mean|^2 / var ulps of fp64: nothing at any ratio that float stats hold)
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats, int nchunk, double n_full, double n_last, double eps) {
     __shared__ double sm[2][8][32];
     const int b = blockIdx.x, g = threadIdx.x & 31, sl = threadIdx.x >> 5;      // 8 slices of the chunk list per group, combined in slice order
-    double a = 0.0, a2 = 0.0;
-    for (int c = sl; c < nchunk; c += 8) { const double* p = part + (((size_t)b * nchunk + c) * 32 + g) * 2; a += p[0]; a2 += p[1]; }
-    sm[0][sl][g] = a; sm[1][sl][g] = a2;
+    const double* pb = part + (size_t)b * nchunk * 64 + 2 * g;
+    const double if_ = 1.0 / n_full, il = 1.0 / n_last;
+    double a = 0.0, m = 0.0;
+    for (int c = sl; c < nchunk; c += 8) {
+        const double s = pb[(size_t)c * 64];
+        a += s; m += pb[(size_t)c * 64 + 1] + s * s * (c == nchunk - 1 ? il : if_);
+    }
+    sm[0][sl][g] = a; sm[1][sl][g] = m;
     __syncthreads();
     if (sl) return;
-    for (int i = 1; i < 8; ++i) { a += sm[0][i][g]; a2 += sm[1][i][g]; }
-    const double mean = a / count, var = fmax(a2 / count - mean * mean, 0.0);
+    for (int i = 1; i < 8; ++i) { a += sm[0][i][g]; m += sm[1][i][g]; }
+    const double count = (nchunk - 1) * n_full + n_last, mean = a / count, var = fmax((m - a * mean) / count, 0.0);
     stats[((size_t)b * 32 + g) * 2] = (float)mean;
     stats[((size_t)b * 32 + g) * 2 + 1] = (float)(1.0 / sqrt(var + eps));
+}
+
+static int gn_finalize(const double* part, float* stats, int B, int nchunk, double n_full, double n_last, hipStream_t s) {
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, part, stats, nchunk, n_full, n_last, 1e-6);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// The stand-alone statistics pass of rows [B H W][C]: up to 64 chunks of whole rows per image.  part: B * min(H, 64) * 64 doubles.
+static int gn_stats_rows(const float* x, double* part, float* stats, int B, int C, int H, int W, hipStream_t s) {
+    SDVAR_CHECK_ARG(x && part && stats && B >= 1 && H >= 1 && W >= 1 && C % 32 == 0 && C >= 32 && C <= 1280 && 320 % (C / 4) == 0,
+                    "gn_stats: C = %d unsupported ((C/4) must divide 320) or bad shape (B %d H %d W %d)", C, B, H, W);
+    const int nch = H < 64 ? H : 64, rpc = (H + nch - 1) / nch, chunks = (H + rpc - 1) / rpc, cpg = C / 32;
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(chunks, B), dim3(320), 0, s, x, part, C, H, W, rpc);
+    SDVAR_LAUNCH_CHECK();
+    return gn_finalize(part, stats, B, chunks, (double)rpc * W * cpg, (double)(H - (chunks - 1) * rpc) * W * cpg, s);
+}
+
+// the partials a convolution epilogue left (conv.hip: 256-row tiles, four per tile with the fused up-sampling)
+static int gn_stats_fused(const double* part, float* stats, int B, int N, int HW, bool up, hipStream_t s) {
+    const double n = 256.0 * (N / 32);
+    return gn_finalize(part, stats, B, (up ? 4 : 1) * (HW / 256), n, n, s);
 }
 
 // ---------------------------------------------------------------------------------------------------- planes producer
@@ -205,27 +246,37 @@ __global__ __launch_bounds__(512) void vae_attn_mfma_kernel(const float* __restr
     const float* base = qkv + (size_t)b * N * 3 * C;
     const float scale = 1.0f / sqrtf((float)C);
     {
-        f32x4m acc[NKT];
+        // blocked summation: the MFMAs accumulate 64 channels at a time, the block sums are added into a second fp32 sum.  One running sum over all C channels
+        // costs ~2e-5 of the output at C = 640 and scores of +-30 (tests/test_gpu_vae_kernels.py), the blocked sum about a quarter of that
+        f32x4m tot[NKT];
 #pragma unroll
-        for (int t = 0; t < NKT; ++t) acc[t] = f32x4m{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NKT; ++t) tot[t] = f32x4m{0.f, 0.f, 0.f, 0.f};
         const float* pq = base + (size_t)(q0 + j) * 3 * C + 4 * g;
         const float* pk = base + (size_t)(wave * (N / 8) + j) * 3 * C + C + 4 * g;
-#pragma unroll 4
-        for (int c0 = 0; c0 < C; c0 += 16) {
-            const f32x4 qv = *reinterpret_cast<const f32x4*>(pq + c0);
-            f32x4 kv[NKT];
+        for (int cb = 0; cb < C; cb += 64) {
+            f32x4m acc[NKT];
 #pragma unroll
-            for (int t = 0; t < NKT; ++t) kv[t] = *reinterpret_cast<const f32x4*>(pk + (size_t)(16 * t) * 3 * C + c0);
+            for (int t = 0; t < NKT; ++t) acc[t] = f32x4m{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int t = 0; t < NKT; ++t)
+            for (int sl = 0; sl < 4; ++sl) {
+                const int c0 = cb + 16 * sl;
+                const f32x4 qv = *reinterpret_cast<const f32x4*>(pq + c0);
+                f32x4 kv[NKT];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[e], kv[t][e], acc[t], 0, 0, 0);
+                for (int t = 0; t < NKT; ++t) kv[t] = *reinterpret_cast<const f32x4*>(pk + (size_t)(16 * t) * 3 * C + c0);
+#pragma unroll
+                for (int t = 0; t < NKT; ++t)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[e], kv[t][e], acc[t], 0, 0, 0);
+            }
+#pragma unroll
+            for (int t = 0; t < NKT; ++t) tot[t] += acc[t];
         }
         // D: lane holds S[query 4 g + r][key tile column j]
 #pragma unroll
         for (int t = 0; t < NKT; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) vps[(4 * g + r) * SP + wave * (N / 8) + 16 * t + j] = acc[t][r] * scale;
+            for (int r = 0; r < 4; ++r) vps[(4 * g + r) * SP + wave * (N / 8) + 16 * t + j] = tot[t][r] * scale;
     }
     __syncthreads();
     for (int qi = 2 * wave; qi < 2 * wave + 2; ++qi) {
@@ -277,10 +328,12 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(const float* __restrict__
     const float* base = qkv + (size_t)b * N * 3 * C;
     const float scale = 1.0f / sqrtf((float)C);
     for (int k0 = 0; k0 < N; k0 += 256) {
-        f32x2v acc[4][2];
+        f32x2v acc[4][2], tot[4][2];          // blocked summation (as vae_attn_mfma_kernel): the sums of every 32-channel slab are added into tot
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2v{0.f, 0.f}; acc[i][1] = f32x2v{0.f, 0.f}; }
+        for (int i = 0; i < 4; ++i) { tot[i][0] = f32x2v{0.f, 0.f}; tot[i][1] = f32x2v{0.f, 0.f}; }
         for (int c0 = 0; c0 < C; c0 += 32) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2v{0.f, 0.f}; acc[i][1] = f32x2v{0.f, 0.f}; }
             __syncthreads();
 #pragma unroll
             for (int it = 0; it < 8; ++it) {           // k slab: thread = key, 8 x float4 along the channels
@@ -310,6 +363,8 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(const float* __restrict__
                     acc[i][1] = __builtin_elementwise_fma(qq, k23, acc[i][1]);
                 }
             }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { tot[i][0] += acc[i][0]; tot[i][1] += acc[i][1]; }
         }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -317,7 +372,7 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(const float* __restrict__
             if (key < N) {
                 f32x4 o;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = acc[i][kk >> 1][kk & 1] * scale;
+                for (int i = 0; i < 4; ++i) o[i] = tot[i][kk >> 1][kk & 1] * scale;
                 *reinterpret_cast<f32x4*>(ps + key * VA_SP + 4 * tq) = o;
             }
         }
@@ -362,6 +417,47 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(const float* __restrict__
             if (qi < N) *reinterpret_cast<f32x4*>(out + ((size_t)b * N + qi) * C + 4 * cq) = f32x4{acc[i][0][0], acc[i][0][1], acc[i][1][0], acc[i][1][1]};
         }
     }
+}
+
+// AttnBlock core over qkv rows [B N][3C] -> out rows [B N][C].  kernel: -1 = the decoder's choice (below), 0 = vae_attn_kernel<false> (probabilities in LDS),
+// 1 = vae_attn_mfma_kernel, 2 = vae_attn_kernel<true> (probabilities in ws, as many images per launch as ws_floats holds).  The decoder's choice: the
+// matrix-core kernel for N in {256, 1024} and C % 64 == 0 (unless SDVAR_VAE_ATTN_FMA is set: A/B runs), else the LDS kernel up to 160 KB of LDS, else kernel 2.
+// A forced kernel that cannot take the shape is an argument error.
+static int vae_attention(const float* qkv, float* out, int B, int C, int N, float* ws, size_t ws_floats, int kernel, hipStream_t s) {
+    SDVAR_CHECK_ARG(qkv && out && B >= 1 && N >= 1 && C >= 32 && C % 32 == 0 && kernel >= -1 && kernel <= 2, "vae attention: B %d C %d N %d kernel %d", B, C, N, kernel);
+    const size_t lds_fix = ((size_t)32 * 256 + 32 * VA_QT) * sizeof(float), lds = lds_fix + (size_t)N * VA_SP * sizeof(float);
+    const int qgroups = (N + VA_QT - 1) / VA_QT;
+    const bool mfma_ok = (N == 256 || N == 1024) && C % 64 == 0, lds_ok = lds <= 160 * 1024;
+    if (kernel < 0) {
+        static const bool no_mfma = getenv("SDVAR_VAE_ATTN_FMA") != nullptr;
+        kernel = (mfma_ok && !no_mfma) ? 1 : lds_ok ? 0 : 2;
+    }
+    if (kernel == 1) {                                                             // 16^2 / 32^2 latents
+        SDVAR_CHECK_ARG(mfma_ok, "vae attention: the matrix-core kernel needs N in {256, 1024} and C %% 64 == 0 (N %d, C %d)", N, C);
+        const size_t lm = (size_t)16 * (N + 4) * sizeof(float);
+        if (N == 256) {
+            hipLaunchKernelGGL(vae_attn_mfma_kernel<2>, dim3(N / 16, B), dim3(512), lm, s, qkv, out, C, N);
+        } else {
+            SDVAR_HIP(hipFuncSetAttribute((const void*)vae_attn_mfma_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm));
+            hipLaunchKernelGGL(vae_attn_mfma_kernel<8>, dim3(N / 16, B), dim3(512), lm, s, qkv, out, C, N);
+        }
+        SDVAR_LAUNCH_CHECK();
+    } else if (kernel == 0) {
+        SDVAR_CHECK_ARG(lds_ok, "vae attention: %d tokens need %zu bytes of LDS (at most 160 KB)", N, lds);
+        SDVAR_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(vae_attn_kernel<false>, dim3(qgroups, B), dim3(256), lds, s, qkv, out, C, N, (float*)nullptr);
+        SDVAR_LAUNCH_CHECK();
+    } else {
+        const size_t per_img = (size_t)qgroups * N * VA_SP;
+        const int nb_max = ws ? (int)(ws_floats / per_img < (size_t)B ? ws_floats / per_img : (size_t)B) : 0;
+        SDVAR_CHECK_ARG(nb_max >= 1, "vae attention: %d tokens need %zu floats of scratch per image (workspace: %zu)", N, per_img, ws ? ws_floats : 0);
+        for (int b0 = 0; b0 < B; b0 += nb_max) {
+            const int nb = B - b0 < nb_max ? B - b0 : nb_max;
+            hipLaunchKernelGGL(vae_attn_kernel<true>, dim3(qgroups, nb), dim3(256), lds_fix, s, qkv + (size_t)b0 * N * 3 * C, out + (size_t)b0 * N * C, C, N, ws);
+            SDVAR_LAUNCH_CHECK();
+        }
+    }
+    return SDVAR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------- conv_out
@@ -430,6 +526,24 @@ __global__ void convout_weight_kernel(const float* __restrict__ w, float* __rest
     if (i >= C * 28) return;
     const int c = i / 28, k = i % 28;
     wt[i] = (k < 27) ? w[((size_t)(k % 3) * C + c) * 9 + k / 3] : 0.f;
+}
+
+static int convout_weights(const float* w, float* wt, int C, hipStream_t s) {
+    hipLaunchKernelGGL(convout_weight_kernel, dim3((C * 28 + 255) / 256), dim3(256), 0, s, w, wt, C);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// norm_out + SiLU + conv_out + clamp: x rows [B H W][C], stats [B][32][mean, rstd], wt from convout_weights, t27 scratch of B H W 28 floats -> img (B, 3, H, W)
+static int convout(const float* x, const float* stats, const float* gamma, const float* beta, const float* wt, const float* bias, float* t27, float* img, int B, int C, int H,
+                   int W, hipStream_t s) {
+    const size_t M = (size_t)B * H * W;
+    hipLaunchKernelGGL(convout_partial_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, x, stats, gamma, beta, wt, t27, B, C, H, W);
+    SDVAR_LAUNCH_CHECK();
+    const size_t total = (size_t)B * 3 * H * W;
+    hipLaunchKernelGGL(convout_gather_kernel, dim3((unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192)), dim3(256), 0, s, t27, bias, img, B, H, W);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
 }
 
 }  // namespace sdvar
@@ -630,8 +744,7 @@ int sdvar_vae_bind(sdvar_vae_t* v, const float* const* tensors, int32_t n_tensor
     if (b.rc) { set_error("vae_bind: failed while binding tensor %d", b.pos); return b.rc; }
     if (v->wt_out) { (void)hipFree(v->wt_out); v->wt_out = nullptr; }
     SDVAR_HIP(hipMalloc((void**)&v->wt_out, (size_t)cprev * 28 * sizeof(float)));
-    hipLaunchKernelGGL(convout_weight_kernel, dim3((cprev * 28 + 255) / 256), dim3(256), 0, (hipStream_t)stream, wo, v->wt_out, cprev);
-    SDVAR_LAUNCH_CHECK();
+    VAE_TRY(convout_weights(wo, v->wt_out, cprev, (hipStream_t)stream));
     v->bound = true;
     return SDVAR_OK;
 }
@@ -645,24 +758,15 @@ struct Runner {
     int H = 0;                               // current resolution (square)
     float *x, *h, *t;                        // residual stream, temporary, third buffer
 
-    const float* stats_src = nullptr;        // tensor whose GroupNorm partial sums the last convolution left in v->part ...
-    int stats_chunks = 0;                    // ... as this many 256-row chunks per image
+    const float* stats_src = nullptr;        // tensor whose GroupNorm partials the last convolution left in v->part ...
+    bool stats_up = false;                   // ... four per 256-row tile (the fused up-sampling launch)
 
     size_t M() const { return (size_t)B * H * H; }
     int stats_of(const float* src, int C) {
-        int chunks;
-        if (src == stats_src) {
-            chunks = stats_chunks;           // fused in the producing convolution's epilogue
-        } else {
-            const int nch = H < 64 ? H : 64, rpc = (H + nch - 1) / nch;
-            chunks = (H + rpc - 1) / rpc;
-            hipLaunchKernelGGL(gn_partial_kernel, dim3(chunks, B), dim3(320), 0, s, src, v->part, C, H, H, rpc);
-            SDVAR_LAUNCH_CHECK();
-        }
+        const bool fused = src == stats_src;
         stats_src = nullptr;
-        hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, v->part, v->stats, chunks, (double)H * H * (C / 32), 1e-6);
-        SDVAR_LAUNCH_CHECK();
-        return SDVAR_OK;
+        if (fused) return gn_stats_fused(v->part, v->stats, B, C, stats_up ? H * H / 4 : H * H, stats_up, s);      // H: already the output side
+        return gn_stats_rows(src, v->part, v->stats, B, C, H, H, s);
     }
     // planes of (optionally normalised / activated / up-sampled) src -> dst planes; returns via out params the operand geometry
     int prep(const float* src, int C, const NormW* nw, int silu, int up, uint16_t* dst, size_t dst_elems, size_t* ops, size_t* rows, int* G) {
@@ -677,7 +781,7 @@ struct Runner {
         int done = 0;
         VAE_TRY(conv_planes(xp, ops, rows, G, c.wp, c.wps, v->pfmt, c.wsc ? c.wsc + 1 : nullptr, c.bias, res, out, B, H, H, c.cout, c.cin, c.taps, v->ws, v->ws_floats, 0,
                             v->part, &done, -1, 0, s));
-        stats_src = done ? out : nullptr; stats_chunks = H * H / 256;
+        stats_src = done ? out : nullptr; stats_up = false;
         return SDVAR_OK;
     }
     int resblock(const ResW& r) {        // x <- shortcut(x) + conv2(silu(gn2(conv1(silu(gn1(x))))))          basic_vae.py:62-73
@@ -700,34 +804,7 @@ struct Runner {
         const int C = a.n.C;
         VAE_TRY(prep(x, C, &a.n, 0, 0, v->p1, v->p1_elems, &ops, &rows, &G));
         VAE_TRY(conv(a.qkv, v->p1, ops, rows, G, nullptr, h));
-        const int N = H * H;
-        const size_t lds_fix = ((size_t)32 * 256 + 32 * VA_QT) * sizeof(float), lds = lds_fix + (size_t)N * VA_SP * sizeof(float);
-        SDVAR_CHECK_ARG(C % 32 == 0, "vae: attention over %d channels (need a multiple of 32)", C);
-        const int qgroups = (N + VA_QT - 1) / VA_QT;
-        static const bool no_mfma = getenv("SDVAR_VAE_ATTN_FMA") != nullptr;       // A/B runs: the fp32-FMA kernel
-        if (!no_mfma && (N == 256 || N == 1024) && C % 64 == 0) {                  // 16^2 / 32^2 latents: the matrix-core kernel
-            const size_t lm = (size_t)16 * (N + 4) * sizeof(float);
-            if (N == 256) {
-                hipLaunchKernelGGL(vae_attn_mfma_kernel<2>, dim3(N / 16, B), dim3(512), lm, s, h, t, C, N);
-            } else {
-                SDVAR_HIP(hipFuncSetAttribute((const void*)vae_attn_mfma_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm));
-                hipLaunchKernelGGL(vae_attn_mfma_kernel<8>, dim3(N / 16, B), dim3(512), lm, s, h, t, C, N);
-            }
-            SDVAR_LAUNCH_CHECK();
-        } else if (lds <= 160 * 1024) {
-            SDVAR_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(vae_attn_kernel<false>, dim3(qgroups, B), dim3(256), lds, s, h, t, C, N, (float*)nullptr);
-            SDVAR_LAUNCH_CHECK();
-        } else {            // probabilities in the split-K workspace (idle between the qkv and the proj convolution), as many images per launch as fit
-            const size_t per_img = (size_t)qgroups * N * VA_SP;
-            const int nb_max = (int)(v->ws_floats / per_img);
-            SDVAR_CHECK_ARG(nb_max >= 1, "vae: attention over %d tokens needs %zu floats of scratch per image (workspace: %zu)", N, per_img, v->ws_floats);
-            for (int b0 = 0; b0 < B; b0 += nb_max) {
-                const int nb = B - b0 < nb_max ? B - b0 : nb_max;
-                hipLaunchKernelGGL(vae_attn_kernel<true>, dim3(qgroups, nb), dim3(256), lds_fix, s, h + (size_t)b0 * N * 3 * C, t + (size_t)b0 * N * C, C, N, v->ws);
-                SDVAR_LAUNCH_CHECK();
-            }
-        }
+        VAE_TRY(vae_attention(h, t, B, C, H * H, v->ws, v->ws_floats, -1, s));     // the probabilities may use the split-K workspace: idle between qkv and proj
         if (stats_src == t) stats_src = nullptr;
         VAE_TRY(prep(t, C, nullptr, 0, 0, v->p1, v->p1_elems, &ops, &rows, &G));
         VAE_TRY(conv(a.proj, v->p1, ops, rows, G, x, x));
@@ -770,7 +847,7 @@ int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, 
                 int done = 0;
                 VAE_TRY(conv_planes(v->p1, ops, rows, G, L.up.wp, L.up.wps, v->pfmt, L.up.wsc ? L.up.wsc + 1 : nullptr, L.up.bias, nullptr, r.h, B, r.H, r.H, L.up.cout,
                                     L.up.cin, 4, nullptr, 0, 0, v->part, &done, 0, v->npl * L.up.wps, s));
-                r.stats_src = done ? r.h : nullptr; r.stats_chunks = 4 * (r.H * r.H / 256);
+                r.stats_src = done ? r.h : nullptr; r.stats_up = true;
                 r.H <<= 1;
             } else {                                                                       // too few tiles: 3x3 on the up-sampled planes, split along K
                 VAE_TRY(r.prep(r.x, L.up9.cin, nullptr, 0, 1, v->p1, v->p1_elems, &ops, &rows, &G));
@@ -782,14 +859,7 @@ int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, 
     }
     // norm_out + SiLU + conv_out + clamp
     VAE_TRY(r.stats_of(r.x, v->c_out));
-    const size_t M = r.M();
-    hipLaunchKernelGGL(convout_partial_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, r.x, v->stats, v->norm_out.gamma, v->norm_out.beta, v->wt_out,
-                       v->t27, B, v->c_out, r.H, r.H);
-    SDVAR_LAUNCH_CHECK();
-    const size_t total = (size_t)B * 3 * r.H * r.H;
-    hipLaunchKernelGGL(convout_gather_kernel, dim3((unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192)), dim3(256), 0, s, v->t27, v->b_out, img, B, r.H, r.H);
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
+    return convout(r.x, v->stats, v->norm_out.gamma, v->norm_out.beta, v->wt_out, v->b_out, v->t27, img, B, v->c_out, r.H, r.H, s);
 }
 
 #define SDVAR_TRY_(call) do { int rc_ = (call); if (rc_ != SDVAR_OK) return rc_; } while (0)
@@ -809,6 +879,37 @@ int sdvar_op_conv_planes(const uint16_t* x_planes, uint64_t x_plane_stride, uint
                          int32_t taps, float* workspace, uint64_t workspace_floats, int32_t force_split, void* stream) {
     return conv_planes(x_planes, (size_t)x_plane_stride, (size_t)x_rows, x_row0, w_planes, (size_t)w_plane_stride, plane_format, w_scale ? w_scale + 1 : nullptr, bias, res, out,
                        B, H, W, N, Cin, taps, workspace, (size_t)workspace_floats, force_split, nullptr, nullptr, -1, 0, (hipStream_t)stream);
+}
+int sdvar_op_conv_planes_ex(const uint16_t* x_planes, uint64_t x_plane_stride, uint64_t x_rows, int32_t x_row0, const uint16_t* w_planes, uint64_t w_plane_stride,
+                            int32_t plane_format, const float* w_scale, const float* bias, const float* res, float* out, int32_t B, int32_t H, int32_t W, int32_t N,
+                            int32_t Cin, int32_t taps, float* workspace, uint64_t workspace_floats, int32_t force_split, int32_t up_phase, uint64_t w_phase_stride,
+                            double* gn_part, float* stats, int32_t* gn_done, void* stream) {
+    SDVAR_CHECK_ARG(!gn_part || (stats && gn_done), "conv_planes_ex: gn_part needs stats and gn_done");
+    int done = 0;
+    if (gn_done) *gn_done = 0;
+    SDVAR_TRY_(conv_planes(x_planes, (size_t)x_plane_stride, (size_t)x_rows, x_row0, w_planes, (size_t)w_plane_stride, plane_format, w_scale ? w_scale + 1 : nullptr, bias, res,
+                           out, B, H, W, N, Cin, taps, workspace, (size_t)workspace_floats, force_split, gn_part, &done, up_phase, (size_t)w_phase_stride, (hipStream_t)stream));
+    if (done) SDVAR_TRY_(gn_stats_fused(gn_part, stats, B, N, H * W, up_phase >= 0, (hipStream_t)stream));
+    if (gn_done) *gn_done = done;
+    return SDVAR_OK;
+}
+int sdvar_op_upconv_weights(const float* w, float* weff, int32_t Cout, int32_t Cin, void* stream) {
+    SDVAR_CHECK_ARG(w && weff && Cout >= 1 && Cin >= 1, "upconv_weights: bad arguments");
+    return upconv_weights(w, weff, Cout, Cin, (hipStream_t)stream);
+}
+int sdvar_op_vae_gn_stats(const float* x_rows, int32_t B, int32_t C, int32_t H, int32_t W, double* part_ws, float* stats, void* stream) {
+    return gn_stats_rows(x_rows, part_ws, stats, B, C, H, W, (hipStream_t)stream);
+}
+int sdvar_op_vae_attn(const float* qkv, float* out, int32_t B, int32_t C, int32_t N, float* workspace, uint64_t ws_floats, int32_t kernel, void* stream) {
+    return vae_attention(qkv, out, B, C, N, workspace, (size_t)ws_floats, kernel, (hipStream_t)stream);
+}
+int sdvar_op_vae_conv_out(const float* x_rows, const float* stats, const float* gamma, const float* beta, const float* w, const float* bias, float* img, int32_t B,
+                          int32_t C, int32_t H, int32_t W, float* workspace, void* stream) {
+    SDVAR_CHECK_ARG(x_rows && stats && gamma && beta && w && bias && img && workspace && B >= 1 && H >= 1 && W >= 1 && C >= 32 && C % 32 == 0,
+                    "vae_conv_out: bad arguments (B %d C %d H %d W %d)", B, C, H, W);
+    float* wt = workspace;
+    SDVAR_TRY_(convout_weights(w, wt, C, (hipStream_t)stream));
+    return convout(x_rows, stats, gamma, beta, wt, bias, workspace + (size_t)C * 28, img, B, C, H, W, (hipStream_t)stream);
 }
 
 }  // extern "C"

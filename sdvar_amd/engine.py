@@ -108,7 +108,12 @@ _SIGNATURES = {
     "sdvar_op_conv_weight_planes": (_I, [_P, _P, _I, _I, _I, _U64, _I, _P, _P]),
     "sdvar_op_vae_prep": (_I, [_P, _P, _P, _P, _P, _U64, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sdvar_op_conv_planes": (_I, [_P, _U64, _U64, _I, _P, _U64, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _U64, _I, _P]),
-    "sdvar_op_vae_img_planes": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P]),
+    "sdvar_op_conv_planes_ex": (_I, [_P, _U64, _U64, _I, _P, _U64, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _U64, _I, _I, _U64, _P, _P, C.POINTER(_I), _P]),
+    "sdvar_op_upconv_weights": (_I, [_P, _P, _I, _I, _P]),
+    "sdvar_op_vae_gn_stats": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "sdvar_op_vae_attn": (_I, [_P, _P, _I, _I, _I, _P, _U64, _I, _P]),
+    "sdvar_op_vae_conv_out": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "sdvar_op_vae_img_planes":(_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _P]),
     "sdvar_op_vae_s2d_planes": (_I, [_P, _P, _U64, _I, _I, _I, _I, _I, _I, _P]),
     "sdvar_op_vae_s2d_weights": (_I, [_P, _P, _I, _I, _P]),
     "sdvar_op_quant_nearest": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
