@@ -186,6 +186,64 @@ def test_xent_stats_against_torch(dev):
     assert torch.equal(am2, am) and torch.isfinite(nll2[1]).all()
 
 
+def xent_bound_c(V):
+    """c of |nll_hip - nll_64| <= c 2^-24 max(1, |lse|, |x_t|) for sdvar_xent_stats (csrc/xent.hip), from its operation count, first order, u = 2^-24.
+    The kernel forms s = sum_v exp(x_v - m), lse = m + log s, nll = lse - x_t.  Relative error of s (s >= 1, it holds the maximum's exp(0)), in units of u:
+      10      the subtractions x_v - m: u |x_v - m| on each exponent, weighted by the term's share of s: sum_v p_v |x_v - m| <= ln V <= 10 for V <= 16384
+       2      expf, 1 ulp = 2 u on every term
+      R + 8   additions a term passes through: 2 inside its float4, at most R = ceil(V / 256) down its lane's running sum, 6 in the butterfly
+      3 R + 2 the rescaling s <- s expf(m_old - m_new) of a lane's running sum, at most once per round: expf (2 u) and the product (u); its exponent's own
+              rounding is weighted by what survives the rescaling, sum_j d_j exp(-(d_j + d_j+1 + ...)) <= 2
+      26      six butterfly merges: both sides' expf and product (3 u), the sum (u), the exponents' roundings (<= 2 over all levels)
+    That relative error of s is an absolute one of log s.  Then, in units of u max(1, |lse|, |x_t|):
+      20      logf, 1 ulp of |log s| <= ln V <= 10 (not bounded by |lse| when m < 0): 2 u x 10
+       3      m + log s (u |lse|), lse - x_t (u |nll| <= u (|lse| + |x_t|))
+    c = 71 + 4 R."""
+    return 71 + 4 * ((V + 255) // 256)
+
+
+@pytest.mark.parametrize("V", [4, 1000, 4096, 16384])
+@pytest.mark.parametrize("B,L,tail", [(1, 5, 0), (3, 7, 7), (2, 681, 3)])
+def test_xent_stats_shapes_and_confident_rows(dev, V, B, L, tail):
+    """sdvar_xent_stats against fp64 F.cross_entropy: V = 4 (one float4, 63 idle lanes), 1000 (a ragged last round of the 64 lanes), 4096, 16384 (64 rounds);
+    B L = 5, 21, 1362 (none a multiple of the 4 rows per workgroup); tail = 0, tail = L and a short tail.  Every third row is confident: its target is the
+    maximum at about +30 over logits of magnitude 30 and nll is about 1e-4 - the kernel computes (m + log s) - x_t, so its error there is absolute, a few
+    ulp of 30.  Bound: xent_bound_c above (derived, not measured); torch's own float cross_entropy on the CPU must meet it on the same inputs."""
+    from sdvar_amd import engine as E
+    gen = torch.Generator().manual_seed(V + 7 * L)
+    lg = torch.randn(B, L, V, generator=gen) * 3
+    tg = torch.randint(0, V, (B, L), generator=gen)
+    conf = torch.zeros(B, L, dtype=torch.bool)
+    conf.view(-1)[::3] = True
+    # confident rows: the target at 30, the V - 1 others around 30 - ln(1e4) - ln(V - 1), so that sum_{v != t} exp(x_v - 30) ~ 1e-4
+    lo = 30.0 - np.log(1e4) - np.log(V - 1) + 0.3 * torch.randn(B, L, V, generator=gen)
+    lg[conf] = lo[conf]
+    lg.view(-1, V)[conf.view(-1), tg.view(-1)[conf.view(-1)]] = 30.0
+    lgd, tgd = lg.to(dev), tg.to(dev)
+    sums, nll, am = torch.zeros(4, dtype=torch.float64, device=dev), torch.empty(B, L, device=dev), torch.empty(B, L, dtype=torch.int64, device=dev)
+    E.xent_stats(lgd, tgd, tail, sums, nll_out=nll, argmax_out=am)
+    ref = F.cross_entropy(lg.double().view(-1, V), tg.view(-1), reduction="none").view(B, L)
+    assert 0.5e-4 <= ref[conf].min().item() and ref[conf].max().item() <= 2e-4
+    lse = torch.logsumexp(lg.double(), -1)
+    xt = lg.double().gather(-1, tg.unsqueeze(-1)).squeeze(-1)
+    bound = xent_bound_c(V) * 2.0 ** -24 * torch.maximum(torch.ones_like(lse), torch.maximum(lse.abs(), xt.abs()))
+    err = (nll.cpu().double() - ref).abs()
+    cpu32 = (F.cross_entropy(lg.view(-1, V), tg.view(-1), reduction="none").view(B, L).double() - ref).abs()
+    print(f"xent V={V} B L={B * L} tail={tail}: max|err| {err.max().item():.2e} (confident rows {err[conf].max().item():.2e}; torch float on the CPU {cpu32.max().item():.2e}; "
+          f"bound {bound.min().item():.2e} .. {bound.max().item():.2e})")
+    assert (cpu32 <= bound).all()
+    assert (err <= bound).all(), (err / bound).max().item()
+    assert torch.equal(am.cpu(), lg.argmax(-1))
+    n64 = nll.cpu().double()
+    cor = (am.cpu() == tg).double()
+    want = torch.stack([n64.sum(), n64[:, L - tail:].sum(), cor.sum(), cor[:, L - tail:].sum()])
+    s = sums.cpu()
+    assert torch.equal(s[2:], want[2:]) and s[2].item() >= conf.sum().item()
+    assert ((s[:2] - want[:2]).abs() <= 1e-12 * want[:2].abs()).all()
+    assert tail > 0 or (s[1].item() == 0.0 and s[3].item() == 0.0)
+    assert tail < L or torch.equal(s[0::2], s[1::2])
+
+
 def test_batching_over_passes(dev):
     g = golden("tf_d4_256_stress")
     m = _var(dev, g)

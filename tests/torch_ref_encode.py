@@ -80,7 +80,7 @@ def idxBl_to_var_input_torch(vae, ids):                # quant.py:169-184
     pns, C = q.v_patch_nums, q.Cvae
     B, H, SN = ids[0].shape[0], pns[-1], len(pns)
     E = q.embedding.weight.data
-    f_hat, nxt = torch.zeros(B, C, H, H), []
+    f_hat, nxt = torch.zeros(B, C, H, H, dtype=E.dtype), []                # a .double() model keeps the whole chain in fp64
     for si in range(SN - 1):
         h = F.interpolate(E[ids[si]].transpose(1, 2).reshape(B, C, pns[si], pns[si]), size=(H, H), mode="bicubic")
         f_hat.add_(_phi(q, si, SN, h))
