@@ -10,7 +10,8 @@
  * memory; the KV cache, adaLN table and workspaces it allocates itself are freed by the *_destroy calls.
  * One host thread per model object (same contract as the reference's module-attribute caches, basic_var.py:85-87); different
  * host threads may drive different objects on different streams concurrently (per-thread split-K workspaces, no shared mutable state
- * outside the objects; the sdvar_debug_* / sdvar_prof_* switches are process-wide and meant for single-threaded tools).
+ * outside the objects; the sdvar_debug_* / sdvar_prof_* switches are process-wide and meant for single-threaded tools: the kernel-variant
+ * switches live in one table of atomics (csrc/gemm_plan.h), so a GEMM call that reads one while a tool sets it sees the old or the new value).
  */
 #ifndef SDVAR_HIP_H
 #define SDVAR_HIP_H
@@ -20,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SDVAR_ABI_VERSION 4      /* 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
+#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU); 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
 #define SDVAR_MAX_STAGES 16
 
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
@@ -319,12 +320,21 @@ int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const 
                          int32_t M, int32_t N, int32_t K, int32_t epilogue, const float* res, int32_t ldres, const float* gate, int32_t rows_per_gate, int32_t gate_stride,
                          const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int32_t l, int32_t H, int32_t Lp, int32_t pos0, int32_t kv_fmt, void* stream);
 /* Select a kernel variant that otherwise only an environment variable (read at first use) selects - tests run the non-default variants in one process.
- * name: "gemm_h4_var" 0..3, "gemm_h2_stages" 2..6, "gemm_small_pp" 0..2, "attn_pp_sched" 0..3, "conv_pp" 0..2; value < 0 restores the environment / default. */
+ * name: "gemm_h4_var" 0..3, "gemm_h2_stages" 2..6, "gemm_small_pp" 0..2, "attn_pp_sched" 0..3, "conv_pp" 0..2; value < 0 restores the environment / default.
+ * A lookup in the library's one table of process-wide switches (csrc/gemm_plan.h), which sdvar_debug_set_rowblk ("rowblk" 0..2), sdvar_debug_set_qkv_fuse
+ * ("qkv_fuse" 0..1) and sdvar_debug_set_gemm_cfg write too; "gemm_v2" 0..1 (bf16x3: the 128-row tile on the LDS-DMA kernel, default 1) has no other setter. */
 int sdvar_debug_set_variant(const char* name, int32_t value);
-/* test aid: out4 = {row tile (32/64/128/256) of the LAST f16x2 GEMM call of this host thread, its K split, number of launches that took the hybrid tail
+/* test aid: out4 = {kernel code (as sdvar_debug_plan_gemm; 17 = row-block launch) of the LAST f16x2 GEMM call of this host thread, its K split, number of launches that took the hybrid tail
  * split since the last read, number of QKV launches that finished q and k in their epilogue since the last read}; reading resets the two counters.
  * Tests assert with it that the path they mean to cover is the one that ran. */
 int sdvar_debug_get_gemm_cfg(int32_t* out4);
+/* The GEMM planner (csrc/gemm_plan.h) on its own: what a GEMM of this shape would launch.  Pure host code - no HIP call, no GPU needed; a pure function of the
+ * arguments, the switches above and the SDVAR_GEMM_* environment.  mode: 0 f32, 1 bf16x3, 2 f16x2.  flags: bit 0 = the caller defers the K-slice sum to its
+ * consumer kernel, bit 1 = the call offers a QKV finish for the epilogue (sdvar_stage_forward's QKV launch), bit 2 = every output pointer and leading dimension
+ * allows 16-byte accesses (bits 0 and 1 matter in mode 2 only).  out4 = {kernel code, K split, hybrid tail split (0 = none), 1 if the QKV finish runs in the
+ * epilogue}; kernel codes: 16 = skinny (M <= 80), 32 / 64 / 128 / 256 = rows of a (rows x 128) tile, 512 = 256 x 256, 768 = 256 x 192 (17, the row-block
+ * launch, is asked for by its callers and never planned).  After an f16x2 GEMM call sdvar_debug_get_gemm_cfg reports the same kernel code and split. */
+int sdvar_debug_plan_gemm(int32_t mode, int32_t M, int32_t N, int32_t K, int32_t flags, int32_t* out4);
 /* f16x2 guard (debug, off by default; mode f16x2 only).  The f16x2 operand format of the default GEMM mode saturates finite activations at +-65504 and loses
  * relative precision below ~1e-3 (the reference computes these GEMMs in fp32: basic_var.py:44-52, 87-119).  With the guard on, every producer of GEMM operand
  * planes inside sdvar_stage_forward (ln_modulate, attention, the fc1 GELU epilogue) is followed by a counting pass over the plane it wrote.

@@ -8,7 +8,7 @@
 
 #include "../../include/sdvar_hip.h"
 #include "common.h"
-#include <string>
+#include "gemm_plan.h"
 
 namespace sdvar {
 
@@ -23,13 +23,12 @@ size_t splitk_workspace_floats();
 int qk_norm_append(const float* qkv, const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int kv_f16, int R, int l, int H, int Lmax, int pos0, const PendingSplitK* pend, int v_only, hipStream_t stream);
 int gemm_f16x2_qkv(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, int M, int N, int K,
                    const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int l, int H, int Lp, int pos0, int kv_fmt, int* defer, int* fused, hipStream_t stream);
-bool gemm_f16x2_rowblk_ok(int M, int N, int K, int ln, int qkv);
+bool gemm_f16x2_rowblk_ok(int M, int N, int K, int ln, int qkv, bool floor32);
 bool gemm_f16x2_rowblk_want(int M, int C, int V, int rows_per_img);
 int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* shift, int rows_per_img, int mod_stride, const uint16_t* X, size_t xps,
                       const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops, int M, int N, int K, int epi,
                       const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride,
                       const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int l, int H, int Lp, int pos0, int kv_fmt, hipStream_t stream);
-void debug_set_rowblk(int v);
 int silu_rows(const float* x, float* y, int n, hipStream_t stream);
 int add_row_vector(const float* src, const float* vec, float* out, int rows, int cols, hipStream_t stream);
 int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int R, int nlab, int num_classes,
@@ -49,15 +48,7 @@ int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, 
                   int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
 int split_planes_f16(const float* x, uint16_t* planes, int rows, int cols, size_t plane_stride, const float* scale, hipStream_t stream);
 int weight_scale_f16(const float* w, size_t n, float* sc, hipStream_t stream);
-void debug_set_gemm_cfg_h(int bm, int split);
-void debug_set_gemm_cfg_p(int bm, int split);
 void debug_set_gemm_stamps(unsigned long long* p);
-void debug_set_qkv_fuse(int on);
-void debug_set_h4_var(int v);
-void debug_set_h2_stages(int v);
-void debug_set_small_pp(int v);
-void debug_set_attn_pp_sched(int v);
-void debug_set_conv_pp(int v);
 void debug_get_gemm_cfg_h(int* out);
 int planes_guard(const uint16_t* h_plane, size_t n, unsigned long long* cnt, hipStream_t stream);
 int cfg_sample(const float* logits, int B, int l, int V, float one_plus_t, float t, int top_k, int use_top_p, float top_p_thr, const float* q, uint64_t seed,
@@ -69,7 +60,6 @@ int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, cons
 int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, float* out, hipStream_t stream);
 int gumbel_mix(const float* masked, int B, int l, int V, float scale, float tau, const float* e, uint64_t seed, uint32_t draw, uint32_t image_offset,
                const float* codebook, int Cv, float* h, hipStream_t stream);
-void debug_set_gemm_cfg(int bm, int split);
 int quant_code_norms(const float* codebook, float* e2, int V, int Cv, hipStream_t stream);
 int quant_nearest(const float* z, int N, int P, const float* codebook, const float* e2, int V, int Cv, long long* ids, int ids_stride, hipStream_t stream);
 int quant_encode_stage(float* f_rest, float* f_hat, float* z, float* up_scratch, const float* codebook, const float* e2, const float* Wdn_si, const float* Wup_si,
@@ -901,19 +891,17 @@ int sdvar_debug_set_gemm_cfg(int32_t bm, int32_t split) {
     // f16x2 only: bm 512 = the 256 x 256 tile kernel, 768 = the 256 x 192 one; bm 16 = the skinny kernel (M <= 80); bm 256 with split -T = hybrid tail split T ways (the other modes take their nearest tile)
     SDVAR_CHECK_ARG(bm == 0 || bm == 16 || bm == 32 || bm == 64 || bm == 128 || bm == 256 || bm == 512 || bm == 768, "debug_set_gemm_cfg: bm %d", bm);
     SDVAR_CHECK_ARG(split >= -64 && split <= 64 && (split >= 0 || bm == 256), "debug_set_gemm_cfg: split %d", split);
-    debug_set_gemm_cfg(bm >= 512 ? 256 : bm == 16 ? 32 : bm, split < 0 ? 0 : split);
-    debug_set_gemm_cfg_p(bm >= 512 ? 256 : bm == 16 ? 32 : bm, split < 0 ? 0 : split);
-    debug_set_gemm_cfg_h(bm, split);
+    g_variants[VAR_FORCE_BM].store(bm); g_variants[VAR_FORCE_SPLIT].store(split);
     return SDVAR_OK;
 }
 
-int sdvar_debug_set_qkv_fuse(int32_t on) { debug_set_qkv_fuse(on); return SDVAR_OK; }
-int sdvar_debug_set_rowblk(int32_t on) { debug_set_rowblk(on); return SDVAR_OK; }          // 0 off, 1 default (32 .. 80 rows), 2 every call of at most 80 rows
+int sdvar_debug_set_qkv_fuse(int32_t on) { g_variants[VAR_QKV_FUSE].put(on); return SDVAR_OK; }
+int sdvar_debug_set_rowblk(int32_t on) { g_variants[VAR_ROWBLK].put(on); return SDVAR_OK; }          // 0 off, 1 default (32 .. 80 rows), 2 every call of at most 80 rows
 int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const float* shift, int32_t rows_per_img, int32_t mod_stride, const uint16_t* Xp, uint64_t x_plane_stride,
                          const uint16_t* Wp, uint64_t w_plane_stride, const float* w_scale, const float* bias, float* out, int32_t ldo, uint16_t* out_planes, uint64_t out_plane_stride,
                          int32_t M, int32_t N, int32_t K, int32_t epi, const float* res, int32_t ldres, const float* gate, int32_t rows_per_gate, int32_t gate_stride,
                          const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int32_t l, int32_t H, int32_t Lp, int32_t pos0, int32_t kv_fmt, void* stream) {
-    SDVAR_CHECK_ARG(gemm_f16x2_rowblk_ok(M, N, K, x != nullptr, q_out != nullptr), "op_gemm_rowblk: M=%d N=%d K=%d outside the row-block kernel's range (M <= 80; K <= 1024 with a LayerNorm operand, <= 4096 with planes) or the kernel is switched off", M, N, K);
+    SDVAR_CHECK_ARG(gemm_f16x2_rowblk_ok(M, N, K, x != nullptr, q_out != nullptr, false), "op_gemm_rowblk: M=%d N=%d K=%d outside the row-block kernel's range (M <= 80; K <= 1024 with a LayerNorm operand, <= 4096 with planes) or the kernel is switched off", M, N, K);
     ProfScope ps(9, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), (hipStream_t)stream);
     return gemm_f16x2_rowblk(x, ldx, scale, shift, rows_per_img, mod_stride, Xp, (size_t)x_plane_stride, Wp, (size_t)w_plane_stride, w_scale ? w_scale + 1 : nullptr, bias, out, ldo, out_planes,
                              (size_t)out_plane_stride, M, N, K, epi, res, ldres, gate, rows_per_gate, gate_stride, scale_mul, q_out, k_cache, v_cache, l, H, Lp, pos0, kv_fmt, (hipStream_t)stream);
@@ -923,13 +911,17 @@ int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const 
 // environment / default.
 int sdvar_debug_set_variant(const char* name, int32_t value) {
     SDVAR_CHECK_ARG(name, "debug_set_variant: null name");
-    const std::string n(name);
-    if (n == "gemm_h4_var") { SDVAR_CHECK_ARG(value <= 3, "gemm_h4_var %d", value); debug_set_h4_var(value); }
-    else if (n == "gemm_h2_stages") { SDVAR_CHECK_ARG(value < 0 || value == 2 || value == 3 || value == 4 || value == 5 || value == 6, "gemm_h2_stages %d", value); debug_set_h2_stages(value); }
-    else if (n == "gemm_small_pp") { SDVAR_CHECK_ARG(value <= 2, "gemm_small_pp %d", value); debug_set_small_pp(value); }
-    else if (n == "attn_pp_sched") { SDVAR_CHECK_ARG(value <= 3, "attn_pp_sched %d", value); debug_set_attn_pp_sched(value); }
-    else if (n == "conv_pp") { SDVAR_CHECK_ARG(value <= 2, "conv_pp %d", value); debug_set_conv_pp(value); }
-    else { set_error("debug_set_variant: unknown variant '%s'", name); return SDVAR_ERR_ARG; }
+    return set_variant_by_name(name, value);
+}
+
+// The plan a GEMM of this shape gets (gemm_plan.h), without launching anything: pure host code, no HIP call.  mode: 0 f32, 1 bf16x3, 2 f16x2; flags: bit 0 the caller
+// defers the K-slice sum, bit 1 a QKV epilogue is offered, bit 2 the outputs allow 16-byte accesses; out4 = {kernel code, K split, hybrid tail split, QKV fused}.
+int sdvar_debug_plan_gemm(int32_t mode, int32_t M, int32_t N, int32_t K, int32_t flags, int32_t* out4) {
+    SDVAR_CHECK_ARG(out4 && mode >= 0 && mode <= 2, "debug_plan_gemm: mode %d", mode);
+    SDVAR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 32 == 0, "debug_plan_gemm: need K %% 32 == 0 (M=%d N=%d K=%d)", M, N, K);
+    const size_t wsf = splitk_workspace_floats();
+    const GemmPlan p = mode == 0 ? plan_f32(M, N, K, wsf) : mode == 1 ? plan_bf16x3(M, N, K, wsf) : plan_f16x2(M, N, K, wsf, flags & 1, flags & 2, flags & 4);
+    out4[0] = p.kernel; out4[1] = p.split; out4[2] = p.tail; out4[3] = p.qkv_fused;
     return SDVAR_OK;
 }
 

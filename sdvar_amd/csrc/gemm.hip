@@ -22,6 +22,7 @@
 //   EPI_BIAS_GELU   out = gelu_tanh(acc + bias)                         (basic_var.py:40,52)
 //   EPI_GATED_RES   out = res + (acc + bias) * gate[row / rows_per_gate] (basic_var.py:157-158: x + f(.)*gamma)
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace sdvar {
 
@@ -183,84 +184,52 @@ static thread_local float* g_ws_model = nullptr;   // a model object's own slabs
 float* set_splitk_workspace(float* p) { float* old = g_ws_model; g_ws_model = p; return old; }
 size_t splitk_workspace_floats() { return WS_FLOATS; }
 
-float* splitk_workspace(size_t* floats) {          // shared with gemm_bf16x3.hip
+float* splitk_workspace(size_t* floats) {          // shared with gemm_bf16x3.hip and gemm_f16x2.hip
     if (floats) *floats = WS_FLOATS;
     if (g_ws_model) return g_ws_model;
     if (!g_ws && hipMalloc((void**)&g_ws, WS_FLOATS * sizeof(float)) != hipSuccess) { set_error("split-K workspace allocation failed"); return nullptr; }
     return g_ws;
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_cfg(GemmArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+// every process-wide switch with a setter: name (sdvar_debug_set_variant), environment variable, default, legal range, value an out-of-range environment maps to
+Variant g_variants[VAR_COUNT] = {
+    {"gemm_h4_var", "SDVAR_GEMM_H4_VAR", 3, 0, 3, 3, false, false},             // which 256 x 256 kernel: 3 = 16x16x32 MFMAs, 0 - 2 = 32x32x16 and its DMA placements
+    {"gemm_h2_stages", "SDVAR_GEMM_H2_STAGES", 6, 2, 6, 6, false, false},       // ring of the 128 x 128 kernel
+    {"gemm_small_pp", "SDVAR_GEMM_SMALL_PP", 2, 0, 2, 2, false, false},         // 0 = ring kernel for every small tile, 1 = ping-pong kernel for 64-row tiles, 2 = for 32-row tiles too
+    {"attn_pp_sched", "SDVAR_ATTN_PP_SCHED", 1, 0, 3, 1, false, false},         // schedule of the 8-wave attention kernel
+    {"conv_pp", "SDVAR_CONV_PP", 2, 0, 2, 2, true, false},                      // decoder convolution loop
+    {"rowblk", "SDVAR_ROWBLK", 1, 0, 2, 1, false, false},                       // 0 off, 1 from 32 rows, 2 every call of at most 80 rows (sdvar_debug_set_rowblk)
+    {"qkv_fuse", "SDVAR_NO_QKV_FUSE", 1, 0, 1, 1, false, true},                 // QKV finish in the GEMM epilogue (sdvar_debug_set_qkv_fuse)
+    {"gemm_v2", nullptr, 1, 0, 1, 1, false, false},                             // bf16x3 128-row tile on the LDS-DMA kernel
+    {nullptr, nullptr, 0, 0, 768, 0, false, false},                             // forced tile, in f16x2's codes (sdvar_debug_set_gemm_cfg); 0 = automatic
+    {nullptr, nullptr, 0, -64, 64, 0, false, false},                            // forced K split; < 0 with tile 256: hybrid tail split
+};
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI>
+static int launch_f32_kernel(const GemmArgs& a, int grid, hipStream_t stream) {
     const size_t lds = 2 * (size_t)(BM + BN) * LDS_STRIDE * sizeof(float);
-    dim3 block(256);
     static LdsOptIn opt_in;         // > 64 KiB of dynamic LDS needs the opt-in once per kernel and device
-    SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_BIAS>, (const void*)gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_BIAS_GELU>,
-                     (const void*)gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_GATED_RES>, (const void*)gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_PARTIAL>);
-    const int nkt = a.K / BK;
-    if (split > 1) {
-        float* const ws = splitk_workspace(nullptr);          // the calling model's slabs, or this thread's
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_PARTIAL>), dim3(tiles * split), block, lds, stream, p);
-        SDVAR_LAUNCH_CHECK();
-        const size_t total = (size_t)a.M * (a.N / 4);
-        const int rgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        switch (epi) {
-            case EPI_BIAS: hipLaunchKernelGGL(splitk_reduce_kernel<EPI_BIAS>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-            case EPI_BIAS_GELU: hipLaunchKernelGGL(splitk_reduce_kernel<EPI_BIAS_GELU>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-            default: hipLaunchKernelGGL(splitk_reduce_kernel<EPI_GATED_RES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-        }
-        SDVAR_LAUNCH_CHECK();
-        return SDVAR_OK;
-    }
-    a.split = 1; a.k_per_split = nkt;
-    dim3 grid(tiles);
-    switch (epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_BIAS>), grid, block, lds, stream, a); break;
-        case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_BIAS_GELU>), grid, block, lds, stream, a); break;
-        case EPI_GATED_RES: hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI_GATED_RES>), grid, block, lds, stream, a); break;
-        default: set_error("gemm: unknown epilogue %d", epi); return SDVAR_ERR_ARG;
-    }
+    SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI>);
+    hipLaunchKernelGGL((gemm_f32_nt_kernel<BM, BN, WAVES_M, WAVES_N, EPI>), dim3(grid), dim3(256), lds, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
 
-static int g_force_bm = 0, g_force_split = 0;     // tools/gemm_bench.py --sweep (sdvar_debug_set_gemm_cfg); 0 = automatic
-void debug_set_gemm_cfg(int bm, int split) { g_force_bm = bm; g_force_split = split; }
+static int launch_reduce(const GemmArgs& a, const float* ws, int split, int epi, hipStream_t stream) {
+    return dispatch_epi(epi, [&](auto e) {
+        hipLaunchKernelGGL(splitk_reduce_kernel<decltype(e)::value>, dim3(splitk_reduce_grid(a.M, a.N)), dim3(256), 0, stream, ws, split, a.bias, a.out, a.res, a.gate, a.M, a.N, a.ldo, a.ldres,
+                           a.rows_per_gate, a.gate_stride);
+        SDVAR_LAUNCH_CHECK();
+        return SDVAR_OK;
+    });
+}
 
-// (row tile, K slices) as a pure function of the shape - the summation order, hence every output bit, depends only on
-// (M, N, K).  Cost model in MFMA cycles per CU, calibrated with tools/gemm_bench.py --sweep on MI355X:
-//   a workgroup spends 64 cycles x 16 x (bm/32 x 4 / 4 waves) per K-step on each SIMD; workgroups are dealt evenly over
-//   the 256 CUs, co-resident ones share the matrix pipes (so time ~ per-CU sum), a lone workgroup per CU cannot hide
-//   its LDS/barrier latency, every workgroup pays a fixed prologue/epilogue, and split > 1 pays the slab round trip.
-static void choose_cfg(int M, int N, int K, int* bm_out, int* split_out) {
-    const int nkt = K / BK, tiles_n = (N + 127) / 128;
-    double best = 1e30; int bbm = 128, bs = 1;
-    const int bms[3] = {128, 64, 32};
-    const int resident[3] = {2, 2, 3};                                   // workgroups per CU the LDS footprint admits
-    const double lat[4] = {0.0, 1.35, 1.08, 1.0};                        // slowdown of n co-resident workgroups' K-step (latency exposed when alone)
-    for (int bi = 0; bi < 3; ++bi) {
-        const int bm = bms[bi], res = resident[bi];
-        const int tiles = ((M + bm - 1) / bm) * tiles_n;
-        // MFMA cycles per K-step per workgroup; narrower tiles re-read more LDS/L2 per MFMA (measured +3 % / +12 %)
-        const double ktile = 64.0 * 16.0 * (bm / 32) * (bm == 32 ? 1.12 : (bm == 64 ? 1.03 : 1.0));
-        for (int split = 1; split <= 32 && split <= nkt / 2; ++split) {
-            if (split > 1 && ((size_t)split * M * N > WS_FLOATS || N % 4)) break;
-            const int kps = (nkt + split - 1) / split;
-            if ((nkt + kps - 1) / kps != split) continue;               // would leave empty trailing slices
-            const long blocks = (long)tiles * split;
-            const long per_cu = (blocks + 255) / 256;                    // workgroups the busiest CU executes
-            const double T = kps * ktile + 2500.0 + 40.0 * bm;           // one workgroup alone on the matrix pipes (+ prologue/epilogue)
-            const long full = per_cu / res, rem = per_cu % res;
-            double cyc = full * res * T * lat[res] + (rem ? rem * T * lat[rem] : 0.0);
-            if (split > 1) cyc += 6000.0 + (double)(split + 1) * M * N * 4.0 / 1800.0;   // reduce launch + slab traffic (~3.8 TB/s at 2.1 GHz)
-            if (cyc < best) { best = cyc; bbm = bm; bs = split; }
-        }
-    }
-    *bm_out = bbm; *split_out = bs;
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+static int launch_cfg(const GemmArgs& a, int epi, int split, hipStream_t stream) {
+    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+    return launch_splitk(a, epi, split, tiles, nullptr,
+                         [&](const GemmArgs& x, int grid, auto e) { return launch_f32_kernel<BM, BN, WAVES_M, WAVES_N, decltype(e)::value>(x, grid, stream); },
+                         [&](const GemmArgs& x, const float* ws, int sp, int ep) { return launch_reduce(x, ws, sp, ep, stream); });
 }
 
 // Host entry used by the model code and by the op-level C-ABI.
@@ -272,21 +241,11 @@ int gemm_f32_nt(const float* X, int ldx, const float* W, const float* bias, floa
     SDVAR_CHECK_ARG(((uintptr_t)X % 16) == 0 && ((uintptr_t)W % 16) == 0, "gemm: operands must be 16-byte aligned");
     SDVAR_CHECK_ARG(epi >= EPI_BIAS && epi <= EPI_GATED_RES, "gemm: unknown epilogue %d", epi);
     if (epi == EPI_GATED_RES) SDVAR_CHECK_ARG(res && gate && rows_per_gate > 0 && ldres >= N, "gemm: gated-residual epilogue needs res/gate");
-    GemmArgs a{X, W, bias, out, res, gate, M, N, K, ldx, ldo, ldres, rows_per_gate > 0 ? rows_per_gate : 1, gate_stride, 1, K / BK};
-    int bm, split;
-    choose_cfg(M, N, K, &bm, &split);
-    if (g_force_bm && g_force_bm <= 128) bm = g_force_bm;
-    if (g_force_split) {
-        split = g_force_split;
-        const int nkt = K / BK;
-        if (split > nkt) split = nkt;
-        while (split > 1 && (size_t)split * M * N > WS_FLOATS) --split;
-        const int kps = (nkt + split - 1) / split;
-        split = (nkt + kps - 1) / kps;
-    }
-    if (bm == 32) return launch_cfg<32, 128, 1, 4>(a, epi, split, stream);
-    if (bm == 64) return launch_cfg<64, 128, 2, 2>(a, epi, split, stream);
-    return launch_cfg<128, 128, 2, 2>(a, epi, split, stream);
+    const GemmArgs a{X, W, bias, out, res, gate, M, N, K, ldx, ldo, ldres, rows_per_gate > 0 ? rows_per_gate : 1, gate_stride, 1, K / BK};
+    const GemmPlan p = plan_f32(M, N, K, WS_FLOATS);
+    if (p.kernel == 32) return launch_cfg<32, 128, 1, 4>(a, epi, p.split, stream);
+    if (p.kernel == 64) return launch_cfg<64, 128, 2, 2>(a, epi, p.split, stream);
+    return launch_cfg<128, 128, 2, 2>(a, epi, p.split, stream);
 }
 
 }  // namespace sdvar

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace sdvar {
 
@@ -569,83 +570,9 @@ int split_planes(const float* x, uint16_t* planes, int rows, int cols, size_t pl
     return SDVAR_OK;
 }
 
-float* splitk_workspace(size_t* floats);     // gemm.hip: the shared slab workspace
-
-// cost-model constants (see choose_cfg_p; tools/fit_gemm_model.py on profiles/r01_e_gemm_sweep_bf16x3.jsonl: geometric-mean
-// regret 1.8 %, worst case 21 %, over the d12 / d16 shapes incl. gamma = 2 chunks)
-#define CM_R256 1
-#define CM_R128 1
-#define CM_R64 3
-#define CM_R32 3
-#define CM_P256 1.1
-#define CM_P64 1.3
-#define CM_P32 1.3
-#define CM_L1 1.2
-#define CM_L2 1.0
-#define CM_L3 1.0
-#define CM_KOVER 260.0
-#define CM_FIX 1500.0
-#define CM_FIXBM 20.0
-#define CM_RED0 2000.0
-#define CM_REDBW 5000.0
-
-static unsigned long long* g_dbg_stamps = nullptr;
-void debug_set_gemm_stamps(unsigned long long* p) { g_dbg_stamps = p; }
-unsigned long long* debug_get_gemm_stamps() { return g_dbg_stamps; }
-static int g_force_bm_p = 0, g_force_split_p = 0;
-void debug_set_gemm_cfg_p(int bm, int split) { g_force_bm_p = bm; g_force_split_p = split; }
-
-// same cost model as gemm.hip::choose_cfg with this kernel's constants: 6 MFMAs x 32 cycles per 16 k per 32x32 tile
-static void choose_cfg_p(int M, int N, int K, size_t ws_floats, int* bm_out, int* split_out, int* tail_out, bool allow_hybrid) {
-    const int nkt = K / PBK, tiles_n = (N + PBN - 1) / PBN;
-    double best = 1e30; int bbm = 128, bs = 1, btail = 0;
-    // per row-tile constants fitted to tools/gemm_bench.py --mode bf16x3 --sweep --dump (tools/fit_gemm_model.py):
-    //   resident workgroups per CU, K-step cost factor over the MFMA time, slowdown when 1 / 2 / 3 workgroups share a CU
-    const int bms[4] = {256, 128, 64, 32};
-    const int resident[4] = {CM_R256, CM_R128, CM_R64, CM_R32};
-    const double kfac[4] = {CM_P256, 1.0, CM_P64, CM_P32};
-    const double lat[5] = {0.0, CM_L1, CM_L2, CM_L3, 1.0};
-    for (int bi = 0; bi < 4; ++bi) {
-        const int bm = bms[bi], res = resident[bi];
-        const int tiles = ((M + bm - 1) / bm) * tiles_n;
-        const double ktile = 384.0 * (bm / 32) * kfac[bi];              // 6 MFMAs x 32 cycles x 2 k16-steps per 32x32 sub-tile
-        for (int split = 1; split <= 32 && split <= nkt / 2; ++split) {
-            if (split > 1 && ((size_t)split * M * N > ws_floats || N % 4)) break;
-            const int kps = (nkt + split - 1) / split;
-            if ((nkt + kps - 1) / kps != split) continue;
-            const long blocks = (long)tiles * split;
-            const long per_cu = (blocks + 255) / 256;
-            const double T = kps * (ktile + CM_KOVER) + CM_FIX + CM_FIXBM * bm;    // + per-K-step sync/refill, prologue + epilogue
-            const long full = per_cu / res, rem = per_cu % res;
-            const double l_full = (bm == 256) ? 1.0 : lat[res < 4 ? res : 4], l_rem = (bm == 256) ? 1.0 : lat[rem < 4 ? rem : 4];
-            double cyc = full * res * T * l_full + (rem ? rem * T * l_rem : 0.0);
-            if (split > 1) cyc += CM_RED0 + (double)(split + 1) * M * N * 4.0 / CM_REDBW;
-            if (cyc < best) { best = cyc; bbm = bm; bs = split; btail = 0; }
-        }
-        // hybrid for the 256-row tile: the full rounds run unsplit, only the last, partial round is split along K so that it, too,
-        // spreads over the CUs (264 tiles = 256 + 8: the 8 cost a whole second round otherwise)
-        if (allow_hybrid && bm == 256 && tiles > 256 && tiles % 256 && N % 4 == 0) {
-            const long fullr = tiles / 256, remt = tiles % 256;
-            const double Tfull = nkt * (ktile + CM_KOVER) + CM_FIX + CM_FIXBM * bm;
-            const int cand[7] = {2, 3, 4, 6, 8, 12, 16};
-            for (int ci = 0; ci < 7; ++ci) {
-                const int ts = cand[ci];
-                if (ts > nkt / 2 || (size_t)ts * remt * (256 * 128) > ws_floats) continue;
-                const int kps = (nkt + ts - 1) / ts;
-                if ((nkt + kps - 1) / kps != ts) continue;
-                const long rounds = (remt * ts + 255) / 256;
-                // the two extra launches are not free: ~10 us of prologue / slab epilogue / launch latency for the tail kernel, ~6 us for the reduce
-                const double cyc = fullr * Tfull + rounds * (kps * (ktile + CM_KOVER) + 20000.0) + 12000.0 + (double)(ts + 1) * remt * (256.0 * 128.0) * 4.0 / CM_REDBW;
-                if (cyc < best) { best = cyc; bbm = 256; bs = 1; btail = ts; }
-            }
-        }
-    }
-    *bm_out = bbm; *split_out = bs; *tail_out = btail;
-}
-
-static thread_local int* g_defer = nullptr;     // set per call by gemm_bf16x3_nt; thread-local: host threads may drive different model objects concurrently
-static bool g_use_v2 = true;
-void debug_set_gemm_v2(int on) { g_use_v2 = on != 0; }
+static std::atomic<unsigned long long*> g_dbg_stamps{nullptr};
+void debug_set_gemm_stamps(unsigned long long* p) { g_dbg_stamps.store(p, std::memory_order_relaxed); }
+unsigned long long* debug_get_gemm_stamps() { return g_dbg_stamps.load(std::memory_order_relaxed); }
 
 template <int EPI>
 static int launch_v2_kernel(const GemmPArgs& a, int grid, hipStream_t stream) {
@@ -667,113 +594,44 @@ static int launch_v3_kernel(const GemmPArgs& a, int grid, hipStream_t stream) {
     return SDVAR_OK;
 }
 
+template <int BM, int WAVES_M, int WAVES_N, int EPI>
+static int launch_p_kernel(const GemmPArgs& a, int grid, hipStream_t stream) {
+    const size_t lds = 3 * (size_t)(BM + PBN) * PROW * sizeof(uint16_t);      // at most 60 KB: no opt-in
+    hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, WAVES_M, WAVES_N, EPI>), dim3(grid), dim3(256), lds, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
 static int launch_reduce_p(const GemmPArgs& a, const float* ws, int split, int epi, hipStream_t stream) {
-    const size_t total = (size_t)a.M * (a.N / 4);
-    const int rgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    dim3 block(256);
-    switch (epi) {
-        case PEPI_BIAS: hipLaunchKernelGGL(splitk_reduce_p_kernel<PEPI_BIAS>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-        case PEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL(splitk_reduce_p_kernel<PEPI_BIAS_GELU_PLANES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-        default: hipLaunchKernelGGL(splitk_reduce_p_kernel<PEPI_GATED_RES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-    }
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
-}
-
-static int launch_v3(GemmPArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + PBN - 1) / PBN);
-    const int nkt = a.K / PBK;
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmPArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        int rc = launch_v3_kernel<PEPI_PARTIAL>(p, tiles * split, stream);
-        if (rc) return rc;
-        if (g_defer) { *g_defer = split; return SDVAR_OK; }
-        return launch_reduce_p(a, ws, split, epi, stream);
-    }
-    a.split = 1; a.k_per_split = nkt;
-    switch (epi) {
-        case PEPI_BIAS: return launch_v3_kernel<PEPI_BIAS>(a, tiles, stream);
-        case PEPI_BIAS_GELU_PLANES: return launch_v3_kernel<PEPI_BIAS_GELU_PLANES>(a, tiles, stream);
-        default: return launch_v3_kernel<PEPI_GATED_RES>(a, tiles, stream);
-    }
-}
-
-// full rounds unsplit + the partial last round split `tail` ways along K (compact slabs) + a reduce over the tail tiles only
-static int launch_v3_hybrid(GemmPArgs a, int epi, int tail, hipStream_t stream) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + PBN - 1) / PBN), full = tiles / 256 * 256, remt = tiles - full;
-    const int nkt = a.K / PBK;
-    size_t wsf = 0;
-    float* ws = splitk_workspace(&wsf);
-    if (!ws) return SDVAR_ERR_HIP;
-    GemmPArgs f = a;
-    f.split = 1; f.k_per_split = nkt; f.tile_off = 0; f.tile_cnt = full;
-    int rc;
-    switch (epi) {
-        case PEPI_BIAS: rc = launch_v3_kernel<PEPI_BIAS>(f, full, stream); break;
-        case PEPI_BIAS_GELU_PLANES: rc = launch_v3_kernel<PEPI_BIAS_GELU_PLANES>(f, full, stream); break;
-        default: rc = launch_v3_kernel<PEPI_GATED_RES>(f, full, stream); break;
-    }
-    if (rc) return rc;
-    GemmPArgs p = a;
-    p.out = ws; p.split = tail; p.k_per_split = (nkt + tail - 1) / tail; p.tile_off = full; p.tile_cnt = remt;
-    rc = launch_v3_kernel<PEPI_PARTIAL>(p, remt * tail, stream);
-    if (rc) return rc;
-    GemmPArgs r = a;
-    r.tile_off = full; r.tile_cnt = remt;
-    switch (epi) {
-        case PEPI_BIAS: hipLaunchKernelGGL(splitk_reduce_tiles_kernel<PEPI_BIAS>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r); break;
-        case PEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL(splitk_reduce_tiles_kernel<PEPI_BIAS_GELU_PLANES>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r); break;
-        default: hipLaunchKernelGGL(splitk_reduce_tiles_kernel<PEPI_GATED_RES>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r); break;
-    }
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
-}
-
-template <int BM, int WAVES_M, int WAVES_N>
-static int launch_p(GemmPArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + PBN - 1) / PBN);
-    const size_t lds = 3 * (size_t)(BM + PBN) * PROW * sizeof(uint16_t);
-    dim3 block(256);
-    const bool v2 = (BM == 128) && g_use_v2;
-    const int nkt = a.K / PBK;
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmPArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        if (v2) { int rc = launch_v2_kernel<PEPI_PARTIAL>(p, tiles * split, stream); if (rc) return rc; }
-        else { hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, WAVES_M, WAVES_N, PEPI_PARTIAL>), dim3(tiles * split), block, lds, stream, p); SDVAR_LAUNCH_CHECK(); }
-        if (g_defer) { *g_defer = split; return SDVAR_OK; }
-        const size_t total = (size_t)a.M * (a.N / 4);
-        const int rgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        switch (epi) {
-            case PEPI_BIAS: hipLaunchKernelGGL(splitk_reduce_p_kernel<PEPI_BIAS>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-            case PEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL(splitk_reduce_p_kernel<PEPI_BIAS_GELU_PLANES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-            default: hipLaunchKernelGGL(splitk_reduce_p_kernel<PEPI_GATED_RES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-        }
+    return dispatch_epi(epi, [&](auto e) {
+        hipLaunchKernelGGL(splitk_reduce_p_kernel<decltype(e)::value>, dim3(splitk_reduce_grid(a.M, a.N)), dim3(256), 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N,
+                           a.ldo, a.ldres, a.rows_per_gate, a.gate_stride);
         SDVAR_LAUNCH_CHECK();
         return SDVAR_OK;
-    }
-    a.split = 1; a.k_per_split = nkt;
-    if (v2) {
-        switch (epi) {
-            case PEPI_BIAS: return launch_v2_kernel<PEPI_BIAS>(a, tiles, stream);
-            case PEPI_BIAS_GELU_PLANES: return launch_v2_kernel<PEPI_BIAS_GELU_PLANES>(a, tiles, stream);
-            default: return launch_v2_kernel<PEPI_GATED_RES>(a, tiles, stream);
-        }
-    }
-    switch (epi) {
-        case PEPI_BIAS: hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, WAVES_M, WAVES_N, PEPI_BIAS>), dim3(tiles), block, lds, stream, a); break;
-        case PEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, WAVES_M, WAVES_N, PEPI_BIAS_GELU_PLANES>), dim3(tiles), block, lds, stream, a); break;
-        default: hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, WAVES_M, WAVES_N, PEPI_GATED_RES>), dim3(tiles), block, lds, stream, a); break;
-    }
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
+    });
+}
+
+// the 128-row tile runs on the LDS-DMA kernel unless gemm_v2 is switched off
+template <int BM, int WAVES_M, int WAVES_N, int EPI>
+static int launch_p_any(const GemmPArgs& a, int grid, hipStream_t stream) {
+    if (BM == 128 && variant(VAR_GEMM_V2)) return launch_v2_kernel<EPI>(a, grid, stream);
+    return launch_p_kernel<BM, WAVES_M, WAVES_N, EPI>(a, grid, stream);
+}
+
+static int launch_bf16x3(const GemmPArgs& a, int epi, const GemmPlan& p, int* defer, hipStream_t stream) {
+    const auto reduce = [&](const GemmPArgs& x, const float* ws, int sp, int ep) { return launch_reduce_p(x, ws, sp, ep, stream); };
+    const auto v3 = [&](const GemmPArgs& x, int grid, auto e) { return launch_v3_kernel<decltype(e)::value>(x, grid, stream); };
+    const auto tiles = [&](int bm) { return ((a.M + bm - 1) / bm) * ((a.N + PBN - 1) / PBN); };
+    if (p.kernel == 256 && p.tail > 0)
+        return launch_hybrid_tail(a, epi, p.tail, v3, [&](const float* ws, int tail, const GemmPArgs& r, int remt, auto e) {
+            hipLaunchKernelGGL(splitk_reduce_tiles_kernel<decltype(e)::value>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r);
+            SDVAR_LAUNCH_CHECK();
+            return SDVAR_OK;
+        });
+    if (p.kernel == 256) return launch_splitk(a, epi, p.split, tiles(256), defer, v3, reduce);
+    if (p.kernel == 32) return launch_splitk(a, epi, p.split, tiles(32), defer, [&](const GemmPArgs& x, int grid, auto e) { return launch_p_any<32, 1, 4, decltype(e)::value>(x, grid, stream); }, reduce);
+    if (p.kernel == 64) return launch_splitk(a, epi, p.split, tiles(64), defer, [&](const GemmPArgs& x, int grid, auto e) { return launch_p_any<64, 2, 2, decltype(e)::value>(x, grid, stream); }, reduce);
+    return launch_splitk(a, epi, p.split, tiles(128), defer, [&](const GemmPArgs& x, int grid, auto e) { return launch_p_any<128, 2, 2, decltype(e)::value>(x, grid, stream); }, reduce);
 }
 
 // X planes [3][M][K] (plane stride xps), W planes [3][N][K] (plane stride wps).  epi: 0 bias -> out fp32; 1 bias + GELU ->
@@ -783,7 +641,6 @@ static int launch_p(GemmPArgs a, int epi, int split, hipStream_t stream) {
 int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer,
                    hipStream_t stream) {
-    g_defer = defer;
     if (defer) *defer = 0;
     SDVAR_CHECK_ARG(X && W, "gemm_bf16x3: null operand");
     SDVAR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % PBK == 0, "gemm_bf16x3: need K %% 32 == 0 (M=%d N=%d K=%d)", M, N, K);
@@ -796,29 +653,11 @@ int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps,
 #else
     const int same_tile = 0;
 #endif
-    GemmPArgs a{X, W, xps, wps, bias, out, outp, ops, res, gate, M, N, K, ldo, ldres, rows_per_gate > 0 ? rows_per_gate : 1, gate_stride, 1, K / PBK,
-                g_dbg_stamps, same_tile, 0, 0};
-    size_t wsf = 0;
-    (void)splitk_workspace(&wsf);
-    int bm, split, tail = 0;
-    static const bool no_hybrid = getenv("SDVAR_GEMM_NO_HYBRID") != nullptr;       // A/B runs only
-    choose_cfg_p(M, N, K, wsf, &bm, &split, &tail, !no_hybrid);
-    if (g_force_bm_p) { bm = g_force_bm_p; tail = 0; }
-    static const bool trace = getenv("SDVAR_GEMM_TRACE") != nullptr;
-    if (trace) fprintf(stderr, "[gemm_bf16x3] M=%d N=%d K=%d epi=%d -> bm=%d split=%d tail=%d\n", M, N, K, epi, bm, split, tail);
-    if (g_force_split_p) {
-        split = g_force_split_p;
-        const int nkt = K / PBK;
-        if (split > nkt) split = nkt;
-        while (split > 1 && (size_t)split * M * N > wsf) --split;
-        const int kps = (nkt + split - 1) / split;
-        split = (nkt + kps - 1) / kps;
-    }
-    if (bm == 256 && tail > 0) return launch_v3_hybrid(a, epi, tail, stream);
-    if (bm == 256) return launch_v3(a, epi, split, stream);
-    if (bm == 32) return launch_p<32, 1, 4>(a, epi, split, stream);
-    if (bm == 64) return launch_p<64, 2, 2>(a, epi, split, stream);
-    return launch_p<128, 2, 2>(a, epi, split, stream);
+    const GemmPArgs a{X, W, xps, wps, bias, out, outp, ops, res, gate, M, N, K, ldo, ldres, rows_per_gate > 0 ? rows_per_gate : 1, gate_stride, 1, K / PBK,
+                      debug_get_gemm_stamps(), same_tile, 0, 0};
+    const GemmPlan p = plan_bf16x3(M, N, K, splitk_workspace_floats());
+    if (gemm_trace()) fprintf(stderr, "[gemm_bf16x3] M=%d N=%d K=%d epi=%d -> bm=%d split=%d tail=%d\n", M, N, K, epi, p.kernel, p.split, p.tail);
+    return launch_bf16x3(a, epi, p, defer, stream);
 }
 
 }  // namespace sdvar

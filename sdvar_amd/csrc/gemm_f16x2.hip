@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace sdvar {
 
@@ -1966,158 +1967,40 @@ int split_planes_f16(const float* x, uint16_t* planes, int rows, int cols, size_
     return SDVAR_OK;
 }
 
-float* splitk_workspace(size_t* floats);     // gemm.hip: the shared slab workspace
-
-// cost-model constants (see choose_cfg_h).  Fitted to a sweep with HBM-COLD weights (tools/micro/gemm_sweep_cold.sh: rotating weight tensors, as inside a
-// model pass; the earlier fit re-read one weight tensor out of the Infinity Cache) in which the launches whose K-slice sum a consumer kernel takes over are
-// timed as the slab launch alone and charged the consumer's slab reads instead of a reduce launch:
-// `tools/fit_gemm_model.py profiles/r02_gemm_sweep_cold_full.jsonl 192 profiles/r02_gemm_sweep_cold_slab.jsonl`: geometric-mean regret 1.1 %, worst case
-// 16 %, over the d12 / d16 shapes incl. gamma = 2 chunks (the constants before this fit: 6 % / 1.44x on the same data)
-#define CM_R256 1
-#define CM_R128 1
-#define CM_R64 2
-#define CM_R32 2
-#define CM_P256 1.0
-#define CM_P64 1.1
-#define CM_P32 1.8
-#define CM_L1 1.0
-#define CM_L2 0.8
-#define CM_L3 1.0
-#define CM_KOVER 260.0
-#define CM_FIX 8000.0
-#define CM_FIXBM 80.0
-#define CM_RED0 4000.0
-#define CM_REDBW 5000.0
-#define CM_DEFBW 2000.0     // bytes per cycle at which a deferring consumer (ln_modulate, qk_norm_append) reads the slabs: not fitted
-#define CM_K4 2850.0        // 256 x 256 kernel: cost per K-step in the units of the other tiles (3072 matrix-pipe cycles per K-step, at the higher clock the 16x16x32 shape holds)
-#define CM_FIX4 50000.0     // ... and its prologue + epilogue + launch, in the units of the other tiles' costs (calibrated on M = 2704 / 4096 / 6800, profiles/r03_gemm_tile_ab.log)
-
-static int g_force_bm_h = 0, g_force_split_h = 0;
-void debug_set_gemm_cfg_h(int bm, int split) { g_force_bm_h = bm; g_force_split_h = split; }
-// test aid: {row tile of the last gemm_f16x2_nt call of this host thread, its K split, launches that took the hybrid tail split since the last read,
-// QKV launches that finished q and k in their epilogue since the last read} - tests assert that the path they mean to cover is the one that ran
-static thread_local int g_last_cfg_h[4] = {0, 0, 0, 0};
-void debug_get_gemm_cfg_h(int* out) { for (int i = 0; i < 4; ++i) out[i] = g_last_cfg_h[i]; g_last_cfg_h[2] = g_last_cfg_h[3] = 0; }
-
-// same cost model as gemm_bf16x3.hip with half the matrix work per K-step: 3 MFMAs x 32 cycles per 16 k per 32x32 tile
-static int g_small_pp = -1;       // SDVAR_GEMM_SMALL_PP (A/B runs): 0 = the 4-wave ring kernel for every small tile, 1 = the K-split ping-pong kernel for 64-row tiles, 2 (default) = for 32-row tiles too
-static int small_pp_on() {          // 0 = ring kernel for every small tile, 1 = K-split ping-pong kernel for 64-row tiles, 2 = for 32-row tiles too
-    if (g_small_pp < 0) { const char* e = getenv("SDVAR_GEMM_SMALL_PP"); g_small_pp = e ? atoi(e) : 2; }          // default 2: qkv / fc1 at M = 144 / 256 16.7 -> 14.0 us, gemm_small class -2 % (profiles/r03_U_pp32_ab.log)
-    return g_small_pp;
-}
-static inline bool bm_is(int a, int b) { return a == b; }
-static void choose_cfg_h(int M, int N, int K, size_t ws_floats, int* bm_out, int* split_out, int* tail_out, bool allow_hybrid, bool deferred) {
-    const int nkt = K / HBK, tiles_n = (N + HBN - 1) / HBN;
-    double best = 1e30; int bbm = 128, bs = 1, btail = 0;
-    const bool spp = small_pp_on() >= 1, spp32 = small_pp_on() >= 2;       // the 64-row tile runs on gemm_f16x2_small_pp_kernel: 144 KB of LDS = ONE workgroup per CU, K-step ~0.8 of the ring kernel's (profiles/r03_x_smallpp_ab.log)
-    // per row-tile constants fitted to tools/gemm_bench.py --mode bf16x3 --sweep --dump (tools/fit_gemm_model.py):
-    //   resident workgroups per CU, K-step cost factor over the MFMA time, slowdown when 1 / 2 / 3 workgroups share a CU
-    const int bms[4] = {256, 128, 64, 32};
-    const int resident[4] = {CM_R256, CM_R128, CM_R64, CM_R32};
-    const double kfac[4] = {CM_P256, 1.0, CM_P64, CM_P32};
-    const double lat[5] = {0.0, CM_L1, CM_L2, CM_L3, 1.0};
-    for (int bi = 0; bi < 4; ++bi) {
-        const bool ppk = (bm_is(bms[bi], 64) && spp) || (bm_is(bms[bi], 32) && spp32);
-        const int bm = bms[bi], res = ppk ? 1 : resident[bi];
-        const int tiles = ((M + bm - 1) / bm) * tiles_n;
-        const double ktile = 192.0 * (bm / 32) * kfac[bi] * (ppk ? 0.8 : 1.0);              // 3 MFMAs x 32 cycles x 2 k16-steps per 32x32 sub-tile
-        for (int split = 1; split <= 32 && split <= nkt / 2; ++split) {
-            if (split > 1 && ((size_t)split * M * N > ws_floats || N % 4)) break;
-            const int kps = (nkt + split - 1) / split;
-            if ((nkt + kps - 1) / kps != split) continue;
-            const long blocks = (long)tiles * split;
-            const long per_cu = (blocks + 255) / 256;
-            const double T = kps * (ktile + CM_KOVER) + CM_FIX + CM_FIXBM * bm;    // + per-K-step sync/refill, prologue + epilogue
-            const long full = per_cu / res, rem = per_cu % res;
-            const double l_full = (bm == 256) ? 1.0 : lat[res < 4 ? res : 4], l_rem = (bm == 256) ? 1.0 : lat[rem < 4 ? rem : 4];
-            double cyc = full * res * T * l_full + (rem ? rem * T * l_rem : 0.0);
-            if (split > 1) cyc += deferred ? (double)split * M * N * 4.0 / CM_DEFBW : CM_RED0 + (double)(split + 1) * M * N * 4.0 / CM_REDBW;
-            if (cyc < best) { best = cyc; bbm = bm; bs = split; btail = 0; }
-        }
-        // hybrid for the 256-row tile: the full rounds run unsplit, only the last, partial round is split along K so that it, too,
-        // spreads over the CUs (264 tiles = 256 + 8: the 8 cost a whole second round otherwise)
-        if (allow_hybrid && bm == 256 && tiles > 256 && tiles % 256 && N % 4 == 0) {
-            const long fullr = tiles / 256, remt = tiles % 256;
-            const double Tfull = nkt * (ktile + CM_KOVER) + CM_FIX + CM_FIXBM * bm;
-            const int cand[7] = {2, 3, 4, 6, 8, 12, 16};
-            for (int ci = 0; ci < 7; ++ci) {
-                const int ts = cand[ci];
-                if (ts > nkt / 2 || (size_t)ts * remt * (256 * 128) > ws_floats) continue;
-                const int kps = (nkt + ts - 1) / ts;
-                if ((nkt + kps - 1) / kps != ts) continue;
-                const long rounds = (remt * ts + 255) / 256;
-                // the two extra launches are not free: ~10 us of prologue / slab epilogue / launch latency for the tail kernel, ~6 us for the reduce
-                const double cyc = fullr * Tfull + rounds * (kps * (ktile + CM_KOVER) + 20000.0) + 12000.0 + (double)(ts + 1) * remt * (256.0 * 128.0) * 4.0 / CM_REDBW;
-                if (cyc < best) { best = cyc; bbm = 256; bs = 1; btail = ts; }
-            }
-        }
-    }
-    // the 256 x 256 ping-pong kernel (bm code 512): its K loop runs at the matrix pipe's issue rate (3072 cycles per K-step for twice the tile, in-kernel stamps:
-    // tools/micro/gemm_v4_stamps.py) but it needs one workgroup per CU and whole rounds of 256 tiles; unsplit only
-    static const bool no_v4 = getenv("SDVAR_GEMM_NO_V4") != nullptr;       // A/B runs only
-    if (!no_v4 && N >= 256 && M > 512) {
-        const long tiles4 = (long)((M + 255) / 256) * ((N + 255) / 256), rounds = (tiles4 + 255) / 256;
-        const double cyc = rounds * (nkt * CM_K4 + CM_FIX4);
-        if (cyc < best) { best = cyc; bbm = 512; bs = 1; btail = 0; }
-    }
-    // the 256 x 192 ping-pong kernel (bm code 768): 3/4 of the 256 x 256 tile's matrix work per K-step and whole rounds where N / 192 x M / 256 fills the chip better
-    // than N / 256 does (N = 3 C); same conditions.  Constants: the 256 x 256 kernel's scaled by the MFMA count (72 of 96 per wave and K-step) and
-    // the epilogue's share of the fixed part; checked against tools/gemm_bench.py --force on the d12 / d16 shapes (profiles/r04_n_v7_ab.log)
-    static const bool no_v7 = getenv("SDVAR_GEMM_NO_V7") != nullptr;       // A/B runs only
-    if (!no_v4 && !no_v7 && N >= 192 && N % 64 == 0 && M > 512) {      // a ragged last column tile is fine (N = 4096: 22 tiles; d16 fc1 at M = 2704: 68.7 against 78.0 us)
-        const long tiles7 = (long)((M + 255) / 256) * ((N + 191) / 192), rounds = (tiles7 + 255) / 256;
-        const double cyc = rounds * (nkt * (0.75 * CM_K4) + 0.85 * CM_FIX4);
-        if (cyc < best) { best = cyc; bbm = 768; bs = 1; btail = 0; }
-    }
-    *bm_out = bbm; *split_out = bs; *tail_out = btail;
+// test aid: the plan of the last gemm_f16x2_nt / gemm_f16x2_qkv / gemm_f16x2_rowblk call of this host thread, and how many launches since the last read took the hybrid
+// tail split / finished q and k in their epilogue - tests assert that the path they mean to cover is the one that ran
+static thread_local struct { GemmPlan plan; int tail_launches, fused_launches; } g_last_plan = {{0, 0, 0, false}, 0, 0};
+void debug_get_gemm_cfg_h(int* out) {
+    out[0] = g_last_plan.plan.kernel; out[1] = g_last_plan.plan.split; out[2] = g_last_plan.tail_launches; out[3] = g_last_plan.fused_launches;
+    g_last_plan.tail_launches = g_last_plan.fused_launches = 0;
 }
 
-static thread_local int* g_defer_h = nullptr;     // set per call by gemm_bf16x3_nt; thread-local: host threads may drive different model objects concurrently
+// gemm_h2_stages, the variant of the 128 x 128 kernel: 6 (default, round 3) = 4-stage ring, the two waves of a SIMD alternate (1 - 7 % faster than 4: profiles/r03_l_v2pp_ab.log;
+// the same kernel on 16x16x32 MFMAs was built, passed the suite and was no faster - this tile is DMA / CU-intake bound, not power bound: profiles/r03_r_v6_ab.log);
+// 4 (round-2 default) = 3-stage ring with software-pipelined fragment reads (3-10 % faster than 3 on the shapes
+// that use this tile); 3 = 3-stage ring, reads in front of the MFMAs; 2 = 2-stage ring, two workgroups per CU (SDVAR_GEMM_H2_STAGES for A/B runs)
 
-static int g_h2_stages = -1;      // variant of the 128 x 128 kernel: 6 (default, round 3) = 4-stage ring, the two waves of a SIMD alternate (1 - 7 % faster than 4: profiles/r03_l_v2pp_ab.log;
-                                   // the same kernel on 16x16x32 MFMAs was built, passed the suite and was no faster - this tile is DMA / CU-intake bound, not power bound: profiles/r03_r_v6_ab.log);
-                                   // 4 (round-2 default) = 3-stage ring with software-pipelined fragment reads (3-10 % faster than 3 on the shapes
-                                   // that use this tile); 3 = 3-stage ring, reads in front of the MFMAs; 2 = 2-stage ring, two workgroups per CU (SDVAR_GEMM_H2_STAGES for A/B runs)
-
-template <int EPI>
-static int launch_h2_kernel(const GemmHArgs& a, int grid, hipStream_t stream) {
-    if (g_h2_stages < 0) { const char* e = getenv("SDVAR_GEMM_H2_STAGES"); g_h2_stages = (e && atoi(e) == 2) ? 2 : (e && atoi(e) == 3) ? 3 : (e && atoi(e) == 5) ? 5 : (e && atoi(e) == 4) ? 4 : 6; }
-    if (g_h2_stages == 5) {        // 5-stage ring (160 KB): four K-steps in flight
-        const size_t lds = 5 * (size_t)H2_STAGE * sizeof(uint16_t);
-        static LdsOptIn opt_in5;
-        SDVAR_LDS_OPT_IN(opt_in5, lds, (const void*)gemm_f16x2_v2_kernel<EPI, 5>);
-        hipLaunchKernelGGL((gemm_f16x2_v2_kernel<EPI, 5>), dim3(grid), dim3(512), lds, stream, a);
-        SDVAR_LAUNCH_CHECK();
-        return SDVAR_OK;
+template <int EPI, int NS>
+static int launch_h2_ring(const GemmHArgs& a, int grid, hipStream_t stream) {
+    constexpr int STAGES = NS == 6 ? 4 : NS == 4 ? 3 : NS;          // 5: 160 KB, four K-steps in flight; 6: 128 KB, ping-pong halves; 4 / 3: 96 KB; 2: 64 KB, two workgroups per CU
+    const size_t lds = STAGES * (size_t)H2_STAGE * sizeof(uint16_t);
+    if (NS != 2) {          // the 64 KB ring needs no opt-in
+        static LdsOptIn opt_in;
+        SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)gemm_f16x2_v2_kernel<EPI, NS>);
     }
-    if (g_h2_stages == 6) {        // 4 stages (128 KB), ping-pong halves
-        const size_t lds = 4 * (size_t)H2_STAGE * sizeof(uint16_t);
-        static LdsOptIn opt_in6;
-        SDVAR_LDS_OPT_IN(opt_in6, lds, (const void*)gemm_f16x2_v2_kernel<EPI, 6>);
-        hipLaunchKernelGGL((gemm_f16x2_v2_kernel<EPI, 6>), dim3(grid), dim3(512), lds, stream, a);
-        SDVAR_LAUNCH_CHECK();
-        return SDVAR_OK;
-    }
-    if (g_h2_stages == 4) {        // 3 stages, software-pipelined fragment reads
-        const size_t lds = 3 * (size_t)H2_STAGE * sizeof(uint16_t);
-        static LdsOptIn opt_in4;
-        SDVAR_LDS_OPT_IN(opt_in4, lds, (const void*)gemm_f16x2_v2_kernel<EPI, 4>);
-        hipLaunchKernelGGL((gemm_f16x2_v2_kernel<EPI, 4>), dim3(grid), dim3(512), lds, stream, a);
-        SDVAR_LAUNCH_CHECK();
-        return SDVAR_OK;
-    }
-    if (g_h2_stages == 2) {
-        const size_t lds = 2 * (size_t)H2_STAGE * sizeof(uint16_t);      // 64 KB
-        hipLaunchKernelGGL((gemm_f16x2_v2_kernel<EPI, 2>), dim3(grid), dim3(512), lds, stream, a);
-        SDVAR_LAUNCH_CHECK();
-        return SDVAR_OK;
-    }
-    const size_t lds = 3 * (size_t)H2_STAGE * sizeof(uint16_t);      // 96 KB
-    static LdsOptIn opt_in;
-    SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)gemm_f16x2_v2_kernel<EPI, 3>);
-    hipLaunchKernelGGL((gemm_f16x2_v2_kernel<EPI, 3>), dim3(grid), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((gemm_f16x2_v2_kernel<EPI, NS>), dim3(grid), dim3(512), lds, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
+}
+template <int EPI>
+static int launch_h2_kernel(const GemmHArgs& a, int grid, hipStream_t stream) {
+    switch (variant(VAR_GEMM_H2_STAGES)) {
+        case 5: return launch_h2_ring<EPI, 5>(a, grid, stream);
+        case 6: return launch_h2_ring<EPI, 6>(a, grid, stream);
+        case 4: return launch_h2_ring<EPI, 4>(a, grid, stream);
+        case 2: return launch_h2_ring<EPI, 2>(a, grid, stream);
+        default: return launch_h2_ring<EPI, 3>(a, grid, stream);
+    }
 }
 
 template <int EPI>
@@ -2130,80 +2013,20 @@ static int launch_h3_kernel(const GemmHArgs& a, int grid, hipStream_t stream) {
     return SDVAR_OK;
 }
 
-static int g_h4_var = -1;          // which 256 x 256 kernel (SDVAR_GEMM_H4_VAR, A/B runs)
+// gemm_h4_var, which 256 x 256 kernel: 3 (default) = the 16x16x32 kernel (gemm_f16x2_v5_kernel): 8 - 10 % faster than 0 on qkv / fc1 at M >= 2704
+// (profiles/r03_p_v5_ab.log); 0 - 2 = the 32x32x16 kernel and its DMA placements
 template <int EPI>
 static int launch_h4_kernel(const GemmHArgs& a, int grid, hipStream_t stream) {
     const size_t lds = 2 * (size_t)H4_STAGE * sizeof(uint16_t);      // 128 KB
-    if (g_h4_var < 0) { const char* e = getenv("SDVAR_GEMM_H4_VAR"); g_h4_var = e ? atoi(e) : 3; if (g_h4_var < 0 || g_h4_var > 3) g_h4_var = 3; }        // 3 (default) = the 16x16x32 kernel (gemm_f16x2_v5_kernel): 8 - 10 % faster than 0 on
-                                                                                                                             // qkv / fc1 at M >= 2704 (profiles/r03_p_v5_ab.log); 0 - 2 = the 32x32x16 kernel and its DMA placements
-    static LdsOptIn opt_in;
+    const int var = variant(VAR_GEMM_H4);
+    static LdsOptIn opt_in;         // ONE flag for the four kernels it opts in
     SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)gemm_f16x2_v4_kernel<EPI, 0>, (const void*)gemm_f16x2_v4_kernel<EPI, 1>, (const void*)gemm_f16x2_v4_kernel<EPI, 2>, (const void*)gemm_f16x2_v5_kernel<EPI>);
-    if (g_h4_var == 3) hipLaunchKernelGGL((gemm_f16x2_v5_kernel<EPI>), dim3(grid), dim3(512), lds, stream, a);
-    else if (g_h4_var == 1) hipLaunchKernelGGL((gemm_f16x2_v4_kernel<EPI, 1>), dim3(grid), dim3(512), lds, stream, a);
-    else if (g_h4_var == 2) hipLaunchKernelGGL((gemm_f16x2_v4_kernel<EPI, 2>), dim3(grid), dim3(512), lds, stream, a);
+    if (var == 3) hipLaunchKernelGGL((gemm_f16x2_v5_kernel<EPI>), dim3(grid), dim3(512), lds, stream, a);
+    else if (var == 1) hipLaunchKernelGGL((gemm_f16x2_v4_kernel<EPI, 1>), dim3(grid), dim3(512), lds, stream, a);
+    else if (var == 2) hipLaunchKernelGGL((gemm_f16x2_v4_kernel<EPI, 2>), dim3(grid), dim3(512), lds, stream, a);
     else hipLaunchKernelGGL((gemm_f16x2_v4_kernel<EPI, 0>), dim3(grid), dim3(512), lds, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
-}
-void debug_set_h4_var(int v) { g_h4_var = v; }
-void debug_set_h2_stages(int v) { g_h2_stages = v; }
-void debug_set_small_pp(int v) { g_small_pp = v; }
-
-static int launch_reduce_h(const GemmHArgs& a, const float* ws, int split, int epi, hipStream_t stream) {
-    const size_t total = (size_t)a.M * (a.N / 4);
-    const int rgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    dim3 block(256);
-    switch (epi) {
-        case HEPI_BIAS: hipLaunchKernelGGL(splitk_reduce_h_kernel<HEPI_BIAS>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-        case HEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL(splitk_reduce_h_kernel<HEPI_BIAS_GELU_PLANES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-        default: hipLaunchKernelGGL(splitk_reduce_h_kernel<HEPI_GATED_RES>, dim3(rgrid), block, 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N, a.ldo, a.ldres, a.rows_per_gate, a.gate_stride); break;
-    }
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
-}
-
-static int launch_h3(GemmHArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + HBN - 1) / HBN);
-    const int nkt = a.K / HBK;
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmHArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        int rc = launch_h3_kernel<HEPI_PARTIAL>(p, tiles * split, stream);
-        if (rc) return rc;
-        if (g_defer_h) { *g_defer_h = split; return SDVAR_OK; }
-        return launch_reduce_h(a, ws, split, epi, stream);
-    }
-    a.split = 1; a.k_per_split = nkt;
-    switch (epi) {
-        case HEPI_BIAS: return launch_h3_kernel<HEPI_BIAS>(a, tiles, stream);
-        case HEPI_BIAS_GELU_PLANES: return launch_h3_kernel<HEPI_BIAS_GELU_PLANES>(a, tiles, stream);
-        default: return launch_h3_kernel<HEPI_GATED_RES>(a, tiles, stream);
-    }
-}
-
-static int launch_h4(GemmHArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-    const int nkt = a.K / HBK;
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmHArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        int rc = launch_h4_kernel<HEPI_PARTIAL>(p, tiles * split, stream);
-        if (rc) return rc;
-        if (g_defer_h) { *g_defer_h = split; return SDVAR_OK; }
-        return launch_reduce_h(a, ws, split, epi, stream);
-    }
-    a.split = 1; a.k_per_split = nkt;
-    switch (epi) {
-        case HEPI_BIAS: return launch_h4_kernel<HEPI_BIAS>(a, tiles, stream);
-        case HEPI_BIAS_GELU_PLANES: return launch_h4_kernel<HEPI_BIAS_GELU_PLANES>(a, tiles, stream);
-        default: return launch_h4_kernel<HEPI_GATED_RES>(a, tiles, stream);
-    }
 }
 
 template <int EPI>
@@ -2215,93 +2038,10 @@ static int launch_h7_kernel(const GemmHArgs& a, int grid, hipStream_t stream) {
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
-static int launch_h7(GemmHArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + 191) / 192);
-    const int nkt = a.K / HBK;
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmHArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        int rc = launch_h7_kernel<HEPI_PARTIAL>(p, tiles * split, stream);
-        if (rc) return rc;
-        if (g_defer_h) { *g_defer_h = split; return SDVAR_OK; }
-        return launch_reduce_h(a, ws, split, epi, stream);
-    }
-    a.split = 1; a.k_per_split = nkt;
-    switch (epi) {
-        case HEPI_BIAS: return launch_h7_kernel<HEPI_BIAS>(a, tiles, stream);
-        case HEPI_BIAS_GELU_PLANES: return launch_h7_kernel<HEPI_BIAS_GELU_PLANES>(a, tiles, stream);
-        default: return launch_h7_kernel<HEPI_GATED_RES>(a, tiles, stream);
-    }
-}
 
-template <int MT, int NW>
-static int launch_skinny_mt(GemmHArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles_n = (a.N + 15) / 16, nkt = a.K / HBK;
-    const size_t lds = (size_t)NW * MT * 64 * 16;
-    GemmHArgs p = a;
-    p.split = split; p.k_per_split = (nkt + split - 1) / split;
-    const dim3 grid(tiles_n * split), block(64 * NW);
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        p.out = ws; p.ldo = a.N;
-        hipLaunchKernelGGL((gemm_f16x2_skinny_kernel<MT, NW, HEPI_PARTIAL>), grid, block, lds, stream, p);
-        SDVAR_LAUNCH_CHECK();
-        if (g_defer_h) { *g_defer_h = split; return SDVAR_OK; }
-        return launch_reduce_h(a, ws, split, epi, stream);
-    }
-    switch (epi) {
-        case HEPI_BIAS: hipLaunchKernelGGL((gemm_f16x2_skinny_kernel<MT, NW, HEPI_BIAS>), grid, block, lds, stream, p); break;
-        case HEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL((gemm_f16x2_skinny_kernel<MT, NW, HEPI_BIAS_GELU_PLANES>), grid, block, lds, stream, p); break;
-        default: hipLaunchKernelGGL((gemm_f16x2_skinny_kernel<MT, NW, HEPI_GATED_RES>), grid, block, lds, stream, p); break;
-    }
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
-}
-// M <= 80 rows: NW waves per workgroup and the K split so that a wave streams at most 8 K-steps
-template <int NW>
-static int launch_skinny(const GemmHArgs& a, int epi, int split, hipStream_t stream) {
-    const int mt = (a.M + 15) / 16;
-    switch (mt) {
-        case 1: return launch_skinny_mt<1, NW>(a, epi, split, stream);
-        case 2: return launch_skinny_mt<2, NW>(a, epi, split, stream);
-        case 3: return launch_skinny_mt<3, NW>(a, epi, split, stream);
-        case 4: return launch_skinny_mt<4, NW>(a, epi, split, stream);
-        default: return launch_skinny_mt<5, NW>(a, epi, split, stream);
-    }
-}
-
-// full rounds unsplit + the partial last round split `tail` ways along K (compact slabs) + a reduce over the tail tiles only
-static int launch_h3_hybrid(GemmHArgs a, int epi, int tail, hipStream_t stream) {
-    const int tiles = ((a.M + 255) / 256) * ((a.N + HBN - 1) / HBN), full = tiles / 256 * 256, remt = tiles - full;
-    const int nkt = a.K / HBK;
-    size_t wsf = 0;
-    float* ws = splitk_workspace(&wsf);
-    if (!ws) return SDVAR_ERR_HIP;
-    GemmHArgs f = a;
-    f.split = 1; f.k_per_split = nkt; f.tile_off = 0; f.tile_cnt = full;
-    int rc;
-    switch (epi) {
-        case HEPI_BIAS: rc = launch_h3_kernel<HEPI_BIAS>(f, full, stream); break;
-        case HEPI_BIAS_GELU_PLANES: rc = launch_h3_kernel<HEPI_BIAS_GELU_PLANES>(f, full, stream); break;
-        default: rc = launch_h3_kernel<HEPI_GATED_RES>(f, full, stream); break;
-    }
-    if (rc) return rc;
-    GemmHArgs p = a;
-    p.out = ws; p.split = tail; p.k_per_split = (nkt + tail - 1) / tail; p.tile_off = full; p.tile_cnt = remt;
-    rc = launch_h3_kernel<HEPI_PARTIAL>(p, remt * tail, stream);
-    if (rc) return rc;
-    GemmHArgs r = a;
-    r.tile_off = full; r.tile_cnt = remt;
-    switch (epi) {
-        case HEPI_BIAS: hipLaunchKernelGGL(splitk_reduce_tiles_h_kernel<HEPI_BIAS>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r); break;
-        case HEPI_BIAS_GELU_PLANES: hipLaunchKernelGGL(splitk_reduce_tiles_h_kernel<HEPI_BIAS_GELU_PLANES>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r); break;
-        default: hipLaunchKernelGGL(splitk_reduce_tiles_h_kernel<HEPI_GATED_RES>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r); break;
-    }
+template <int MT, int NW, int EPI>
+static int launch_skinny_kernel(const GemmHArgs& a, int grid, hipStream_t stream) {
+    hipLaunchKernelGGL((gemm_f16x2_skinny_kernel<MT, NW, EPI>), dim3(grid), dim3(64 * NW), (size_t)NW * MT * 64 * 16, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
@@ -2326,64 +2066,83 @@ static int launch_small_pp(const GemmHArgs& a, int grid, hipStream_t stream) {
 }
 template <int BM, int EPI>
 static int launch_small_any(const GemmHArgs& a, int grid, hipStream_t stream) {
-    if (!a.stamps && (BM == 64 ? small_pp_on() : small_pp_on() >= 2)) return launch_small_pp<BM, EPI>(a, grid, stream);          // gemm_small_pp: 1 = 64-row tiles only, 2 = 32-row tiles too
+    if (!a.stamps && (BM == 64 ? variant(VAR_GEMM_SMALL_PP) : variant(VAR_GEMM_SMALL_PP) >= 2)) return launch_small_pp<BM, EPI>(a, grid, stream);          // gemm_small_pp: 1 = 64-row tiles only, 2 = 32-row tiles too
     return launch_small_kernel<BM, 3, EPI>(a, grid, stream);
 }
 
-template <int BM>
-static int launch_h(GemmHArgs a, int epi, int split, hipStream_t stream) {
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + HBN - 1) / HBN);
-    constexpr bool v2 = (BM == 128);
-    constexpr int SB = BM == 32 ? 32 : 64;
-    const int nkt = a.K / HBK;
-    if (split > 1) {
-        size_t wsf = 0;
-        float* ws = splitk_workspace(&wsf);
-        if (!ws) return SDVAR_ERR_HIP;
-        GemmHArgs p = a;
-        p.out = ws; p.ldo = a.N; p.split = split; p.k_per_split = (nkt + split - 1) / split;
-        int rc = v2 ? launch_h2_kernel<HEPI_PARTIAL>(p, tiles * split, stream) : launch_small_any<SB, HEPI_PARTIAL>(p, tiles * split, stream);
-        if (rc) return rc;
-        if (g_defer_h) { *g_defer_h = split; return SDVAR_OK; }
-        if (SDVAR_DBG(a, 8)) return SDVAR_OK;      // timing experiments: the slab launch alone (what a deferring caller pays)
-        return launch_reduce_h(a, ws, split, epi, stream);
+static int launch_reduce_h(const GemmHArgs& a, const float* ws, int split, int epi, hipStream_t stream) {
+    return dispatch_epi(epi, [&](auto e) {
+        hipLaunchKernelGGL(splitk_reduce_h_kernel<decltype(e)::value>, dim3(splitk_reduce_grid(a.M, a.N)), dim3(256), 0, stream, ws, split, a.bias, a.out, a.outp, a.ops, a.res, a.gate, a.M, a.N,
+                           a.ldo, a.ldres, a.rows_per_gate, a.gate_stride);
+        SDVAR_LAUNCH_CHECK();
+        return SDVAR_OK;
+    });
+}
+
+// One tile family (kern(args, workgroups, EpiTag)): the QKV finish in the epilogue where the plan says so, else the shared split / reduce / epilogue sequence
+template <class Kern>
+static int launch_family(const GemmHArgs& a, int epi, const GemmPlan& p, const GemmCall& call, int tiles, bool skip_reduce, hipStream_t stream, Kern&& kern) {
+    if (p.qkv_fused) {
+        GemmHArgs q = a;
+        q.qk = *call.qkv; q.split = 1; q.k_per_split = a.K / HBK;
+        *call.fused = 1;
+        return kern(q, tiles, EpiTag<HEPI_QKV>{});
     }
-    a.split = 1; a.k_per_split = nkt;
-    switch (epi) {
-        case HEPI_BIAS: return v2 ? launch_h2_kernel<HEPI_BIAS>(a, tiles, stream) : launch_small_any<SB, HEPI_BIAS>(a, tiles, stream);
-        case HEPI_BIAS_GELU_PLANES: return v2 ? launch_h2_kernel<HEPI_BIAS_GELU_PLANES>(a, tiles, stream) : launch_small_any<SB, HEPI_BIAS_GELU_PLANES>(a, tiles, stream);
-        default: return v2 ? launch_h2_kernel<HEPI_GATED_RES>(a, tiles, stream) : launch_small_any<SB, HEPI_GATED_RES>(a, tiles, stream);
+    return launch_splitk(a, epi, p.split, tiles, call.defer, kern, [&](const GemmHArgs& x, const float* ws, int sp, int ep) { return launch_reduce_h(x, ws, sp, ep, stream); }, skip_reduce);
+}
+
+static int launch_f16x2(const GemmHArgs& a, int epi, const GemmPlan& p, const GemmCall& call, hipStream_t stream) {
+    const int tm256 = (a.M + 255) / 256, tn128 = (a.N + HBN - 1) / HBN;
+    const auto h3 = [&](const GemmHArgs& x, int grid, auto e) { return launch_h3_kernel<decltype(e)::value>(x, grid, stream); };
+    const bool slabs_only = SDVAR_DBG(a, 8) != 0;      // timing experiments: the slab launch alone (what a deferring caller pays)
+    switch (p.kernel) {
+        case 16: {      // M <= 80 rows, NW = 4 waves per workgroup; the planner chose the K split so that a wave streams at most 8 K-steps
+            const auto reduce = [&](const GemmHArgs& x, const float* ws, int sp, int ep) { return launch_reduce_h(x, ws, sp, ep, stream); };
+            const int tiles = (a.N + 15) / 16;
+            switch ((a.M + 15) / 16) {
+                case 1: return launch_splitk(a, epi, p.split, tiles, call.defer, [&](const GemmHArgs& x, int grid, auto e) { return launch_skinny_kernel<1, 4, decltype(e)::value>(x, grid, stream); }, reduce);
+                case 2: return launch_splitk(a, epi, p.split, tiles, call.defer, [&](const GemmHArgs& x, int grid, auto e) { return launch_skinny_kernel<2, 4, decltype(e)::value>(x, grid, stream); }, reduce);
+                case 3: return launch_splitk(a, epi, p.split, tiles, call.defer, [&](const GemmHArgs& x, int grid, auto e) { return launch_skinny_kernel<3, 4, decltype(e)::value>(x, grid, stream); }, reduce);
+                case 4: return launch_splitk(a, epi, p.split, tiles, call.defer, [&](const GemmHArgs& x, int grid, auto e) { return launch_skinny_kernel<4, 4, decltype(e)::value>(x, grid, stream); }, reduce);
+                default: return launch_splitk(a, epi, p.split, tiles, call.defer, [&](const GemmHArgs& x, int grid, auto e) { return launch_skinny_kernel<5, 4, decltype(e)::value>(x, grid, stream); }, reduce);
+            }
+        }
+        case 768: return launch_family(a, epi, p, call, tm256 * ((a.N + 191) / 192), false, stream, [&](const GemmHArgs& x, int grid, auto e) { return launch_h7_kernel<decltype(e)::value>(x, grid, stream); });
+        case 512: return launch_family(a, epi, p, call, tm256 * ((a.N + 255) / 256), false, stream, [&](const GemmHArgs& x, int grid, auto e) { return launch_h4_kernel<decltype(e)::value>(x, grid, stream); });
+        case 256:
+            if (p.tail > 0)
+                return launch_hybrid_tail(a, epi, p.tail, h3, [&](const float* ws, int tail, const GemmHArgs& r, int remt, auto e) {
+                    hipLaunchKernelGGL(splitk_reduce_tiles_h_kernel<decltype(e)::value>, dim3(32 * remt), dim3(256), 0, stream, ws, tail, r);
+                    SDVAR_LAUNCH_CHECK();
+                    return SDVAR_OK;
+                });
+            return launch_family(a, epi, p, call, tm256 * tn128, false, stream, h3);
+        case 128: return launch_family(a, epi, p, call, ((a.M + 127) / 128) * tn128, slabs_only, stream, [&](const GemmHArgs& x, int grid, auto e) { return launch_h2_kernel<decltype(e)::value>(x, grid, stream); });
+        case 64: return launch_family(a, epi, p, call, ((a.M + 63) / 64) * tn128, slabs_only, stream, [&](const GemmHArgs& x, int grid, auto e) { return launch_small_any<64, decltype(e)::value>(x, grid, stream); });
+        default: return launch_family(a, epi, p, call, ((a.M + 31) / 32) * tn128, slabs_only, stream, [&](const GemmHArgs& x, int grid, auto e) { return launch_small_any<32, decltype(e)::value>(x, grid, stream); });
     }
 }
 
 // ---- row-block launches (gemm_f16x2_rowblk_kernel): M <= 80 ---------------------------------------------------------------------------
-static thread_local bool g_rowblk_floor = false;   // set around the model's query (gemm_f16x2_rowblk_want)
-static int g_rowblk = -1;          // SDVAR_ROWBLK (A/B runs): 0 = the round-3 launch sequence (ln_modulate + skinny / small_pp + qk_norm_append) at every M
-void debug_set_rowblk(int v) { g_rowblk = v; }
 // can the (LayerNorm +) GEMM (+ QKV finish) of this shape run as one row-block launch?  ln: the operand is the fp32 residual stream (K = C)
-bool gemm_f16x2_rowblk_ok(int M, int N, int K, int ln, int qkv) {
-    if (g_rowblk < 0) { const char* e = getenv("SDVAR_ROWBLK"); g_rowblk = e ? atoi(e) : 1; }
-    if (!g_rowblk || g_force_bm_h) return false;                 // a forced tile (tests of the other kernels) keeps the old sequence
+// floor32: the model's own calls (not the op-level tests) come with a floor - below 32 rows the old sequence wins.  A 16-row call is ONE row block: its QKV launch has
+// H x 3 workgroups pulling 256 KB of W each, and with one image per row every workgroup also reads 16 x 8 KB of modulation vectors - a CU takes in only
+// ~45 GB/s of L2 hits / ~20 GB/s of HBM misses, so bytes per workgroup decide (d16 stage 0: 0.84 ms fused against 0.78 ms; stage 1, M = 64: 0.84 against 0.96)
+bool gemm_f16x2_rowblk_ok(int M, int N, int K, int ln, int qkv, bool floor32) {
+    if (!variant(VAR_ROWBLK) || variant(VAR_FORCE_BM)) return false;                 // a forced tile (tests of the other kernels) keeps the old sequence
     if (M < 1 || M > 80 || K % HBK) return false;
-    // the model's own calls (not the op-level tests) come with a floor: below 32 rows the old sequence wins.  A 16-row call is ONE row block: its QKV launch has
-    // H x 3 workgroups pulling 256 KB of W each, and with one image per row every workgroup also reads 16 x 8 KB of modulation vectors - a CU takes in only
-    // ~45 GB/s of L2 hits / ~20 GB/s of HBM misses, so bytes per workgroup decide (d16 stage 0: 0.84 ms fused against 0.78 ms; stage 1, M = 64: 0.84 against 0.96)
-    if (g_rowblk_floor && M < 32) return false;
+    if (floor32 && M < 32) return false;
     if (ln ? K > 1024 : K > 4096) return false;
     return qkv ? N % 64 == 0 : N % 16 == 0;
 }
 
-// stage_forward's question: should a call with M rows take the row-block sequence?  (2 forces it at every M <= 80: A/B runs and the tests of the 16-row shapes)
+// stage_forward's question: should a call with M rows take the row-block sequence?  (rowblk = 2 forces it at every M <= 80: A/B runs and the tests of the 16-row shapes)
 bool gemm_f16x2_rowblk_want(int M, int C, int V, int rows_per_img) {
-    g_rowblk_floor = true;
-    if (g_rowblk < 0) { const char* e = getenv("SDVAR_ROWBLK"); g_rowblk = e ? atoi(e) : 1; }
-    if (g_rowblk == 2) g_rowblk_floor = false;
+    const bool floor = variant(VAR_ROWBLK) != 2;
     // ... and a width floor: at C = 768 (d12) the QKV launch has only 36 x ceil(M / 16) workgroups and fc1 falls between one and two rounds - stage 1 of d12 ran
     // 0.68 ms fused against 0.62 ms (profiles/r04_g_stage_d12.log); at C = 1024 (d16) 0.86 against 0.96
     // ... and at least 4 rows per image (the measured cases: l = 4, 5): with one image per row (stage 0 of a large batch) a row block reads 16 x 8 KB of modulation vectors
-    const bool ok = (!g_rowblk_floor || (C >= 1024 && rows_per_img >= 4)) && gemm_f16x2_rowblk_ok(M, 3 * C, C, 1, 1) && gemm_f16x2_rowblk_ok(M, C, 4 * C, 0, 0) && gemm_f16x2_rowblk_ok(M, V, C, 1, 0);
-    g_rowblk_floor = false;
-    return ok;
+    return (!floor || (C >= 1024 && rows_per_img >= 4)) && gemm_f16x2_rowblk_ok(M, 3 * C, C, 1, 1, floor) && gemm_f16x2_rowblk_ok(M, C, 4 * C, 0, 0, floor) && gemm_f16x2_rowblk_ok(M, V, C, 1, 0, floor);
 }
 
 template <int NT, int KS, int EPI, int LN>
@@ -2401,7 +2160,7 @@ int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* 
                       const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride,
                       const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int l, int H, int Lp, int pos0, int kv_fmt, hipStream_t stream) {
     const bool ln = x != nullptr, qkv = q_out != nullptr;
-    SDVAR_CHECK_ARG(W && (ln || X) && gemm_f16x2_rowblk_ok(M, N, K, ln, qkv), "gemm_f16x2_rowblk: shape M=%d N=%d K=%d (ln %d, qkv %d) not supported", M, N, K, (int)ln, (int)qkv);
+    SDVAR_CHECK_ARG(W && (ln || X) && gemm_f16x2_rowblk_ok(M, N, K, ln, qkv, false), "gemm_f16x2_rowblk: shape M=%d N=%d K=%d (ln %d, qkv %d) not supported", M, N, K, (int)ln, (int)qkv);
     SDVAR_CHECK_ARG(!ln || (scale && shift && rows_per_img > 0 && ldx >= K && ldx % 4 == 0 && mod_stride % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0),
                     "gemm_f16x2_rowblk: bad LayerNorm operand");
     SDVAR_CHECK_ARG(((uintptr_t)W % 16) == 0 && wps % 8 == 0 && (ln || (((uintptr_t)X % 16) == 0 && xps % 8 == 0)), "gemm_f16x2_rowblk: planes must be 16-byte aligned");
@@ -2415,7 +2174,6 @@ int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* 
     auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
     ra.g.vec = N % 4 == 0 && al16(bias) && al16(out) && al16(outp) && al16(res) && al16(gate) && ldo % 4 == 0 && ops % 4 == 0 && (epi != HEPI_GATED_RES || (ldres % 4 == 0 && gate_stride % 4 == 0));
     ra.x = x; ra.ldx = ldx; ra.scale = scale; ra.shift = shift; ra.rows_per_img = rows_per_img > 0 ? rows_per_img : 1; ra.mod_stride = mod_stride; ra.eps = 1e-6f;
-    static const bool trace = getenv("SDVAR_GEMM_TRACE") != nullptr;
     const int rb = (M + 15) / 16;
     // column tiles per workgroup: bytes a workgroup pulls through its CU (W 16 nt columns + its 16 rows of x + their modulation vectors, all K long) x rounds of 256
     // workgroups - a CU takes in ~45 GB/s of L2 hits, so this product is what a launch costs (the fixed part is the same for every nt)
@@ -2431,8 +2189,8 @@ int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* 
         }
     }
     if (!ln) nt = 1;
-    if (trace) fprintf(stderr, "[gemm_f16x2] M=%d N=%d K=%d epi=%d -> rowblk ln=%d qkv=%d nt=%d\n", M, N, K, epi, (int)ln, (int)qkv, qkv ? 4 : nt);
-    g_last_cfg_h[0] = 17; g_last_cfg_h[1] = 1;
+    if (gemm_trace()) fprintf(stderr, "[gemm_f16x2] M=%d N=%d K=%d epi=%d -> rowblk ln=%d qkv=%d nt=%d\n", M, N, K, epi, (int)ln, (int)qkv, qkv ? 4 : nt);
+    g_last_plan.plan = GemmPlan{17, 1, 0, false};
     if (qkv) return launch_rowblk_kernel<4, 4, HEPI_QKV, 1>(ra, stream);
     if (ln) {
         if (epi == HEPI_BIAS_GELU_PLANES) return nt == 1 ? launch_rowblk_kernel<1, 4, HEPI_BIAS_GELU_PLANES, 1>(ra, stream) : nt == 2 ? launch_rowblk_kernel<2, 4, HEPI_BIAS_GELU_PLANES, 1>(ra, stream)
@@ -2444,39 +2202,9 @@ int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* 
     return launch_rowblk_kernel<1, 16, HEPI_BIAS, 0>(ra, stream);
 }
 
-// X planes [2][K/32][M][32] (plane stride xps), W planes [2][K/32][N][32] of W * 2^S (plane stride wps), wsi -> 2^-S on the device (null: 1).
-// epi: 0 bias -> out fp32; 1 bias + GELU -> outp planes of (M, N) (plane stride ops); 2 gated residual -> out fp32.
-// defer: as gemm_bf16x3_nt (the slabs already carry the 2^-S factor).
-int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
-                  int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer,
-                  hipStream_t stream);
-static bool g_qkv_fuse_off = false;
-void debug_set_qkv_fuse(int on) { g_qkv_fuse_off = !on; }
-static thread_local const QkvEpi* g_qkv_epi = nullptr;      // set by gemm_f16x2_qkv around its call of gemm_f16x2_nt
-static thread_local int* g_qkv_fused = nullptr;
-
-// The QKV launch of a transformer block: as gemm_f16x2_nt(epi 0, out = the (M, 3 H 64) fp32 qkv buffer, defer), but when the launch comes out UNSPLIT the
-// q, k and v are finished in the epilogue (QkvEpi) and *fused = 1: the caller runs no qk_norm_append at all.  Otherwise *fused = 0 and the
-// result is in `out` (or in the slabs, *defer > 0) as before.
-int gemm_f16x2_qkv(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, int M, int N, int K,
-                   const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int l, int H, int Lp, int pos0, int kv_fmt, int* defer, int* fused, hipStream_t stream) {
-    SDVAR_CHECK_ARG(fused && defer && q_out && k_cache && v_cache && l > 0 && H > 0 && N == 3 * H * 64 && M % l == 0, "gemm_f16x2_qkv: bad arguments (M=%d N=%d l=%d H=%d)", M, N, l, H);
-    *fused = 0;
-    static const bool env_off = getenv("SDVAR_NO_QKV_FUSE") != nullptr;      // A/B runs
-    const bool off = env_off || g_qkv_fuse_off;
-    const QkvEpi e{scale_mul, q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, l, H, Lp, pos0, kv_fmt};
-    const bool ok = !off && (kv_fmt == 3 || kv_fmt == 4) && (H * 64) % 128 == 0 && ((uintptr_t)q_out % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 && Lp % 8 == 0;
-    g_qkv_epi = ok ? &e : nullptr; g_qkv_fused = fused;
-    const int rc = gemm_f16x2_nt(X, xps, W, wps, wsi, bias, out, ldo, nullptr, 0, M, N, K, HEPI_BIAS, nullptr, 0, nullptr, 1, 0, defer, stream);
-    g_qkv_epi = nullptr; g_qkv_fused = nullptr;
-    return rc;
-}
-
-int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
-                  int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer,
-                  hipStream_t stream) {
-    g_defer_h = defer;
-    if (defer) *defer = 0;
+static int gemm_f16x2_run(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
+                          int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, const GemmCall& call, hipStream_t stream) {
+    if (call.defer) *call.defer = 0;
     SDVAR_CHECK_ARG(X && W, "gemm_f16x2: null operand");
     SDVAR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % HBK == 0, "gemm_f16x2: need K %% 32 == 0 (M=%d N=%d K=%d)", M, N, K);
     SDVAR_CHECK_ARG(epi >= HEPI_BIAS && epi <= HEPI_GATED_RES, "gemm_f16x2: unknown epilogue %d", epi);
@@ -2494,67 +2222,35 @@ int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, 
     auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
     a.vec = N % 4 == 0 && al16(bias) && al16(out) && al16(outp) && al16(res) && al16(gate) && ldo % 4 == 0 && ops % 4 == 0 &&
             (epi != HEPI_GATED_RES || (ldres % 4 == 0 && gate_stride % 4 == 0));
-    size_t wsf = 0;
-    (void)splitk_workspace(&wsf);
-    int bm, split, tail = 0;
-    static const bool no_hybrid = getenv("SDVAR_GEMM_NO_HYBRID") != nullptr;       // A/B runs only
-    // a QKV launch that can finish q and k in its epilogue stays off the hybrid tail split (whose tail tiles go through slabs): the fused epilogue saves more
-    const bool qkv = g_qkv_epi != nullptr && a.vec;
-    choose_cfg_h(M, N, K, wsf, &bm, &split, &tail, !no_hybrid && !qkv, defer != nullptr);
-    if (g_force_bm_h) { bm = g_force_bm_h; tail = 0; }
-    if (g_force_bm_h == 256 && g_force_split_h < 0) {        // test aid: force the hybrid tail split -split ways (where the shape has a partial last round)
-        const int tiles = ((M + 255) / 256) * ((N + HBN - 1) / HBN), remt = tiles % 256, nkt = K / HBK;
-        int ts = -g_force_split_h;
-        if (ts > nkt / 2) ts = nkt / 2;
-        const int kps = ts > 0 ? (nkt + ts - 1) / ts : nkt;
-        if (tiles > 256 && remt && !qkv && N % 4 == 0 && ts >= 2 && (nkt + kps - 1) / kps == ts && (size_t)ts * remt * (256 * 128) <= wsf) { tail = ts; split = 1; }
+    GemmPlan tiled;
+    const GemmPlan p = plan_f16x2(M, N, K, splitk_workspace_floats(), call.defer != nullptr, call.qkv != nullptr, a.vec != 0, &tiled);
+    if (gemm_trace()) {
+        fprintf(stderr, "[gemm_f16x2] M=%d N=%d K=%d epi=%d -> bm=%d split=%d tail=%d\n", M, N, K, epi, tiled.kernel, tiled.split, tiled.tail);
+        if (p.kernel == 16) fprintf(stderr, "[gemm_f16x2] M=%d N=%d K=%d epi=%d -> skinny split=%d\n", M, N, K, epi, p.split);
     }
-    static const bool trace = getenv("SDVAR_GEMM_TRACE") != nullptr;
-    if (trace) fprintf(stderr, "[gemm_f16x2] M=%d N=%d K=%d epi=%d -> bm=%d split=%d tail=%d\n", M, N, K, epi, bm, split, tail);
-    if (g_force_split_h > 0) {
-        split = g_force_split_h;
-        const int nkt = K / HBK;
-        if (split > nkt) split = nkt;
-        while (split > 1 && (size_t)split * M * N > wsf) --split;
-        const int kps = (nkt + split - 1) / split;
-        split = (nkt + kps - 1) / kps;
-    }
-    g_last_cfg_h[0] = bm; g_last_cfg_h[1] = split; g_last_cfg_h[2] += (bm == 256 && tail > 0) ? 1 : 0; g_last_cfg_h[3] += (qkv && split == 1 && tail == 0) ? 1 : 0;
-    // bm code 16: the skinny kernel (M <= 80 rows, N % 16 == 0): chosen for every such shape unless a tile is forced; its own K split (a wave streams <= 8 K-steps)
-    static const int skinny_max = getenv("SDVAR_GEMM_SKINNY_MAX") ? atoi(getenv("SDVAR_GEMM_SKINNY_MAX")) : 80;          // A/B runs: 0 switches it off
-    if ((g_force_bm_h == 16 || (!g_force_bm_h && M <= skinny_max)) && M <= 80 && N % 16 == 0) {
-        const int nkt = K / HBK;
-        int sp = (nkt + 31) / 32;                            // 4 waves x 8 K-steps per workgroup (a 16-wave workgroup for K = 4096 is capped at 128 VGPRs and spills)
-        if (g_force_bm_h == 16 && g_force_split_h > sp) sp = g_force_split_h;
-        while (sp > 1 && (size_t)sp * M * N > wsf) --sp;
-        const int kps = (nkt + sp - 1) / sp;
-        // automatic choice: only where ONE workgroup streams the whole K (K <= 1024): with a split over workgroups (fc2, K = 4096) the slab path of the ring kernels is
-        // as fast or faster (M = 64: 13.5 against 14.9 us, profiles/r03_s_skinny_ab.log); a forced tile (tests) takes any K
-        if (kps <= 32 && (sp == 1 || (g_force_bm_h == 16 && N % 4 == 0))) {
-            sp = (nkt + kps - 1) / kps;
-            g_last_cfg_h[0] = 16; g_last_cfg_h[1] = sp;
-            if (trace) fprintf(stderr, "[gemm_f16x2] M=%d N=%d K=%d epi=%d -> skinny split=%d\n", M, N, K, epi, sp);
-            return launch_skinny<4>(a, epi, sp, stream);
-        }
-    }
-    if (bm == 16) bm = 32;
-    if (qkv && split == 1 && tail == 0) {
-        a.qk = *g_qkv_epi; a.split = 1; a.k_per_split = K / HBK;
-        *g_qkv_fused = 1;
-        if (bm == 768) return launch_h7_kernel<HEPI_QKV>(a, ((M + 255) / 256) * ((N + 191) / 192), stream);
-        if (bm == 512) return launch_h4_kernel<HEPI_QKV>(a, ((M + 255) / 256) * ((N + 255) / 256), stream);
-        if (bm == 256) return launch_h3_kernel<HEPI_QKV>(a, ((M + 255) / 256) * ((N + HBN - 1) / HBN), stream);
-        if (bm == 128) return launch_h2_kernel<HEPI_QKV>(a, ((M + 127) / 128) * ((N + HBN - 1) / HBN), stream);
-        if (bm == 64) return launch_small_any<64, HEPI_QKV>(a, ((M + 63) / 64) * ((N + HBN - 1) / HBN), stream);
-        return launch_small_any<32, HEPI_QKV>(a, ((M + 31) / 32) * ((N + HBN - 1) / HBN), stream);
-    }
-    if (bm == 768) return launch_h7(a, epi, split, stream);
-    if (bm == 512) return launch_h4(a, epi, split, stream);
-    if (bm == 256 && tail > 0) return launch_h3_hybrid(a, epi, tail, stream);
-    if (bm == 256) return launch_h3(a, epi, split, stream);
-    if (bm == 32) return launch_h<32>(a, epi, split, stream);
-    if (bm == 64) return launch_h<64>(a, epi, split, stream);
-    return launch_h<128>(a, epi, split, stream);
+    g_last_plan.plan = p; g_last_plan.tail_launches += p.tail > 0; g_last_plan.fused_launches += p.qkv_fused;
+    return launch_f16x2(a, epi, p, call, stream);
+}
+
+// X planes [2][K/32][M][32] (plane stride xps), W planes [2][K/32][N][32] of W * 2^S (plane stride wps), wsi -> 2^-S on the device (null: 1).
+// epi: 0 bias -> out fp32; 1 bias + GELU -> outp planes of (M, N) (plane stride ops); 2 gated residual -> out fp32.
+// defer: as gemm_bf16x3_nt (the slabs already carry the 2^-S factor).
+int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
+                  int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer,
+                  hipStream_t stream) {
+    return gemm_f16x2_run(X, xps, W, wps, wsi, bias, out, ldo, outp, ops, M, N, K, epi, res, ldres, gate, rows_per_gate, gate_stride, GemmCall{defer, nullptr, nullptr}, stream);
+}
+
+// The QKV launch of a transformer block: as gemm_f16x2_nt(epi 0, out = the (M, 3 H 64) fp32 qkv buffer, defer), but when the launch comes out UNSPLIT the
+// q, k and v are finished in the epilogue (QkvEpi) and *fused = 1: the caller runs no qk_norm_append at all.  Otherwise *fused = 0 and the
+// result is in `out` (or in the slabs, *defer > 0) as before.
+int gemm_f16x2_qkv(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, int M, int N, int K,
+                   const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int l, int H, int Lp, int pos0, int kv_fmt, int* defer, int* fused, hipStream_t stream) {
+    SDVAR_CHECK_ARG(fused && defer && q_out && k_cache && v_cache && l > 0 && H > 0 && N == 3 * H * 64 && M % l == 0, "gemm_f16x2_qkv: bad arguments (M=%d N=%d l=%d H=%d)", M, N, l, H);
+    *fused = 0;
+    const QkvEpi e{scale_mul, q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, l, H, Lp, pos0, kv_fmt};
+    const bool ok = variant(VAR_QKV_FUSE) && (kv_fmt == 3 || kv_fmt == 4) && (H * 64) % 128 == 0 && ((uintptr_t)q_out % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 && Lp % 8 == 0;
+    return gemm_f16x2_run(X, xps, W, wps, wsi, bias, out, ldo, nullptr, 0, M, N, K, HEPI_BIAS, nullptr, 0, nullptr, 1, 0, GemmCall{defer, ok ? &e : nullptr, fused}, stream);
 }
 
 }  // namespace sdvar

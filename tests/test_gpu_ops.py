@@ -1045,3 +1045,36 @@ def test_rowblk_default_gate_at_d16_width(dev):
     assert torch.isfinite(lg[:2 * B * 5 * tc.V]).all()
     assert got == [False, True, False, True], got
     tc.close(); torch.cuda.empty_cache()
+
+
+def test_gemm_plan_is_what_runs(dev):
+    """sdvar_debug_plan_gemm (the planner alone, tests/test_gemm_plan_host.py pins it without a GPU) against the launches: small shapes through sdvar_op_gemm_f16x2 /
+    sdvar_op_gemm_bf16x3, the automatic choice and every forced tile of the forced-tile tests above.  For f16x2, sdvar_debug_get_gemm_cfg must report exactly the
+    planned kernel code, K split, hybrid tail and QKV fusion; in both modes the result matches the fp64 product to the bar of test_gemm_f16x2_epilogues."""
+    lib = E.load_library()
+    plan = (C.c_int32 * 4)()
+    for (M, N, K) in [(16, 256, 256), (64, 384, 256), (144, 384, 128), (300, 512, 256), (520, 384, 128), (520, 512, 4096)]:
+        X, W, b = rnd(1, (M, K)), rnd(2, (N, K), 1 / math.sqrt(K)), rnd(3, (N,)).to(dev)
+        ref = X.double() @ W.double().t() + b.cpu().double()
+        bar = 2e-5 * max(1.0, ref.abs().max().item())
+        (Xh, _), (Wh, sc) = _planes_h(X, dev), _planes_h(W, dev, scaled=True)
+        Xb, Wb = _planes(X, dev), _planes(W, dev)
+        for mode, forces in ((2, [(0, 0)] + [(bm, 1) for bm in (16, 32, 64, 128, 256, 512, 768)]), (1, [(0, 0), (128, 1), (256, 1)])):
+            for force in forces:
+                out = torch.full((M, N), float("nan"), device=dev)
+                E._check(lib.sdvar_debug_set_gemm_cfg(*force))
+                try:
+                    E._check(lib.sdvar_debug_plan_gemm(mode, M, N, K, 4, plan))             # flag 4: the outputs below allow 16-byte accesses
+                    if mode == 2:
+                        E.last_gemm_cfg()                                                    # reset the launch counters
+                        E._check(lib.sdvar_op_gemm_f16x2(_p(Xh), M * K, _p(Wh), N * K, _p(sc), _p(b), _p(out), N, None, 0, M, N, K, 0, None, N, None, 1, 0, _st()))
+                        cfg = E.last_gemm_cfg()
+                        assert [cfg["bm"], cfg["split"], cfg["tail_launches"], cfg["fused_qkv_launches"]] == [plan[0], plan[1], int(plan[2] > 0), plan[3]], (M, N, K, force, cfg, list(plan))
+                    else:
+                        E._check(lib.sdvar_op_gemm_bf16x3(_p(Xb), M * K, _p(Wb), N * K, _p(b), _p(out), N, None, 0, M, N, K, 0, None, N, None, 1, 0, _st()))
+                    if force[0] and not (force[0] == 16 and (M > 80 or mode != 2)):
+                        assert plan[0] == force[0], (M, N, K, force, list(plan))             # a forced tile is the planned one
+                finally:
+                    E._check(lib.sdvar_debug_set_gemm_cfg(0, 0))
+                err = (out.cpu().double() - ref).abs().max().item()
+                assert err <= bar, (mode, M, N, K, force, list(plan), err)
