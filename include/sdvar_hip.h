@@ -254,6 +254,20 @@ int sdvar_op_attention(const float* q, const void* k_cache, const void* v_cache,
                        int32_t plane_format, int32_t R, int32_t H, int32_t l, int32_t Lmax, int32_t Ktot, int32_t n_stages, const int32_t* qbeg /*host*/,
                        const int32_t* vis /*host*/, void* stream);
 int sdvar_op_noise_fill(float* q, int32_t B, int32_t l, int32_t V, uint64_t seed, uint32_t draw, uint32_t image_offset, void* stream);
+/* The reference's operator slots slow_attn / memory_efficient_attention (models/basic_var.py:27-30, called at :113-117; sdvar_amd/seam.py is the Python side):
+ * out = softmax(scale q k^T + bias) v, fp32, head_dim = 64 (anything else is an argument error).  q / out hold Lq tokens, k / v hold Lk tokens, any Lq, Lk >= 1.
+ * strides (host, 12 x int64, in ELEMENTS): (batch, head, token) of q, then k, v, out; the channel stride is 1.  Token rows must be 16-byte aligned: every pointer
+ * % 16 == 0 and every stride a non-negative multiple of 4.  (B, H, L, 64) tensors, permuted views of a (B, L, 3, H, 64) buffer and (B, L, H, 64) tensors are all strides.
+ * bias_kind 0: no bias (bias = NULL); 1: fp32 additive, finite or -inf; 2: uint8 keep-mask (0 = masked, SDPA's bool mask).  bias_strides (host, 3 x int64, elements):
+ * (batch, head, query row), 0 = broadcast; the key stride is 1, no alignment rule (rows of a sliced mask work in place).
+ * skip_map (device, may be NULL): what sdvar_op_sdpa_skip_map wrote for THIS bias, Lq and Lk; marked tiles cost no K/V traffic and no matrix work.
+ * A query row with every key masked has no defined value (NaN here); it does not fault and does not disturb other rows.  No host synchronisation. */
+int sdvar_op_sdpa(const float* q, const float* k, const float* v, float* out, const int64_t* strides /*host*/, const void* bias, int32_t bias_kind,
+                  const int64_t* bias_strides /*host*/, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
+/* skip_map (device, ceil(Lq / 128) * ceil(Lk / 64) bytes): byte (qb, kt) = 1 when bias[bb][hh][128 qb ..][64 kt ..] is masked (-inf / 0) for EVERY bb < Bb, hh < Hb -
+ * Bb, Hb = the bias's own batch and head extents (1 where it broadcasts), so a tile that one head needs is never skipped for another. */
+int sdvar_op_sdpa_skip_map(const void* bias, int32_t bias_kind, const int64_t* bias_strides /*host*/, int32_t Bb, int32_t Hb, int32_t Lq, int32_t Lk, uint8_t* skip_map,
+                           void* stream);
 
 /* conv weight (Cout, Cin, kh, kw) with kh*kw = taps (1 or 9) -> K-blocked planes [3][taps*Cin/32][Cout][32], k = tap*Cin + cin */
 int sdvar_op_conv_weight_planes(const float* w, uint16_t* planes, int32_t Cout, int32_t Cin, int32_t taps, uint64_t plane_stride, int32_t plane_format /* 3 | 2 */,

@@ -43,6 +43,9 @@ int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
 int attention_masked(const float* q, const void* kc, const void* vc, int fmt, const float* bias, float* out, uint16_t* outp, size_t ops, int pfmt, int R, int H, int l,
                      int Lmax, int Ktot, hipStream_t stream);
+int attention_sdpa(const float* q, const float* k, const float* v, float* out, const long long* strides, const void* bias, int kind, const long long* bs,
+                   const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, hipStream_t stream);
+int sdpa_skip_map(const void* bias, int kind, const long long* bs, int Bb, int Hb, int Lq, int Lk, uint8_t* map, hipStream_t stream);
 int split_planes(const float* x, uint16_t* planes, int rows, int cols, size_t plane_stride, hipStream_t stream);
 int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                   int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -885,6 +888,16 @@ int sdvar_op_attention(const float* q, const void* kc, const void* vc, int32_t k
 }
 int sdvar_op_noise_fill(float* q, int32_t B, int32_t l, int32_t V, uint64_t seed, uint32_t draw, uint32_t image_offset, void* stream) {
     return noise_fill(q, B, l, V, seed, draw, image_offset, (hipStream_t)stream);
+}
+// the reference's slow_attn / memory_efficient_attention slots (models/basic_var.py:27-30, 113-117): csrc/attention_sdpa.hip
+int sdvar_op_sdpa(const float* q, const float* k, const float* v, float* out, const int64_t* strides, const void* bias, int32_t bias_kind, const int64_t* bias_strides,
+                  const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "stride arrays are passed through");
+    return attention_sdpa(q, k, v, out, reinterpret_cast<const long long*>(strides), bias, bias_kind, reinterpret_cast<const long long*>(bias_strides), skip_map, B, H, Lq, Lk,
+                          head_dim, (float)scale, (hipStream_t)stream);
+}
+int sdvar_op_sdpa_skip_map(const void* bias, int32_t bias_kind, const int64_t* bias_strides, int32_t Bb, int32_t Hb, int32_t Lq, int32_t Lk, uint8_t* skip_map, void* stream) {
+    return sdpa_skip_map(bias, bias_kind, reinterpret_cast<const long long*>(bias_strides), Bb, Hb, Lq, Lk, skip_map, (hipStream_t)stream);
 }
 
 int sdvar_debug_set_gemm_cfg(int32_t bm, int32_t split) {

@@ -1,0 +1,231 @@
+"""Drop-in HIP operators for the reference's module-level operator slots (models/basic_var.py:15-30).
+
+The reference calls three module globals on its hot path: `slow_attn` / `memory_efficient_attention` (basic_var.py:113-117) and
+`fused_mlp_func` (basic_var.py:46-50, captured per FFN at :36).  This module provides all three on the library's kernels, for a
+maintainer of the reference who wants the kernels without adopting the sampling loop:
+
+    from sdvar_amd import seam
+    import models.basic_var as basic_var
+    seam.install(basic_var, model)          # slots + the fused_mlp_func every FFN captured at construction
+
+Inference only, fp32 only: no backward, no dropout, head dim 64.  Anything else raises SdvarError - there is no fall-back to torch.
+Torch is used for device memory and the current stream only; bool masks go to the kernel as bytes.
+
+Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
+reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
+read in place; a tensor that does not is copied once with .contiguous().
+A query row whose keys are ALL masked has no defined value (NaN); other rows are unaffected.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from collections import OrderedDict
+from typing import Optional
+
+import torch
+
+from . import engine as E
+from .engine import SdvarError
+
+__all__ = ["configure", "slow_attn", "memory_efficient_attention", "fused_mlp_func", "install", "clear_caches"]
+
+_gemm_mode = E.DEFAULT_GEMM_MODE
+# (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
+# a key can never describe two different masks.  Small on purpose: a model has a handful of masks (teacher forcing: one; the hand-off sampler: five).
+_SKIP_MAPS: "OrderedDict[tuple, tuple]" = OrderedDict()
+_SKIP_MAPS_MAX = 8
+# (mode, data_ptr, _version, shape) -> (weight, planes, scale): GEMM operand planes of a weight (none in mode f32).  A d30 model has 60 FFN weights.
+_WEIGHT_PLANES: "OrderedDict[tuple, tuple]" = OrderedDict()
+_WEIGHT_PLANES_MAX = 256
+
+
+def configure(gemm_mode: Optional[str] = None) -> None:
+    """GEMM arithmetic of fused_mlp_func: one of engine.GEMM_MODES (default: the library's, engine.DEFAULT_GEMM_MODE).  'f16x2' saturates activations
+    (x and the GELU output) at +-65504 and loses relative precision below ~1e-3; 'bf16x3' and 'f32' have no range limit."""
+    global _gemm_mode
+    if gemm_mode is not None:
+        if gemm_mode not in E.GEMM_MODES:
+            raise SdvarError(f"seam.configure: gemm_mode {gemm_mode!r} is not one of {E.GEMM_MODES}")
+        _gemm_mode = gemm_mode
+
+
+def clear_caches() -> None:
+    _SKIP_MAPS.clear()
+    _WEIGHT_PLANES.clear()
+
+
+def _p(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _check_operand(name: str, t: torch.Tensor, who: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise SdvarError(f"{who}: {name} is not a tensor")
+    if not t.is_cuda:
+        raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+    if t.dtype != torch.float32:
+        raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
+    if t.requires_grad and torch.is_grad_enabled():
+        raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
+
+
+def _rows_aligned(t: torch.Tensor) -> bool:
+    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 4 == 0 and s >= 0 for s in t.stride()[:-1])
+
+
+def _skip_map(mask: torch.Tensor, kind: int, bstr, Bb: int, Hb: int, Lq: int, Lk: int) -> torch.Tensor:
+    key = (mask.data_ptr(), mask._version, tuple(mask.shape), tuple(mask.stride()), mask.dtype, Lq)       # Lq: a (.., 1, Lk) mask broadcasts over any number of rows
+    hit = _SKIP_MAPS.get(key)
+    if hit is not None:
+        _SKIP_MAPS.move_to_end(key)
+        return hit[1]
+    smap = torch.empty(((Lq + 127) // 128) * ((Lk + 63) // 64), dtype=torch.uint8, device=mask.device)
+    E._check(E.load_library().sdvar_op_sdpa_skip_map(_p(mask), kind, bstr, Bb, Hb, Lq, Lk, _p(smap), E._stream()))
+    _SKIP_MAPS[key] = (mask, smap)
+    while len(_SKIP_MAPS) > _SKIP_MAPS_MAX:
+        _SKIP_MAPS.popitem(last=False)
+    return smap
+
+
+def _sdpa(who: str, q, k, v, idx, scale: float, mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
+    for name, t in (("query", q), ("key", k), ("value", v)):
+        _check_operand(name, t, who)
+        if t.dim() != 4:
+            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
+        if t.shape[-1] != 64:
+            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+    ib, ih, it = idx
+    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
+    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or Lq < 1 or Lk < 1:
+        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
+    if q.device != k.device or q.device != v.device:
+        raise SdvarError(f"{who}: operands live on different devices")
+    q, k, v = (t if _rows_aligned(t) else t.contiguous() for t in (q, k, v))
+    out = torch.empty((B, Lq, H, 64), dtype=torch.float32, device=q.device)
+    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
+    kind, bstr, smap = 0, None, None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+            raise SdvarError(f"{who}: the mask is a CPU tensor (or no tensor)")
+        if mask.dtype == torch.bool:
+            kind, mask = 2, mask.view(torch.uint8)
+        elif mask.dtype == torch.float32:
+            kind = 1
+        else:
+            raise SdvarError(f"{who}: the mask is {mask.dtype}; float32 (additive) or bool (keep) only")
+        if mask.dim() > 4:
+            raise SdvarError(f"{who}: the mask has {mask.dim()} dims")
+        while mask.dim() < 4:
+            mask = mask.unsqueeze(0)
+        mb, mh, mq, mk = mask.shape
+        if mb not in (1, B) or mh not in (1, H) or mq not in (1, Lq) or mk != Lk:
+            raise SdvarError(f"{who}: a mask of shape {tuple(mask.shape)} does not broadcast to {(B, H, Lq, Lk)} (the key dimension must be materialised)")
+        if mask.stride(3) != 1 and Lk > 1:
+            mask = mask.contiguous()
+        sb, sh, sr = (0 if n == 1 else s for n, s in zip(mask.shape[:3], mask.stride()[:3]))
+        bstr = (C.c_int64 * 3)(sb, sh, sr)
+        # the skip map looks at the bias's OWN batch / head slices (one where it broadcasts or is expanded), every one of the Lq rows
+        smap = _skip_map(mask, kind, bstr, 1 if sb == 0 else B, 1 if sh == 0 else H, Lq, Lk)
+    E._check(E.load_library().sdvar_op_sdpa(_p(q), _p(k), _p(v), _p(out), strides, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale), E._stream()))
+    return out
+
+
+def slow_attn(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
+    """The `slow_attn` slot (basic_var.py:25-30, called at :117): softmax(scale q k^T + attn_mask) v.  query (B, H, Lq, 64), key / value (B, H, Lk, 64) fp32 on the
+    GPU, any strides meeting the alignment rule (read in place), else one .contiguous() copy.  attn_mask: float32 additive or bool keep-mask, broadcastable to
+    (B, H, Lq, Lk) with the key dimension materialised; views (mask[:, :, :ed, :ed]) are read in place.  Returns a (B, H, Lq, 64) VIEW of a (B, Lq, H, 64)
+    buffer, so the caller's .transpose(1, 2).reshape(B, L, C) is free."""
+    if dropout_p and dropout_p > 0:
+        raise SdvarError("slow_attn: dropout_p > 0 is not supported (inference only)")
+    return _sdpa("slow_attn", query, key, value, (0, 1, 2), scale, attn_mask).permute(0, 2, 1, 3)
+
+
+def memory_efficient_attention(q, k, v, attn_bias=None, p: float = 0.0, scale: Optional[float] = None):
+    """The xformers slot (basic_var.py:21, called at :115): q (B, Lq, H, 64), k / v (B, Lk, H, 64), attn_bias as for slow_attn ((B, H, Lq, Lk) or broadcastable);
+    returns (B, Lq, H, 64).  The same kernel as slow_attn with other strides."""
+    if p and p > 0:
+        raise SdvarError("memory_efficient_attention: p > 0 (dropout) is not supported (inference only)")
+    return _sdpa("memory_efficient_attention", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
+
+
+def _weight_planes(w: torch.Tensor, mode: str):
+    key = (mode, w.data_ptr(), w._version, tuple(w.shape))
+    hit = _WEIGHT_PLANES.get(key)
+    if hit is not None:
+        _WEIGHT_PLANES.move_to_end(key)
+        return hit[1], hit[2]
+    lib = E.load_library()
+    N, K = w.shape
+    wc = w.detach().contiguous()
+    if mode == "f16x2":
+        planes, sc = torch.empty(2, N * K, dtype=torch.int16, device=w.device), torch.zeros(4, dtype=torch.float32, device=w.device)
+        E._check(lib.sdvar_op_split_planes_f16(_p(wc), _p(planes), N, K, N * K, _p(sc), E._stream()))
+    else:
+        planes, sc = torch.empty(3, N * K, dtype=torch.int16, device=w.device), None
+        E._check(lib.sdvar_op_split_planes(_p(wc), _p(planes), N, K, N * K, E._stream()))
+    _WEIGHT_PLANES[key] = (w, planes, sc)
+    while len(_WEIGHT_PLANES) > _WEIGHT_PLANES_MAX:
+        _WEIGHT_PLANES.popitem(last=False)
+    return planes, sc
+
+
+def fused_mlp_func(x, weight1, weight2, bias1=None, bias2=None, activation: str = "gelu_approx", save_pre_act: bool = False, return_residual: bool = False,
+                   checkpoint_lvl: int = 0, heuristic=0, process_group=None):
+    """The `fused_mlp_func` slot (flash_attn.ops.fused_dense signature; basic_var.py:46-50): fc2(gelu_tanh(fc1(x))), x (..., C) fp32 on the GPU, weight1 (hidden, C),
+    weight2 (out, hidden).  Two launches of the operator GEMMs of the configured mode (seam.configure): fc1 with the GELU epilogue writing the operand planes of fc2
+    directly.  C and hidden must be multiples of 32.  save_pre_act / checkpoint_lvl / heuristic only matter to a backward and are ignored."""
+    who = "fused_mlp_func"
+    if activation != "gelu_approx":
+        raise SdvarError(f"{who}: activation {activation!r}; only 'gelu_approx' (tanh GELU) is built")
+    if return_residual:
+        raise SdvarError(f"{who}: return_residual=True is not supported")
+    if process_group is not None:
+        raise SdvarError(f"{who}: a process group (tensor-parallel MLP) is not supported")
+    for name, t in (("x", x), ("weight1", weight1), ("weight2", weight2)) + tuple((n, b) for n, b in (("bias1", bias1), ("bias2", bias2)) if b is not None):
+        _check_operand(name, t, who)
+    if weight1.dim() != 2 or weight2.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight1.shape[1] or weight2.shape[1] != weight1.shape[0]:
+        raise SdvarError(f"{who}: shapes do not chain: x {tuple(x.shape)}, weight1 {tuple(weight1.shape)}, weight2 {tuple(weight2.shape)}")
+    Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
+    if Cin % 32 or hid % 32:
+        raise SdvarError(f"{who}: in_features {Cin} and hidden_features {hid} must be multiples of 32")
+    lib, st, mode = E.load_library(), E._stream(), _gemm_mode
+    xr = x.detach().reshape(-1, Cin).contiguous()
+    M = xr.shape[0]
+    out = torch.empty(tuple(x.shape[:-1]) + (Cout,), dtype=torch.float32, device=x.device)
+    if M == 0:
+        return out
+    b1 = torch.zeros(hid, dtype=torch.float32, device=x.device) if bias1 is None else bias1.detach().contiguous()
+    b2 = torch.zeros(Cout, dtype=torch.float32, device=x.device) if bias2 is None else bias2.detach().contiguous()
+    if mode == "f32":
+        w1, w2 = weight1.detach().contiguous(), weight2.detach().contiguous()
+        h = torch.empty(M, hid, dtype=torch.float32, device=x.device)
+        E._check(lib.sdvar_op_gemm(_p(xr), Cin, _p(w1), _p(b1), _p(h), hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
+        E._check(lib.sdvar_op_gemm(_p(h), hid, _p(w2), _p(b2), _p(out), Cout, M, Cout, hid, 0, None, 0, None, 1, 0, st))
+        return out
+    (w1p, s1), (w2p, s2) = _weight_planes(weight1, mode), _weight_planes(weight2, mode)
+    npl = 2 if mode == "f16x2" else 3
+    xp = torch.empty(npl, M * Cin, dtype=torch.int16, device=x.device)
+    hp = torch.empty(npl, M * hid, dtype=torch.int16, device=x.device)
+    if mode == "f16x2":
+        E._check(lib.sdvar_op_split_planes_f16(_p(xr), _p(xp), M, Cin, M * Cin, None, st))
+        E._check(lib.sdvar_op_gemm_f16x2(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(s1), _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
+        E._check(lib.sdvar_op_gemm_f16x2(_p(hp), M * hid, _p(w2p), Cout * hid, _p(s2), _p(b2), _p(out), Cout, None, 0, M, Cout, hid, 0, None, 0, None, 1, 0, st))
+    else:
+        E._check(lib.sdvar_op_split_planes(_p(xr), _p(xp), M, Cin, M * Cin, st))
+        E._check(lib.sdvar_op_gemm_bf16x3(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
+        E._check(lib.sdvar_op_gemm_bf16x3(_p(hp), M * hid, _p(w2p), Cout * hid, _p(b2), _p(out), Cout, None, 0, M, Cout, hid, 0, None, 0, None, 1, 0, st))
+    return out
+
+
+def install(module, model=None) -> None:
+    """Set the `slow_attn` and `fused_mlp_func` globals of a basic_var-like module; with a model, also every `ffn.fused_mlp_func` its FFN modules captured at
+    construction (basic_var.py:36).  `memory_efficient_attention` is left alone: setting it would not switch an existing model to it (using_xform is decided at
+    construction, basic_var.py:82); assign seam.memory_efficient_attention yourself before building the model if you want the BLHc route."""
+    module.slow_attn = slow_attn
+    module.fused_mlp_func = fused_mlp_func
+    if model is not None:
+        for m in model.modules():
+            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
+                m.fused_mlp_func = fused_mlp_func

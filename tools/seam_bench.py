@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Time the operator seam (sdvar_amd/seam.py) against what it replaces in the reference's slots, in ONE process on the same tensors.
+
+  slow_attn        vs torch's fp32 F.scaled_dot_product_attention     B 8, H 16, Lq = Lk = 680 under the ten-stage block-causal mask (teacher forcing)
+                                                                      the same shape without a mask (+ the library's older route: contiguous copies of
+                                                                      q, k, v and sdvar_op_attention on an fp32 cache)
+                                                                      B 16, H 16, 256 queries against 680 cached keys, no mask
+  fused_mlp_func   vs F.linear / tanh-GELU / F.linear                 C 1024 (hidden 4096), M = 680 * 8 and M = 64, every GEMM mode
+
+Every figure is the MEDIAN over --reps windows of --iters back-to-back calls, timed with device events; the candidates of one shape alternate window by window, so
+drift of the machine hits them alike.  min / max of the windows are printed beside the median.  The last line is one JSON object with every median (microseconds).
+python tools/seam_bench.py [--iters 20] [--reps 9]"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sdvar_amd import engine as E          # noqa: E402
+from sdvar_amd import seam                 # noqa: E402
+from sdvar_amd.ladder import LADDER_256    # noqa: E402
+
+
+def windows(fns, iters, reps):
+    """{name: callable} -> {name: (median, min, max)} in microseconds per call."""
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            e1.synchronize()
+            us[k].append(e0.elapsed_time(e1) * 1e3 / iters)
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in us.items()}
+
+
+def report(title, res, results, flops=None):
+    print(title)
+    for k, (med, lo, hi) in res.items():
+        extra = f"  {flops / med * 1e-6:7.1f} TFLOP/s (algorithmic)" if flops else ""
+        print(f"    {k:<34s} {med:9.1f} us  (min {lo:.1f}, max {hi:.1f}){extra}")
+        results[f"{title} | {k}"] = round(med, 2)
+
+
+def block_causal(patch_nums, dev):
+    d = torch.cat([torch.full((pn * pn,), i) for i, pn in enumerate(patch_nums)]).to(dev)
+    return torch.where(d[:, None] >= d[None, :], 0.0, float("-inf")).reshape(1, 1, len(d), len(d)).float().contiguous()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=9)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("seam_bench: no GPU (there is nothing to time on a CPU)")
+    torch.set_grad_enabled(False)
+    dev, lib, results = torch.device("cuda:0"), E.load_library(), {}
+    P = lambda t: C.c_void_p(t.data_ptr())
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    # ---- attention, teacher-forced shape: q, k, v are the reference's views of one (B, L, 3, H, 64) buffer (basic_var.py:93-99), attn_l2_norm scaling
+    B, H, L = 8, 16, sum(p * p for p in LADDER_256)
+    qkv = torch.randn(B, L, 3, H, 64, device=dev, generator=g)
+    qkv[:, :, 0] = F.normalize(qkv[:, :, 0], dim=-1) * 4
+    qkv[:, :, 1] = F.normalize(qkv[:, :, 1], dim=-1)
+    q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)
+    mask = block_causal(LADDER_256, dev)
+    flops = 4.0 * B * H * L * L * 64
+    diff = (seam.slow_attn(q, k, v, 1.0, attn_mask=mask) - F.scaled_dot_product_attention(q, k, v, attn_mask=mask, scale=1.0)).abs().max().item()
+    smap = next(iter(seam._SKIP_MAPS.values()))[1]
+    frac = 1.0 - smap.float().mean().item()
+    print(f"block-causal mask L = {L}: {frac * 100:.1f} % of the (128-query, 64-key) tiles are visited; {(mask == 0).float().mean().item() * 100:.1f} % of the elements are visible; "
+          f"max |seam - torch fp32| = {diff:.2e}")
+    rm = windows({"seam.slow_attn": lambda: seam.slow_attn(q, k, v, 1.0, attn_mask=mask),
+                  "torch SDPA fp32": lambda: F.scaled_dot_product_attention(q, k, v, attn_mask=mask, scale=1.0)}, a.iters, a.reps)
+    report(f"attention B{B} H{H} L{L} block-causal mask", rm, results, flops)
+
+    qb, vs, st = (C.c_int32 * 1)(0), (C.c_int32 * 1)(L), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    old_out = torch.empty(B, L, H * 64, device=dev)
+
+    def old_route():
+        qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+        E._check(lib.sdvar_op_attention(P(qc), P(kc), P(vc), 0, P(old_out), None, 0, 3, B, H, L, L, L, 1, qb, vs, st))
+    rn = windows({"seam.slow_attn": lambda: seam.slow_attn(q, k, v, 1.0),
+                  "torch SDPA fp32": lambda: F.scaled_dot_product_attention(q, k, v, scale=1.0),
+                  "copies + sdvar_op_attention fmt 0": old_route}, a.iters, a.reps)
+    report(f"attention B{B} H{H} L{L} no mask", rn, results, flops)
+    ratio = rm["seam.slow_attn"][0] / rn["seam.slow_attn"][0]
+    print(f"    masked / unmasked time of seam.slow_attn: {ratio:.3f}  (tiles visited: {frac:.3f})")
+    results["masked_to_unmasked_ratio"] = round(ratio, 4)
+    results["tiles_visited_fraction"] = round(frac, 4)
+
+    # ---- attention, cached call: 256 new queries (views of the qkv buffer) against 680 keys of the concatenated (B, H, L, 64) caches
+    B2, Lq = 16, 256
+    qkv2 = torch.randn(B2, Lq, 3, H, 64, device=dev, generator=g)
+    q2 = qkv2.permute(2, 0, 3, 1, 4)[0]
+    k2, v2 = torch.randn(B2, H, L, 64, device=dev, generator=g), torch.randn(B2, H, L, 64, device=dev, generator=g)
+    s2 = 0.25 / math.sqrt(64)
+    rc = windows({"seam.slow_attn": lambda: seam.slow_attn(q2, k2, v2, s2),
+                  "torch SDPA fp32": lambda: F.scaled_dot_product_attention(q2, k2, v2, scale=s2)}, a.iters, a.reps)
+    report(f"attention B{B2} H{H} Lq{Lq} Lk{L} no mask", rc, results, 4.0 * B2 * H * Lq * L * 64)
+
+    # ---- fused MLP
+    Cw, hid = 1024, 4096
+    w1, b1 = torch.randn(hid, Cw, device=dev, generator=g) / math.sqrt(Cw), torch.randn(hid, device=dev, generator=g)
+    w2, b2 = torch.randn(Cw, hid, device=dev, generator=g) / math.sqrt(hid), torch.randn(Cw, device=dev, generator=g)
+    for M in (L * 8, 64):
+        x = torch.randn(M, Cw, device=dev, generator=g)
+
+        def seam_mlp(mode):
+            def f():
+                seam.configure(gemm_mode=mode)
+                return seam.fused_mlp_func(x=x, weight1=w1, weight2=w2, bias1=b1, bias2=b2, activation="gelu_approx", save_pre_act=False, return_residual=False,
+                                           checkpoint_lvl=0, heuristic=0, process_group=None)
+            return f
+        fns = {f"seam.fused_mlp_func {m}": seam_mlp(m) for m in E.GEMM_MODES}
+        fns["torch linear/gelu/linear fp32"] = lambda: F.linear(F.gelu(F.linear(x, w1, b1), approximate="tanh"), w2, b2)
+        report(f"mlp M{M} C{Cw}", windows(fns, a.iters, a.reps), results, 4.0 * M * Cw * hid)
+    seam.configure(gemm_mode=E.DEFAULT_GEMM_MODE)
+    print(json.dumps(results))
+
+
+if __name__ == "__main__":
+    main()
