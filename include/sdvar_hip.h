@@ -139,6 +139,15 @@ int sdvar_quant_next_h(sdvar_quant_t* q, int32_t si, const float* h, float* f_ha
  * the final f_hat; f_hat_per_scale (S,B,cvae,HW,HW) or NULL: f_hat after every scale.  cvae = 32 only.  |e_v|^2 is computed once per bind,
  * on the stream of the first call. */
 int sdvar_quant_encode(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, void* stream);
+/* VectorQuantizer2.forward in eval mode (quant.py:52-104): the chain of sdvar_quant_encode (same kernels, same order: ids_out, f_hat_out and
+ * f_hat_per_scale are the same bits) plus the statistics of that method.  hits (S, V) int32: hits[s][v] = rows of scale s assigned to code v,
+ * idx_N.bincount(minlength=V) of quant.py:77 (integer atomics: order-independent).  sqerr (S) double: sqerr[s] = sum over the B*cvae*HW^2 elements of
+ * (f_hat_s - f)^2 with f_hat_s the accumulator after scale s - each difference in fp32, squared and summed in fp64 - so that
+ * F.mse_loss(f_hat, f) of quant.py:95 is sqerr[s] / numel.  One partial per workgroup, then a fixed-order pass; no floating-point atomics: repeated
+ * calls are bit-identical.  f_st (B,cvae,HW,HW) or NULL: the straight-through value of quant.py:98, fl(fl(f_hat - f) + f), which is what the reference
+ * hands to its decoder (not bit-equal to f_hat); written by the last scale's statistics pass.  f_st must not alias f or f_hat_out. */
+int sdvar_quant_encode_stats(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, int32_t* hits,
+                             double* sqerr, float* f_st, void* stream);
 /* more_smooth=True (var.py:206-208 + helpers.py:22-36): h (B,l,cvae) = softmax((masked * (1 + ratio) + g) / tau) @ codebook,
  * g = -log(E), E ~ Exp(1): e_noise (B,l,V) explicit, or NULL for the Philox stream at (seed, draw, image_offset).  `masked_logits`
  * (B,l,V) are the CFG logits as sample_with_top_k_top_p_ leaves them (helpers.py:10,15 mask in place): sdvar_cfg_sample's dbg_masked. */
@@ -169,6 +178,9 @@ int sdvar_vae_tensor_count(const sdvar_vae_desc* desc /*host*/);
 int sdvar_vae_bind(sdvar_vae_t* v, const float* const* tensors /*host*/, int32_t n_tensors, void* stream);
 /* vqvae.py:62-63: img (B,3,H,W) = clamp(decoder(post_quant_conv(f_hat (B,Cvae,h,w))), -1, 1), H = h << (n_mult-1) */
 int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream);
+/* vqvae.py:59 (VQVAE.forward): img = decoder(post_quant_conv(f_hat)) WITHOUT the clamp - the launches of sdvar_vae_decode with the clamp compiled
+ * out of the last kernel, so clamp(raw, -1, 1) is sdvar_vae_decode's image bit for bit. */
+int sdvar_vae_decode_raw(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream);
 
 /* ---- VQVAE encoder: image -> f = quant_conv(encoder(img)) (models/vqvae.py:65-67, models/basic_vae.py:99-161) ------------- */
 /* The decoder's descriptor: images are latent_hw << (n_mult-1) pixels square (256^2 -> latent 16^2, 512^2 -> 32^2), any B <= max_batch. */
@@ -220,6 +232,12 @@ int sdvar_cfg_combine(const float* logits, int32_t B, int32_t lsum, int32_t V, i
  * 16-byte aligned.  Uses a per-host-thread scratch of 4 doubles per 4 tokens (grown on demand). */
 int sdvar_xent_stats(const float* logits, const int64_t* targets, int32_t B, int32_t L, int32_t V, int32_t tail, float* nll_out, int64_t* argmax_out,
                      double* sums, int32_t accumulate, void* stream);
+/* Reconstruction error of a validation batch (the L1 / L2 terms of the VAE objective on VQVAE.forward's output, vqvae.py:56-59): over the n fp32
+ * elements of a and b, sums (2 doubles) = {sum |a - b|, sum (a - b)^2}, overwritten or (accumulate != 0) added to.  Each difference in fp32, |.| and the
+ * square summed in fp64: per-workgroup partials, then one workgroup adds them in a fixed order (no atomics: repeated calls are bit-identical).
+ * 16-byte loads when a and b are 16-byte aligned.  Uses a scratch of 2048 doubles per (host thread, device), on the device that is current at the call:
+ * calls of one host thread on one device share it and must be on one stream, or ordered by the caller. */
+int sdvar_img_err_stats(const float* a, const float* b, int64_t n, double* sums, int32_t accumulate, void* stream);
 
 /* ---- single operators (kernel-level parity tests and micro-benchmarks) ---------------------------------------------- */
 /* out[M,N] = epi(X[M,K] W[N,K]^T + bias); epi 0 bias, 1 bias+GELU(tanh), 2 res + (.)*gate[row / rows_per_gate] */

@@ -67,6 +67,11 @@ int quant_code_norms(const float* codebook, float* e2, int V, int Cv, hipStream_
 int quant_nearest(const float* z, int N, int P, const float* codebook, const float* e2, int V, int Cv, long long* ids, int ids_stride, hipStream_t stream);
 int quant_encode_stage(float* f_rest, float* f_hat, float* z, float* up_scratch, const float* codebook, const float* e2, const float* Wdn_si, const float* Wup_si,
                        const float* phi_w, const float* phi_b, long long* ids, int ids_stride, int B, int pn, int HW, int V, int Cv, int last, hipStream_t stream);
+int diff_stats_blocks(size_t n);
+int diff_stats_partials(const float* a, const float* b, size_t n, float* st, double* part, hipStream_t stream);
+int diff_stats_sum(const double* part, int nblk, int groups, size_t group_stride, int comp0, int ncomp, double* out, int accumulate, hipStream_t stream);
+int img_err_stats(const float* a, const float* b, size_t n, double* sums, int accumulate, hipStream_t stream);
+int quant_hits(const long long* ids, int B, int L, int S, const int* pn, int V, int* hits, hipStream_t stream);
 int quant_next(const long long* ids, int ids_stride, const float* hvec, const float* codebook, const float* Wup, const float* phi_w, const float* phi_b, const float* Wdn,
                float* up_scratch, const float* f_in, float* f_hat, float* nxt, int B, int pn, int pn_next, int HW, int Cv, int last, hipStream_t stream);
 
@@ -176,6 +181,8 @@ struct sdvar_quant {
     float* up_scratch;
     float* Wenc0;        // encoding: area table HW -> pn_0 (scale s >= 1 uses Wdn[s - 1]: HW -> pn_s)
     float *e2, *f_rest, *zrows;          // encoding: |e_v|^2, the residual (B,cvae,HW,HW), the rows of one scale's z
+    double* stat_part;   // encode_stats: per scale the workgroup partials {sum |d|, sum d^2} of f_hat_s - f (S rows of stat_stride doubles)
+    size_t stat_stride;
     bool e2_ready;
     const float* codebook;
     const float* phi_w[SDVAR_MAX_STAGES];
@@ -709,7 +716,7 @@ int sdvar_quant_create(int32_t S, const int32_t* patch_nums, int32_t cvae, int32
         }
     }
     SDVAR_TRY(dmalloc(&q->up_scratch, (size_t)max_batch * cvae * q->HW * q->HW));
-    q->Wenc0 = nullptr; q->e2 = q->f_rest = q->zrows = nullptr; q->e2_ready = false;
+    q->Wenc0 = nullptr; q->e2 = q->f_rest = q->zrows = nullptr; q->stat_part = nullptr; q->e2_ready = false;
     if (S > 1) {
         const int HW = q->HW, p0 = q->pn[0];
         std::vector<float> t((size_t)p0 * HW, 0.f);
@@ -723,6 +730,8 @@ int sdvar_quant_create(int32_t S, const int32_t* patch_nums, int32_t cvae, int32
     SDVAR_TRY(dmalloc(&q->e2, (size_t)vocab));
     SDVAR_TRY(dmalloc(&q->f_rest, (size_t)max_batch * cvae * q->HW * q->HW));
     SDVAR_TRY(dmalloc(&q->zrows, (size_t)max_batch * cvae * q->HW * q->HW));
+    q->stat_stride = 2 * (size_t)diff_stats_blocks((size_t)max_batch * cvae * q->HW * q->HW);
+    SDVAR_TRY(dmalloc(&q->stat_part, (size_t)S * q->stat_stride));
     *out = q;
     return SDVAR_OK;
 }
@@ -733,6 +742,7 @@ int sdvar_quant_destroy(sdvar_quant_t* q) {
     if (q->up_scratch) (void)hipFree(q->up_scratch);
     float* enc[] = {q->Wenc0, q->e2, q->f_rest, q->zrows};
     for (float* p : enc) if (p) (void)hipFree(p);
+    if (q->stat_part) (void)hipFree(q->stat_part);
     delete q;
     return SDVAR_OK;
 }
@@ -768,11 +778,14 @@ int sdvar_quant_next_h(sdvar_quant_t* q, int32_t si, const float* h, float* f_ha
     return quant_next_impl(q, si, nullptr, 0, h, nullptr, f_hat, nxt, B, stream);
 }
 
-int sdvar_quant_encode(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, void* stream) {
+// sdvar_quant_encode, and with hits / sqerr / f_st the statistics of VectorQuantizer2.forward behind the same launches (sdvar_quant_encode_stats)
+static int quant_encode_impl(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, int32_t* hits, double* sqerr,
+                             float* f_st, void* stream) {
     SDVAR_CHECK_ARG(q && q->bound, "quant_encode: quantizer not bound");
     SDVAR_CHECK_ARG(f && ids_out && f_hat_out, "quant_encode: null operand");
     SDVAR_CHECK_ARG(B >= 1 && B <= q->maxB, "quant_encode: batch %d exceeds max_batch %d", B, q->maxB);
     SDVAR_CHECK_ARG(q->Cv == 32, "quant_encode: Cvae %d (32 only)", q->Cv);
+    SDVAR_CHECK_ARG(!f_st || (sqerr && f_st != f && f_st != f_hat_out), "quant_encode_stats: f_st needs sqerr and a buffer of its own");
     hipStream_t s = (hipStream_t)stream;
     if (!q->e2_ready) { SDVAR_TRY(quant_code_norms(q->codebook, q->e2, q->V, q->Cv, s)); q->e2_ready = true; }     // once per bind, on the caller's stream
     const size_t n = (size_t)B * q->Cv * q->HW * q->HW;
@@ -788,9 +801,28 @@ int sdvar_quant_encode(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids
         SDVAR_TRY(quant_encode_stage(q->f_rest, f_hat_out, q->zrows, q->up_scratch, q->codebook, q->e2, wdn, q->Wup[si], q->phi_w[k], q->phi_b[k],
                                      (long long*)ids_out + off, L, B, q->pn[si], q->HW, q->V, q->Cv, last, s));
         if (f_hat_per_scale) SDVAR_HIP(hipMemcpyAsync(f_hat_per_scale + (size_t)si * n, f_hat_out, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        // quant.py:95 against the ORIGINAL f (f_rest is accumulated on its own and is not bit-equal to f - f_hat); the last scale's pass also writes quant.py:98
+        if (sqerr) SDVAR_TRY(diff_stats_partials(f_hat_out, f, n, last ? f_st : nullptr, q->stat_part + (size_t)si * q->stat_stride, s));
         off += q->pn[si] * q->pn[si];
     }
+    if (sqerr) SDVAR_TRY(diff_stats_sum(q->stat_part, diff_stats_blocks(n), q->S, q->stat_stride, 1, 1, sqerr, 0, s));
+    if (hits) SDVAR_TRY(quant_hits((const long long*)ids_out, B, L, q->S, q->pn, q->V, hits, s));
     return SDVAR_OK;
+}
+
+int sdvar_quant_encode(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, void* stream) {
+    return quant_encode_impl(q, f, B, ids_out, f_hat_out, f_hat_per_scale, nullptr, nullptr, nullptr, stream);
+}
+
+int sdvar_quant_encode_stats(sdvar_quant_t* q, const float* f, int32_t B, int64_t* ids_out, float* f_hat_out, float* f_hat_per_scale, int32_t* hits, double* sqerr,
+                             float* f_st, void* stream) {
+    SDVAR_CHECK_ARG(hits && sqerr, "quant_encode_stats: null hits or sqerr");
+    return quant_encode_impl(q, f, B, ids_out, f_hat_out, f_hat_per_scale, hits, sqerr, f_st, stream);
+}
+
+int sdvar_img_err_stats(const float* a, const float* b, int64_t n, double* sums, int32_t accumulate, void* stream) {
+    SDVAR_CHECK_ARG(n >= 1, "img_err_stats: n = %lld", (long long)n);
+    return img_err_stats(a, b, (size_t)n, sums, accumulate, (hipStream_t)stream);
 }
 
 int sdvar_op_quant_nearest(const float* z, int32_t N, const float* codebook, int32_t V, int32_t cvae, float* e2, int64_t* ids, void* stream) {

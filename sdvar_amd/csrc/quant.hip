@@ -321,4 +321,122 @@ int quant_encode_stage(float* f_rest, float* f_hat, float* z, float* up_scratch,
     return SDVAR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------- statistics (VectorQuantizer2.forward, quant.py:77, 95, 98)
+// The numbers the reference's forward() reports besides f_hat, and the image error of a reconstruction: sums over a pair of equally shaped fp32 tensors.
+//     d        = a - b in fp32 (the tensor F.mse_loss squares)
+//     part     {sum |d|, sum d^2} of one workgroup, in fp64: a thread adds its 16-byte chunks i, i + grid, ... in that order, the 64 lanes of a wave are
+//              added by a butterfly (wave_sum_d), the 4 waves through LDS in wave order -> one partial per workgroup
+//     sums     diff_stats_sum_kernel: thread t adds the partials t, t + 256, ... and a fixed tree adds the 256 threads.  The grid is a function of n alone
+//              and nothing is an atomic, so two calls give the same bits.
+//     st       (optional) d + b: the straight-through f_hat of quant.py:98, (f_hat - f) + f, from the values this pass has in registers anyway
+// HBM/L2-bound: 8 bytes read (+ 4 written) per element.
+constexpr int DS_MAX_BLOCKS = 1024;                    // 4 workgroups per CU on 256 CUs; beyond that a thread loops
+
+__global__ __launch_bounds__(256) void diff_stats_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n4, size_t n, float* __restrict__ st,
+                                                         double* __restrict__ part) {
+    __shared__ double red[4][2];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const size_t stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    double s1 = 0.0, s2 = 0.0;
+    for (size_t i = t0; i < n4; i += stride) {
+        const f32x4 va = reinterpret_cast<const f32x4*>(a)[i], vb = reinterpret_cast<const f32x4*>(b)[i];
+        const f32x4 d = va - vb;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { s1 += (double)fabsf(d[k]); s2 += (double)d[k] * (double)d[k]; }
+        if (st) reinterpret_cast<f32x4*>(st)[i] = d + vb;
+    }
+    for (size_t i = 4 * n4 + t0; i < n; i += stride) {           // the elements past the last whole chunk (all of them when a pointer is not 16-byte aligned)
+        const float vb = b[i], d = a[i] - vb;
+        s1 += (double)fabsf(d); s2 += (double)d * (double)d;
+        if (st) st[i] = d + vb;
+    }
+    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+    if (lane == 0) { red[w][0] = s1; red[w][1] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2) part[(size_t)blockIdx.x * 2 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// workgroup g: out[g ncomp + k] (+)= sum over the nblk partial rows of part[g group_stride + 2 i + comp0 + k], k < ncomp <= 2, in a fixed order
+__global__ __launch_bounds__(256) void diff_stats_sum_kernel(const double* __restrict__ part, int nblk, size_t group_stride, int comp0, int ncomp, double* __restrict__ out,
+                                                             int accumulate) {
+    __shared__ double red[2][256];
+    const double* p = part + (size_t)blockIdx.x * group_stride;
+    double acc[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < nblk; i += 256)
+        for (int k = 0; k < ncomp; ++k) acc[k] += p[(size_t)i * 2 + comp0 + k];
+    red[0][threadIdx.x] = acc[0]; red[1][threadIdx.x] = acc[1];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) { red[0][threadIdx.x] += red[0][threadIdx.x + h]; red[1][threadIdx.x] += red[1][threadIdx.x + h]; }
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < ncomp) {
+        double* o = out + (size_t)blockIdx.x * ncomp + threadIdx.x;
+        *o = (accumulate ? *o : 0.0) + red[threadIdx.x][0];
+    }
+}
+
+int diff_stats_blocks(size_t n) {
+    const size_t nb = (n / 4 + 255) / 256;
+    return (int)(nb < 1 ? 1 : (nb > (size_t)DS_MAX_BLOCKS ? (size_t)DS_MAX_BLOCKS : nb));
+}
+
+// part: 2 * diff_stats_blocks(n) doubles
+int diff_stats_partials(const float* a, const float* b, size_t n, float* st, double* part, hipStream_t stream) {
+    SDVAR_CHECK_ARG(a && b && part && n >= 1, "diff_stats: null operand or n = 0");
+    const bool vec = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)st) & 15) == 0;
+    hipLaunchKernelGGL(diff_stats_kernel, dim3(diff_stats_blocks(n)), dim3(256), 0, stream, a, b, vec ? n / 4 : (size_t)0, n, st, part);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+int diff_stats_sum(const double* part, int nblk, int groups, size_t group_stride, int comp0, int ncomp, double* out, int accumulate, hipStream_t stream) {
+    SDVAR_CHECK_ARG(part && out && nblk >= 1 && groups >= 1 && comp0 >= 0 && ncomp >= 1 && comp0 + ncomp <= 2, "diff_stats_sum: bad arguments");
+    hipLaunchKernelGGL(diff_stats_sum_kernel, dim3(groups), dim3(256), 0, stream, part, nblk, group_stride, comp0, ncomp, out, accumulate);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// The partials of img_err_stats: one buffer per (host thread, device), allocated on the device that is current at the call and kept for the thread's life
+// (sdvar_hip.h threading contract; calls of one thread on one device share it, so they must be on one stream or ordered by the caller).
+constexpr int DS_MAX_DEVICES = 64;
+static thread_local double* g_ds_part[DS_MAX_DEVICES] = {};
+
+int img_err_stats(const float* a, const float* b, size_t n, double* sums, int accumulate, hipStream_t stream) {
+    SDVAR_CHECK_ARG(a && b && sums && n >= 1, "img_err_stats: null operand or n = 0");
+    int dev = 0;
+    SDVAR_HIP(hipGetDevice(&dev));
+    SDVAR_CHECK_ARG(dev >= 0 && dev < DS_MAX_DEVICES, "img_err_stats: device %d", dev);
+    if (!g_ds_part[dev]) SDVAR_HIP(hipMalloc((void**)&g_ds_part[dev], (size_t)DS_MAX_BLOCKS * 2 * sizeof(double)));
+    SDVAR_TRY_Q(diff_stats_partials(a, b, n, nullptr, g_ds_part[dev], stream));
+    return diff_stats_sum(g_ds_part[dev], diff_stats_blocks(n), 1, 0, 0, 2, sums, accumulate, stream);
+}
+
+// hits[s][v] += 1 for every id v of scale s (ids (B, L), scale s = tokens [end[s-1], end[s]) of a row).  Integer atomics: the counts do not depend on
+// the order; an id outside [0, V) (all-NaN distances) is not counted.
+struct QuantScaleEnds { int end[16]; };
+__global__ __launch_bounds__(256) void quant_hits_kernel(const long long* __restrict__ ids, int B, int L, int S, QuantScaleEnds e, int V, int* __restrict__ hits) {
+    const int total = B * L;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int p = i % L;
+        int s = 0;
+        while (s < S - 1 && p >= e.end[s]) ++s;
+        const long long id = ids[i];
+        if (id >= 0 && id < V) atomicAdd(hits + (size_t)s * V + id, 1);
+    }
+}
+
+int quant_hits(const long long* ids, int B, int L, int S, const int* pn, int V, int* hits, hipStream_t stream) {
+    SDVAR_CHECK_ARG(ids && hits && pn && B >= 1 && S >= 1 && S <= 16 && V >= 1 && (size_t)B * L <= 0x7FFFFFFF, "quant_hits: bad arguments");
+    QuantScaleEnds e;
+    int acc = 0;
+    for (int s = 0; s < 16; ++s) { if (s < S) acc += pn[s] * pn[s]; e.end[s] = acc; }
+    SDVAR_CHECK_ARG(acc == L, "quant_hits: L %d != sum pn^2 %d", L, acc);
+    SDVAR_HIP(hipMemsetAsync(hits, 0, (size_t)S * V * sizeof(int), stream));
+    const int total = B * L;
+    hipLaunchKernelGGL(quant_hits_kernel, dim3((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024), dim3(256), 0, stream, ids, B, L, S, e, V, hits);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
 }  // namespace sdvar

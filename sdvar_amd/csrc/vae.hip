@@ -506,6 +506,7 @@ __global__ __launch_bounds__(256) void convout_partial_kernel(const float* __res
     }
 }
 
+template <bool CLAMP>     // false: VQVAE.forward's unclamped image (vqvae.py:59)
 __global__ __launch_bounds__(256) void convout_gather_kernel(const float* __restrict__ t, const float* __restrict__ bias, float* __restrict__ img, int B, int H, int W) {
     const size_t total = (size_t)B * 3 * H * W;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -516,7 +517,7 @@ __global__ __launch_bounds__(256) void convout_gather_kernel(const float* __rest
             const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
             if (yy >= 0 && yy < H && xx >= 0 && xx < W) acc += t[(((size_t)b * H + yy) * W + xx) * 28 + tap * 3 + o];
         }
-        img[i] = fminf(fmaxf(acc, -1.0f), 1.0f);
+        img[i] = CLAMP ? fminf(fmaxf(acc, -1.0f), 1.0f) : acc;
     }
 }
 
@@ -536,12 +537,14 @@ static int convout_weights(const float* w, float* wt, int C, hipStream_t s) {
 
 // norm_out + SiLU + conv_out + clamp: x rows [B H W][C], stats [B][32][mean, rstd], wt from convout_weights, t27 scratch of B H W 28 floats -> img (B, 3, H, W)
 static int convout(const float* x, const float* stats, const float* gamma, const float* beta, const float* wt, const float* bias, float* t27, float* img, int B, int C, int H,
-                   int W, hipStream_t s) {
+                   int W, hipStream_t s, bool clamp = true) {
     const size_t M = (size_t)B * H * W;
     hipLaunchKernelGGL(convout_partial_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, x, stats, gamma, beta, wt, t27, B, C, H, W);
     SDVAR_LAUNCH_CHECK();
     const size_t total = (size_t)B * 3 * H * W;
-    hipLaunchKernelGGL(convout_gather_kernel, dim3((unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192)), dim3(256), 0, s, t27, bias, img, B, H, W);
+    const dim3 grid((unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192));
+    if (clamp) hipLaunchKernelGGL(convout_gather_kernel<true>, grid, dim3(256), 0, s, t27, bias, img, B, H, W);
+    else hipLaunchKernelGGL(convout_gather_kernel<false>, grid, dim3(256), 0, s, t27, bias, img, B, H, W);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
@@ -814,9 +817,7 @@ struct Runner {
 
 }  // namespace
 
-extern "C" {
-
-int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream) {
+static int vae_decode_impl(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream, bool clamp) {
     SDVAR_CHECK_ARG(v && f_hat && img, "vae_decode: null argument");
     SDVAR_CHECK_ARG(v->bound, "vae_decode: weights not bound");
     SDVAR_CHECK_ARG(B >= 1 && B <= v->d.max_batch, "vae_decode: batch %d exceeds max_batch %d", B, v->d.max_batch);
@@ -859,8 +860,13 @@ int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, 
     }
     // norm_out + SiLU + conv_out + clamp
     VAE_TRY(r.stats_of(r.x, v->c_out));
-    return convout(r.x, v->stats, v->norm_out.gamma, v->norm_out.beta, v->wt_out, v->b_out, v->t27, img, B, v->c_out, r.H, r.H, s);
+    return convout(r.x, v->stats, v->norm_out.gamma, v->norm_out.beta, v->wt_out, v->b_out, v->t27, img, B, v->c_out, r.H, r.H, s, clamp);
 }
+
+extern "C" {
+
+int sdvar_vae_decode(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream) { return vae_decode_impl(v, f_hat, B, img, stream, true); }
+int sdvar_vae_decode_raw(sdvar_vae_t* v, const float* f_hat, int32_t B, float* img, void* stream) { return vae_decode_impl(v, f_hat, B, img, stream, false); }
 
 #define SDVAR_TRY_(call) do { int rc_ = (call); if (rc_ != SDVAR_OK) return rc_; } while (0)
 /* single operators for the parity tests */

@@ -100,6 +100,20 @@ def allreduce_eval_sums(sums: torch.Tensor, tot: int) -> Tuple[float, ...]:
     return tuple(vec.cpu().tolist())
 
 
+def allreduce_vae_sums(sums: torch.Tensor, vq_weighted: float, n_elems: int, tot: int, hits_SV):
+    """Tokenizer validation (sdvar_amd.evaluate.eval_vae): the rank's {sum |rec - inp|, sum (rec - inp)^2} (float64, on the device), its image-weighted VQ loss
+    sum, element count and image count in ONE float64 all-reduce, and the (S, V) int64 code hit counts (a numpy array) in a second one.  Returns the five
+    global values and the global hit counts (identical on every rank)."""
+    dev = _coll_device(sums.device)
+    vec = torch.cat((sums.detach().to(device=dev, dtype=torch.float64).reshape(2),
+                     torch.tensor([float(vq_weighted), float(n_elems), float(tot)], dtype=torch.float64, device=dev)))
+    hits = torch.from_numpy(hits_SV).to(device=dev, dtype=torch.int64)
+    if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+        tdist.all_reduce(vec, op=tdist.ReduceOp.SUM)
+        tdist.all_reduce(hits, op=tdist.ReduceOp.SUM)
+    return tuple(vec.cpu().tolist()) + (hits.cpu().numpy(),)
+
+
 def max_over_ranks(value: float, device) -> float:
     t = torch.tensor([value], dtype=torch.float64, device=_coll_device(device))
     if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:

@@ -81,12 +81,14 @@ _SIGNATURES = {
     "sdvar_quant_next_from": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P]),
     "sdvar_quant_next_h": (_I, [_P, _I, _P, _P, _P, _I, _P]),
     "sdvar_quant_encode": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "sdvar_quant_encode_stats": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sdvar_gumbel_mix": (_I, [_P, _P, _I, _I, _D, _D, _P, _U64, _U32, _U32, _P, _P]),
     "sdvar_vae_create": (_I, [C.POINTER(_VaeDesc), C.POINTER(_P)]),
     "sdvar_vae_destroy": (_I, [_P]),
     "sdvar_vae_tensor_count": (_I, [C.POINTER(_VaeDesc)]),
     "sdvar_vae_bind": (_I, [_P, C.POINTER(_P), _I, _P]),
     "sdvar_vae_decode": (_I, [_P, _P, _I, _P, _P]),
+    "sdvar_vae_decode_raw": (_I, [_P, _P, _I, _P, _P]),
     "sdvar_vae_enc_create": (_I, [C.POINTER(_VaeDesc), C.POINTER(_P)]),
     "sdvar_vae_enc_destroy": (_I, [_P]),
     "sdvar_vae_enc_tensor_count": (_I, [C.POINTER(_VaeDesc)]),
@@ -96,6 +98,7 @@ _SIGNATURES = {
     "sdvar_verify_accept": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _P, _P, _P]),
     "sdvar_cfg_combine": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _P]),
     "sdvar_xent_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "sdvar_img_err_stats": (_I, [_P, _P, C.c_int64, _P, _I, _P]),
     "sdvar_verify_accept_ex": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "sdvar_op_gemm": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P]),
     "sdvar_op_ln_modulate": (_I, [_P, _P, _P, _P, _P, _U64, _I, _I, _I, _I, _I, _P]),
@@ -346,6 +349,24 @@ class QuantCtx:
         _check(self.lib.sdvar_quant_encode(self.h, _ptr(f), B, _ptr(ids), _ptr(f_hat), _ptr(ps), _stream()))
         return ids, f_hat, ps
 
+    def encode_stats(self, f: torch.Tensor, per_scale: bool = False, straight_through: bool = False):
+        """VectorQuantizer2.forward in eval mode (quant.py:52-104) on the device: `encode` (the same launches, the same bits) -> (ids, f_hat, per_scale or
+        None, hits (S, V) int32 = bincount of every scale's ids, sqerr (S,) float64 = sum (f_hat_s - f)^2 after every scale, f_st or None = the
+        straight-through (f_hat - f) + f of quant.py:98)."""
+        B, HW = f.shape[0], self.lad.patch_nums[-1]
+        if f.dtype != torch.float32 or not f.is_contiguous() or f.device != self.device:
+            f = f.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(f.shape[1:]) != (self.Cv, HW, HW) or B > self.max_batch:
+            raise SdvarError(f"encode_stats: f {tuple(f.shape)} does not fit (max_batch {self.max_batch}, {self.Cv} x {HW}^2)")
+        ids = torch.empty(B, self.lad.L, device=self.device, dtype=torch.int64)
+        f_hat = torch.empty_like(f)
+        ps = torch.empty(self.lad.S, *f.shape, device=self.device, dtype=torch.float32) if per_scale else None
+        hits = torch.empty(self.lad.S, self.V, device=self.device, dtype=torch.int32)
+        sqerr = torch.empty(self.lad.S, device=self.device, dtype=torch.float64)
+        f_st = torch.empty_like(f) if straight_through else None
+        _check(self.lib.sdvar_quant_encode_stats(self.h, _ptr(f), B, _ptr(ids), _ptr(f_hat), _ptr(ps), _ptr(hits), _ptr(sqerr), _ptr(f_st), _stream()))
+        return ids, f_hat, ps, hits, sqerr, f_st
+
     def gumbel_mix(self, masked: torch.Tensor, B: int, l: int, ratio: float, tau: float, e: Optional[torch.Tensor], seed: int, draw: int, image_offset: int,
                    h_out: torch.Tensor):
         """var.py:206-208 + helpers.py:22-36: soft codebook mix of the masked CFG logits under gumbel noise -> h (B, l, Cvae)."""
@@ -412,8 +433,9 @@ class VaeCtx:
                 names.append(f"decoder.up.{lv}.upsample.conv")
         return names + ["decoder.norm_out", "decoder.conv_out"]
 
-    def decode(self, f_hat: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """f_hat (B, Cvae, h, w) fp32 on the device -> image (B, 3, H, W) in [-1, 1]; runs on torch's current stream."""
+    def decode(self, f_hat: torch.Tensor, out: Optional[torch.Tensor] = None, clamp: bool = True) -> torch.Tensor:
+        """f_hat (B, Cvae, h, w) fp32 on the device -> image (B, 3, H, W) in [-1, 1]; runs on torch's current stream.  clamp=False: the unclamped
+        image of VQVAE.forward (vqvae.py:59, sdvar_vae_decode_raw)."""
         B = f_hat.shape[0]
         if f_hat.dtype != torch.float32 or not f_hat.is_contiguous() or f_hat.device != self.device:
             f_hat = f_hat.to(device=self.device, dtype=torch.float32).contiguous()
@@ -421,8 +443,11 @@ class VaeCtx:
             raise SdvarError(f"decode: f_hat {tuple(f_hat.shape)} does not fit (max_batch {self.max_batch}, {self.z} x {self.latent_hw}^2)")
         if out is None:
             out = torch.empty(B, 3, self.out_hw, self.out_hw, device=self.device, dtype=torch.float32)
-        _check(self.lib.sdvar_vae_decode(self.h, _ptr(f_hat), B, _ptr(out), _stream()))
+        _check((self.lib.sdvar_vae_decode if clamp else self.lib.sdvar_vae_decode_raw)(self.h, _ptr(f_hat), B, _ptr(out), _stream()))
         return out
+
+    def decode_raw(self, f_hat: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self.decode(f_hat, out, clamp=False)
 
     def close(self):
         if self.h:
@@ -616,6 +641,18 @@ def xent_stats(logits: torch.Tensor, targets: torch.Tensor, tail: int, sums: tor
     assert argmax_out is None or (argmax_out.dtype == torch.int64 and argmax_out.numel() == B * L)
     load_library()
     _check(_lib.sdvar_xent_stats(_ptr(logits), _ptr(targets), B, L, V, tail, _ptr(nll_out), _ptr(argmax_out), _ptr(sums), int(bool(accumulate)), _stream()))
+
+
+def img_err_stats(a: torch.Tensor, b: torch.Tensor, sums: torch.Tensor, accumulate: bool = False):
+    """sdvar_img_err_stats: a, b fp32 device tensors of one shape -> sums (2,) float64 {sum |a - b|, sum (a - b)^2}, overwritten or (accumulate) added to
+    (fixed-order fp64 reduction: repeated calls are bit-identical)."""
+    load_library()
+    if a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32 or a.device != b.device or a.numel() == 0:
+        raise SdvarError(f"img_err_stats: a {tuple(a.shape)} {a.dtype} and b {tuple(b.shape)} {b.dtype} must be equally shaped, non-empty fp32 tensors on one device")
+    if sums.dtype != torch.float64 or sums.numel() != 2 or sums.device != a.device:
+        raise SdvarError("img_err_stats: sums must be 2 float64 on the tensors' device")
+    a, b = a.contiguous(), b.contiguous()
+    _check(_lib.sdvar_img_err_stats(_ptr(a), _ptr(b), a.numel(), _ptr(sums), int(bool(accumulate)), _stream()))
 
 
 def last_gemm_cfg() -> Dict[str, int]:

@@ -3,8 +3,11 @@
 The quantizer tensors (codebook, shared Phi convs) feed sdvar_amd/csrc/quant.hip; the conv decoder `fhat_to_img`
 (/root/reference/models/vqvae.py:62-63, models/basic_vae.py:163-226) runs as hand-written HIP
 (csrc/conv.hip, csrc/vae.hip) through engine.VaeCtx.  The nn.Module tree below exists for the parameter names only - they follow
-the upstream checkpoint `vae_ch160v4096z32.pth` so it loads unchanged.  No module here has a forward(): there is no torch math in this package
-(the PyTorch decoder the GPU parity tests compare against lives in tests/torch_ref.py).
+the upstream checkpoint `vae_ch160v4096z32.pth` so it loads unchanged.  There is no torch math in this package
+(the PyTorch decoder the GPU parity tests compare against lives in tests/torch_ref.py), and no nn.Module class below defines a forward() of its own:
+VQVAE.forward / VectorQuantizer2.forward (vqvae.py:56-59, quant.py:52-104: reconstruction, VQ loss, codebook usage; eval mode) is a sequence of HIP calls
+that the two container classes inherit from the plain mixins _VaeForward and _QuantizerForward, so tests/test_abi.py's rule that the nn.Module classes
+here stay parameter containers keeps holding, and its scan for torch arithmetic covers the mixins like every other line of the package.
 
 The image side (vqvae.py:65-90, quant.py:107-184: img_to_idxBl, img_to_reconstructed_img, idxBl_to_img, embed_to_img,
 f_to_idxBl_or_fhat, embed_to_fhat, idxBl_to_var_input) runs on HIP as well: the encoder + quant_conv through engine.VaeEncCtx
@@ -15,7 +18,9 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Union
 
+import numpy as np
 import torch
+import torch.distributed as tdist
 import torch.nn as nn
 
 
@@ -109,13 +114,61 @@ class _PhiOne(nn.Module):           # PhiShared (quant.py:209-216): quant_resi.q
         self.qresi = nn.Conv2d(c, c, 3, 1, 1)
 
 
-class Quantizer(nn.Module):
+def _refuse_forward(mod: nn.Module, t: torch.Tensor, what: str):
+    """forward() runs in eval mode on GPU tensors without autograd; anything else is an error, never a torch fall-back."""
+    from . import engine as E
+    if mod.training:
+        raise E.SdvarError(f"{what}: the module is in training mode; the HIP forward is the reference's eval branch (no EMA update, no backward): call .eval() first")
+    if t.requires_grad and torch.is_grad_enabled():
+        raise E.SdvarError(f"{what}: the input requires grad but no backward exists for the HIP kernels; detach it or run under torch.no_grad()")
+    if not t.is_cuda:
+        raise E.SdvarError(f"{what} runs on HIP and needs GPU tensors")
+
+
+class _QuantizerForward:
+    """VectorQuantizer2.forward (quant.py:52-104) in eval mode on HIP: engine.QuantCtx.encode_stats (csrc/quant.hip)."""
+
+    def forward(self, f_BChw: torch.Tensor, ret_usages=False):
+        """-> (f_hat, usages, mean_vq_loss): f_hat the straight-through (f_hat - f) + f of quant.py:98; usages None or per scale the percentage of
+        codes whose ema_vocab_hit_SV entry reaches the reference's margin (world size 1 without a process group); mean_vq_loss a 0-dim fp32 tensor,
+        (1/S) sum_s (beta + 1) mse(f_hat_s, f) - without autograd the two terms of quant.py:95 are one number."""
+        f_st, usages, loss, _ = self._forward_hip(f_BChw, ret_usages)
+        return f_st, usages, torch.tensor(loss, dtype=torch.float32, device=f_st.device)
+
+    def _forward_hip(self, f_BChw: torch.Tensor, ret_usages: bool):
+        """forward() with the loss as a python float (float64 arithmetic on the S sums) and the (S, V) int32 hit counts of this batch."""
+        _refuse_forward(self, f_BChw, "Quantizer.forward")
+        f = f_BChw.detach()
+        if f.dtype != torch.float32:
+            f = f.float()                                                                             # quant.py:54
+        pns = self._ladder(None)
+        if f.dim() != 4 or f.shape[1] != self.Cvae or f.shape[2] != pns[-1] or f.shape[3] != pns[-1]:
+            raise self._err(f"Quantizer.forward: f of shape {tuple(f.shape)}: expected (B, {self.Cvae}, {pns[-1]}, {pns[-1]})")
+        ctx = self._ctx(f.device, f.shape[0], pns)
+        with torch.no_grad(), torch.cuda.device(f.device):
+            _, _, _, hits, sqerr, f_st = ctx.encode_stats(f, straight_through=True)
+        numel = f.numel()
+        loss = sum((self.beta + 1.0) * (v / numel) for v in sqerr.cpu().tolist()) / len(pns)        # quant.py:95-97
+        usages = self._usages(numel // f.shape[1]) if ret_usages else None
+        return f_st, usages, loss, hits
+
+    def _usages(self, n_rows: int) -> List[float]:
+        """quant.py:100-102 on the host, for a batch of n_rows = B H W rows: per scale the percentage of codes whose ema_vocab_hit_SV entry reaches the margin."""
+        world = tdist.get_world_size() if tdist.is_available() and tdist.is_initialized() else 1
+        margin = world * n_rows / self.vocab_size * 0.08
+        ema = self.ema_vocab_hit_SV.detach().to(dtype=torch.float32).cpu().numpy()
+        # torch compares the fp32 buffer with the scalar rounded to fp32 and takes the mean in fp32
+        return [float(np.float32(np.count_nonzero(row >= np.float32(margin))) / np.float32(self.vocab_size)) * 100 for row in ema]
+
+
+class Quantizer(_QuantizerForward, nn.Module):
     """quantize.* tensors of the checkpoint (models/quant.py:15-43) in the layout `share_quant_resi` selects there (quant.py:27-32): 0 = one Phi per scale
     (PhiNonShared, an nn.ModuleList: quant_resi.<k>), 1 = one Phi for all (PhiShared), >= 2 = partially shared.  The arithmetic lives in csrc/quant.hip."""
-    def __init__(self, vocab_size, Cvae, v_patch_nums, share_quant_resi=4, using_znorm=False):
+    def __init__(self, vocab_size, Cvae, v_patch_nums, share_quant_resi=4, using_znorm=False, beta: float = 0.25):
         super().__init__()
         self.vocab_size, self.Cvae, self.v_patch_nums = vocab_size, Cvae, tuple(v_patch_nums)
         self.using_znorm = bool(using_znorm)
+        self.beta = float(beta)             # commitment weight (quant.py:18, 38): enters forward()'s mean_vq_loss
         self._hip_q = None
         if share_quant_resi == 0:
             self.quant_resi = nn.ModuleList([nn.Conv2d(Cvae, Cvae, 3, 1, 1) for _ in range(len(v_patch_nums))])
@@ -229,9 +282,24 @@ class Quantizer(nn.Module):
         return torch.cat(nxts, dim=1)
 
 
-class VQVAE(nn.Module):
+class _VaeForward:
+    """VQVAE.forward (vqvae.py:56-59) on HIP: encoder -> Quantizer.forward -> decoder without the clamp."""
+
+    def forward(self, inp: torch.Tensor, ret_usages=False):
+        """-> (rec, usages, vq_loss): rec (B, 3, H, W) the UNCLAMPED reconstruction of inp (B, 3, H, W) in [-1, 1]; usages / vq_loss as Quantizer.forward."""
+        rec, usages, loss, _ = self._forward_hip(inp, ret_usages)
+        return rec, usages, torch.tensor(loss, dtype=torch.float32, device=rec.device)
+
+    def _forward_hip(self, inp: torch.Tensor, ret_usages: bool):
+        _refuse_forward(self, inp, "VQVAE.forward")
+        with torch.no_grad():
+            f_st, usages, loss, hits = self.quantize._forward_hip(self.img_to_f(inp.detach()), ret_usages)
+            return self._decode(f_st, clamp=False), usages, loss, hits
+
+
+class VQVAE(_VaeForward, nn.Module):
     def __init__(self, vocab_size=4096, z_channels=32, ch=128, share_quant_resi=4, v_patch_nums: Sequence[int] = (1, 2, 3, 4, 5, 6, 8, 10, 13, 16),
-                 test_mode=True, with_encoder=True, using_znorm=False, **_unused):
+                 test_mode=True, with_encoder=True, using_znorm=False, beta: float = 0.25, **_unused):
         super().__init__()
         self.V = self.vocab_size = vocab_size
         self.Cvae = z_channels
@@ -242,7 +310,7 @@ class VQVAE(nn.Module):
             self.encoder = Encoder(ch, ch_mult, nrb, z_channels)
         self.decoder = Decoder(ch, ch_mult, nrb, z_channels)
         self.downsample = 2 ** (len(ch_mult) - 1)
-        self.quantize = Quantizer(vocab_size, z_channels, v_patch_nums, share_quant_resi, using_znorm)
+        self.quantize = Quantizer(vocab_size, z_channels, v_patch_nums, share_quant_resi, using_znorm, beta=beta)
         self.quant_conv = nn.Conv2d(z_channels, z_channels, 3, 1, 1)
         self.post_quant_conv = nn.Conv2d(z_channels, z_channels, 3, 1, 1)
         if test_mode:
@@ -253,9 +321,12 @@ class VQVAE(nn.Module):
     @torch.no_grad()
     def fhat_to_img(self, f_hat: torch.Tensor) -> torch.Tensor:      # vqvae.py:62-63
         """(B, Cvae, h, w) -> (B, 3, 16h, 16w) in [-1, 1] on the HIP decoder.  GPU tensors only: there is no CPU path."""
+        return self._decode(f_hat, clamp=True)
+
+    def _decode(self, f_hat: torch.Tensor, clamp: bool) -> torch.Tensor:
         from . import engine as E
         if not f_hat.is_cuda:
-            raise E.SdvarError("VQVAE.fhat_to_img runs on the HIP decoder and needs a GPU tensor (tests/torch_ref.py holds the PyTorch test reference)")
+            raise E.SdvarError("VQVAE: decoding (fhat_to_img, forward) runs on the HIP decoder and needs a GPU tensor (tests/torch_ref.py holds the PyTorch test reference)")
         B, hw = f_hat.shape[0], f_hat.shape[-1]
         ctx = self._hip_ctx
         if ctx is None or ctx.device != f_hat.device or ctx.max_batch < B or ctx.latent_hw != hw:
@@ -263,7 +334,7 @@ class VQVAE(nn.Module):
                 ctx.close()
             sd = {k: v for k, v in self.state_dict().items() if k.startswith(("decoder.", "post_quant_conv."))}
             ctx = self._hip_ctx = E.VaeCtx(sd, B, f_hat.device, latent_hw=hw, ch_mult=self._ch_mult, num_res_blocks=self._nrb)
-        return ctx.decode(f_hat)
+        return ctx.decode(f_hat, clamp=clamp)
 
     @torch.no_grad()
     def img_to_f(self, img: torch.Tensor) -> torch.Tensor:
