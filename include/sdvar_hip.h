@@ -286,6 +286,13 @@ int sdvar_op_sdpa(const float* q, const float* k, const float* v, float* out, co
  * Bb, Hb = the bias's own batch and head extents (1 where it broadcasts), so a tile that one head needs is never skipped for another. */
 int sdvar_op_sdpa_skip_map(const void* bias, int32_t bias_kind, const int64_t* bias_strides /*host*/, int32_t Bb, int32_t Hb, int32_t Lq, int32_t Lk, uint8_t* skip_map,
                            void* stream);
+/* The reference's flash_attn_func slot (models/basic_var.py:23, called at :112-113 when KV caching is on and qkv is not fp32, :97-98): out = softmax(scale q k^T) v on
+ * fp16 or bf16 operands (dtype 1 = fp16, 2 = bf16; q, k, v and out all of it), no bias.  head_dim must be 64; Lq and Lk are independent, any value >= 1.
+ * strides as for sdvar_op_sdpa (host, 12 x int64, elements: (batch, head, token) of q, k, v, out; channel stride 1).  A 64-element row is 128 bytes and is moved with 16-byte
+ * accesses: every pointer % 16 == 0 and every stride a non-negative multiple of 8 elements.  Scores, softmax and the output accumulate in fp32 (scale multiplies the fp32
+ * score); the softmax weights are rounded to dtype (nearest even) for the P V product and the result is rounded once.  Deterministic; no host synchronisation. */
+int sdvar_op_sdpa_h(const void* q, const void* k, const void* v, void* out, const int64_t* strides /*host*/, int32_t dtype, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
+                    int32_t head_dim, double scale, void* stream);
 
 /* conv weight (Cout, Cin, kh, kw) with kh*kw = taps (1 or 9) -> K-blocked planes [3][taps*Cin/32][Cout][32], k = tap*Cin + cin */
 int sdvar_op_conv_weight_planes(const float* w, uint16_t* planes, int32_t Cout, int32_t Cin, int32_t taps, uint64_t plane_stride, int32_t plane_format /* 3 | 2 */,

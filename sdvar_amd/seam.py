@@ -1,20 +1,24 @@
 """Drop-in HIP operators for the reference's module-level operator slots (models/basic_var.py:15-30).
 
-The reference calls three module globals on its hot path: `slow_attn` / `memory_efficient_attention` (basic_var.py:113-117) and
-`fused_mlp_func` (basic_var.py:46-50, captured per FFN at :36).  This module provides all three on the library's kernels, for a
+The reference calls four module globals on its hot path: `flash_attn_func` / `memory_efficient_attention` / `slow_attn` (basic_var.py:113-117) and
+`fused_mlp_func` (basic_var.py:46-50, captured per FFN at :36).  This module provides all four on the library's kernels, for a
 maintainer of the reference who wants the kernels without adopting the sampling loop:
 
     from sdvar_amd import seam
     import models.basic_var as basic_var
     seam.install(basic_var, model)          # slots + the fused_mlp_func every FFN captured at construction
+    seam.enable_flash(basic_var, model)     # optional: flash_attn_func for the cached, unmasked calls under autocast (fp16 / bf16 operands)
 
-Inference only, fp32 only: no backward, no dropout, head dim 64.  Anything else raises SdvarError - there is no fall-back to torch.
+Inference only: no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
+`flash_attn_func` takes fp16 or bf16 operands only (and no mask).  Anything else raises SdvarError - there is no fall-back to torch.
 Torch is used for device memory and the current stream only; bool masks go to the kernel as bytes.
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
 reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
 read in place; a tensor that does not is copied once with .contiguous().
 A query row whose keys are ALL masked has no defined value (NaN); other rows are unaffected.
+The same rule holds for flash_attn_func's half operands with 2-byte elements: data_ptr % 16 == 0, every stride a multiple of 8 elements, last stride 1 (the
+unbind(dim=2) views of one (B, L, 3, H, 64) buffer and torch.cat caches meet it).
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ import torch
 from . import engine as E
 from .engine import SdvarError
 
-__all__ = ["configure", "slow_attn", "memory_efficient_attention", "fused_mlp_func", "install", "clear_caches"]
+__all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "fused_mlp_func", "install", "enable_flash", "clear_caches"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -150,6 +154,65 @@ def memory_efficient_attention(q, k, v, attn_bias=None, p: float = 0.0, scale: O
     return _sdpa("memory_efficient_attention", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
+_HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}          # sdvar_op_sdpa_h's dtype codes
+
+
+def _rows_aligned_h(t: torch.Tensor) -> bool:
+    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 and s >= 0 for s in t.stride()[:-1])
+
+
+def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[float] = None, causal: bool = False, window_size=(-1, -1), softcap: float = 0.0,
+                    alibi_slopes=None, deterministic: bool = False, return_attn_probs: bool = False):
+    """The `flash_attn_func` slot (flash-attn's signature; basic_var.py:23, called at :113 when no mask is passed and qkv is not fp32): softmax(softmax_scale q k^T) v.
+    q (B, Lq, H, 64), k / v (B, Lk, H, 64), all three float16 or all three bfloat16 on the GPU; operands meeting the alignment rule are read in place, any other is
+    copied once into a dense, freshly allocated tensor.  softmax_scale=None means 1/sqrt(64).  Returns a contiguous (B, Lq, H, 64) tensor of the operand dtype.  fp32 accumulation, the
+    softmax weights rounded to the operand dtype (nearest even) for the P V product; deterministic always (`deterministic` is accepted and ignored)."""
+    who = "flash_attn_func"
+    if dropout_p and dropout_p > 0:
+        raise SdvarError(f"{who}: dropout_p > 0 is not supported (inference only)")
+    if causal:
+        raise SdvarError(f"{who}: causal=True is not supported (the reference's cached calls pass no mask)")
+    if window_size is not None and tuple(window_size) != (-1, -1):
+        raise SdvarError(f"{who}: window_size {tuple(window_size)} is not supported (only (-1, -1), no sliding window)")
+    if softcap:
+        raise SdvarError(f"{who}: softcap {softcap} is not supported (only 0)")
+    if alibi_slopes is not None:
+        raise SdvarError(f"{who}: alibi_slopes is not supported")
+    if return_attn_probs:
+        raise SdvarError(f"{who}: return_attn_probs=True is not supported (no score matrix is ever written)")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise SdvarError(f"{who}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+        if t.dtype == torch.float32:
+            raise SdvarError(f"{who}: {name} is torch.float32; this slot takes float16 / bfloat16 operands - use slow_attn or memory_efficient_attention for float32")
+        if t.dtype not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float16 and bfloat16 operands are supported")
+        if t.requires_grad and torch.is_grad_enabled():
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
+        if t.dim() != 4:
+            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
+    if q.dtype != k.dtype or q.dtype != v.dtype:
+        raise SdvarError(f"{who}: mixed dtypes: q {q.dtype}, k {k.dtype}, v {v.dtype} (all three must be float16 or all three bfloat16)")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.shape[-1] != 64:
+            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+    B, Lq, H, _ = q.shape
+    Lk = k.shape[1]
+    if k.shape != v.shape or k.shape[0] != B or k.shape[2] != H or B < 1 or H < 1 or Lq < 1 or Lk < 1:
+        raise SdvarError(f"{who}: shapes do not match: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+    if q.device != k.device or q.device != v.device:
+        raise SdvarError(f"{who}: operands live on different devices")
+    # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
+    q, k, v = (t if _rows_aligned_h(t) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
+    out = torch.empty((B, Lq, H, 64), dtype=q.dtype, device=q.device)
+    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, out) for i in (0, 2, 1)))
+    scale = 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale)
+    E._check(E.load_library().sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[q.dtype], B, H, Lq, Lk, 64, scale, E._stream()))
+    return out
+
+
 def _weight_planes(w: torch.Tensor, mode: str):
     key = (mode, w.data_ptr(), w._version, tuple(w.shape))
     hit = _WEIGHT_PLANES.get(key)
@@ -229,3 +292,14 @@ def install(module, model=None) -> None:
         for m in model.modules():
             if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
                 m.fused_mlp_func = fused_mlp_func
+
+
+def enable_flash(module, model=None) -> None:
+    """Set the `flash_attn_func` global of a basic_var-like module; with a model, also `using_flash = True` on every submodule that has a `using_flash` attribute
+    (the reference decides that flag at construction, basic_var.py:81, from whether flash-attn could be imported).  Separate from install(): the slot only serves
+    half-precision operands, i.e. a model run under torch.autocast."""
+    module.flash_attn_func = flash_attn_func
+    if model is not None:
+        for m in model.modules():
+            if hasattr(m, "using_flash"):
+                m.using_flash = True

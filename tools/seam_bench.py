@@ -6,10 +6,13 @@
                                                                       q, k, v and sdvar_op_attention on an fp32 cache)
                                                                       B 16, H 16, 256 queries against 680 cached keys, no mask
   fused_mlp_func   vs F.linear / tanh-GELU / F.linear                 C 1024 (hidden 4096), M = 680 * 8 and M = 64, every GEMM mode
+  flash_attn_func  vs torch's SDPA in the same half dtype             fp16 and bf16, (B, L, H, 64) views of one qkv buffer / torch.cat caches, no mask:
+                   and seam.slow_attn on fp32 copies of the           B 16, H 16, Lq 256 on Lk 680;  B 16, H 16, Lq 16 on Lk 91 (cached calls);
+                   same operands (the only route before the slot)     B 8, H 16, L 680 (self-attention);  B 4, H 30, Lq 1024 on Lk 2240 (512^2)
 
 Every figure is the MEDIAN over --reps windows of --iters back-to-back calls, timed with device events; the candidates of one shape alternate window by window, so
 drift of the machine hits them alike.  min / max of the windows are printed beside the median.  The last line is one JSON object with every median (microseconds).
-python tools/seam_bench.py [--iters 20] [--reps 9]"""
+python tools/seam_bench.py [--iters 20] [--reps 9] [--rows all|fp32|flash]"""
 import argparse
 import ctypes as C
 import json
@@ -59,10 +62,31 @@ def block_causal(patch_nums, dev):
     return torch.where(d[:, None] >= d[None, :], 0.0, float("-inf")).reshape(1, 1, len(d), len(d)).float().contiguous()
 
 
+def flash_rows(a, dev, g, results):
+    """seam.flash_attn_func on half operands: the reference's (B, L, H, 64) unbind(dim=2) views of one qkv buffer for q (and for k / v in self-attention), contiguous
+    torch.cat caches otherwise; against torch's SDPA on the same tensors and seam.slow_attn on fp32 copies (made once, outside the timed region)."""
+    for B, H, Lq, Lk in ((16, 16, 256, 680), (16, 16, 16, 91), (8, 16, 680, 680), (4, 30, 1024, 2240)):
+        for dtype in (torch.float16, torch.bfloat16):
+            qkv = torch.randn(B, Lq, 3, H, 64, device=dev, generator=g).to(dtype)
+            q = qkv[:, :, 0]
+            if Lq == Lk:
+                k, v = qkv[:, :, 1], qkv[:, :, 2]
+            else:
+                k, v = torch.randn(B, Lk, H, 64, device=dev, generator=g).to(dtype), torch.randn(B, Lk, H, 64, device=dev, generator=g).to(dtype)
+            tq, tk, tv = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)                   # (B, H, L, 64) views for the (B, H, L, c) interfaces
+            fq, fk, fv = tq.float(), tk.float(), tv.float()
+            diff = (seam.flash_attn_func(q, k, v, softmax_scale=0.125).float() - F.scaled_dot_product_attention(tq, tk, tv, scale=0.125).transpose(1, 2).float()).abs().max().item()
+            r = windows({"seam.flash_attn_func": lambda: seam.flash_attn_func(q, k, v, softmax_scale=0.125),
+                         "torch SDPA same dtype": lambda: F.scaled_dot_product_attention(tq, tk, tv, scale=0.125),
+                         "seam.slow_attn on fp32 copies": lambda: seam.slow_attn(fq, fk, fv, 0.125)}, a.iters, a.reps)
+            report(f"flash {str(dtype)[6:]} B{B} H{H} Lq{Lq} Lk{Lk} (max |seam - torch| {diff:.1e})", r, results, 4.0 * B * H * Lq * Lk * 64)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--rows", choices=("all", "fp32", "flash"), default="all", help="fp32: the slow_attn / fused_mlp_func rows; flash: the flash_attn_func rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("seam_bench: no GPU (there is nothing to time on a CPU)")
@@ -70,6 +94,10 @@ def main():
     dev, lib, results = torch.device("cuda:0"), E.load_library(), {}
     P = lambda t: C.c_void_p(t.data_ptr())
     g = torch.Generator(device=dev).manual_seed(0)
+    if a.rows == "flash":
+        flash_rows(a, dev, g, results)
+        print(json.dumps(results))
+        return
 
     # ---- attention, teacher-forced shape: q, k, v are the reference's views of one (B, L, 3, H, 64) buffer (basic_var.py:93-99), attn_l2_norm scaling
     B, H, L = 8, 16, sum(p * p for p in LADDER_256)
@@ -130,6 +158,8 @@ def main():
         fns["torch linear/gelu/linear fp32"] = lambda: F.linear(F.gelu(F.linear(x, w1, b1), approximate="tanh"), w2, b2)
         report(f"mlp M{M} C{Cw}", windows(fns, a.iters, a.reps), results, 4.0 * M * Cw * hid)
     seam.configure(gemm_mode=E.DEFAULT_GEMM_MODE)
+    if a.rows == "all":
+        flash_rows(a, dev, g, results)
     print(json.dumps(results))
 
 
