@@ -283,7 +283,8 @@ int sdvar_op_noise_fill(float* q, int32_t B, int32_t l, int32_t V, uint64_t seed
 int sdvar_op_sdpa(const float* q, const float* k, const float* v, float* out, const int64_t* strides /*host*/, const void* bias, int32_t bias_kind,
                   const int64_t* bias_strides /*host*/, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
 /* skip_map (device, ceil(Lq / 128) * ceil(Lk / 64) bytes): byte (qb, kt) = 1 when bias[bb][hh][128 qb ..][64 kt ..] is masked (-inf / 0) for EVERY bb < Bb, hh < Hb -
- * Bb, Hb = the bias's own batch and head extents (1 where it broadcasts), so a tile that one head needs is never skipped for another. */
+ * Bb, Hb = the bias's own batch and head extents (1 where it broadcasts), so a tile that one head needs is never skipped for another.
+ * bias_kind 1 / 2 as above; 3 = fp16 additive, 4 = bf16 additive (masked = -inf), for the half biases of sdvar_op_sdpa_hm. */
 int sdvar_op_sdpa_skip_map(const void* bias, int32_t bias_kind, const int64_t* bias_strides /*host*/, int32_t Bb, int32_t Hb, int32_t Lq, int32_t Lk, uint8_t* skip_map,
                            void* stream);
 /* The reference's flash_attn_func slot (models/basic_var.py:23, called at :112-113 when KV caching is on and qkv is not fp32, :97-98): out = softmax(scale q k^T) v on
@@ -392,6 +393,20 @@ int sdvar_debug_set_gemm_stamps(uint64_t* stamps);
 int sdvar_prof_enable(int32_t on);
 /* synchronises the recorded events and accumulates: ms, launches, algorithmic flops, algorithmic bytes per class */
 int sdvar_prof_collect(double* ms /*host[SDVAR_PROF_CLASSES]*/, int64_t* launches, double* flops, double* bytes);
+
+/* The slow_attn / memory_efficient_attention slots under torch.autocast (sdvar_amd/seam.py: slow_attn_amp, memory_efficient_attention_amp): out = softmax(scale q k^T + bias) v
+ * with the arithmetic of sdvar_op_sdpa_h (native fp16 / bf16 matrix cores, fp32 scores / softmax / accumulation, one RNE rounding of the softmax weights and of the
+ * result).  dtype (1 = fp16, 2 = bf16) is the type of v, of out and of the matrix-core operands; q (q_f32 = 1) and k (k_f32 = 1) may each be fp32 instead and are then
+ * rounded to dtype (nearest even) as they are read: the same bits as a prior cast.  strides as for sdvar_op_sdpa (host, 12 x int64: (batch, head, token) of q, k, v, out),
+ * each in ITS operand's elements; every pointer % 16 == 0; strides of a half operand are non-negative multiples of 8, of an fp32 operand of 4.  head_dim must be 64.
+ * bias_kind 0: none (bias = NULL); 1: fp32 additive, finite or -inf; 2: uint8 keep-mask (0 = masked); 3: additive in dtype.  bias_strides (host, 3 x int64, elements):
+ * (batch, head, query row), 0 = broadcast; key stride 1; rows need no alignment (sliced masks are read in place).  The bias is added to the fp32 score.
+ * skip_map (device, may be NULL; needs a bias): what sdvar_op_sdpa_skip_map wrote for THIS bias, Lq and Lk (its kind 3 / 4 for a half bias); marked tiles are never
+ * read or multiplied, and the result is the same bits with and without the map.  A query row with every key masked has no defined value (NaN here); it does not
+ * fault and does not disturb other rows.  Deterministic; no host synchronisation. */
+int sdvar_op_sdpa_hm(const void* q, const void* k, const void* v, void* out, const int64_t* strides /*host, 12*/, int32_t dtype /*1 fp16 | 2 bf16*/, int32_t q_f32,
+                     int32_t k_f32, const void* bias, int32_t bias_kind /*0 none | 1 fp32 | 2 uint8 keep | 3 additive in dtype*/, const int64_t* bias_strides /*host, 3*/,
+                     const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
 
 #ifdef __cplusplus
 }

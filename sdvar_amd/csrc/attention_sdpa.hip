@@ -28,7 +28,7 @@ constexpr int KT = 64;              // keys per LDS tile
 constexpr int KSTR = 68;            // padded K row (floats)
 constexpr int QB = 128;             // queries per workgroup
 
-enum { BIAS_NONE = 0, BIAS_F32 = 1, BIAS_U8 = 2 };
+enum { BIAS_NONE = 0, BIAS_F32 = 1, BIAS_U8 = 2, BIAS_F16 = 3, BIAS_BF16 = 4 };          // 3, 4: the skip map only (additive half biases of sdvar_op_sdpa_hm)
 
 struct SdpaArgs {
     const float *q, *k, *v; float* out;
@@ -271,6 +271,8 @@ __global__ __launch_bounds__(256) void sdpa_skip_map_kernel(const void* bias, lo
         if (key >= keys) continue;
         const long long off = bb * sb + hh * sh + (long long)(qb * QB + row) * sr + kt * KT + key;
         if (BIAS == BIAS_F32) visible = reinterpret_cast<const float*>(bias)[off] != -INFINITY;
+        else if (BIAS == BIAS_F16) visible = reinterpret_cast<const uint16_t*>(bias)[off] != 0xFC00u;         // -inf in fp16
+        else if (BIAS == BIAS_BF16) visible = reinterpret_cast<const uint16_t*>(bias)[off] != 0xFF80u;        // -inf in bf16
         else visible = reinterpret_cast<const uint8_t*>(bias)[off] != 0;
     }
     const int any = __syncthreads_or(visible);
@@ -283,12 +285,14 @@ bool aligned_strides(const long long* s) { return s[0] % 4 == 0 && s[1] % 4 == 0
 
 int sdpa_skip_map(const void* bias, int kind, const long long* bs, int Bb, int Hb, int Lq, int Lk, uint8_t* map, hipStream_t stream) {
     SDVAR_CHECK_ARG(bias && bs && map, "sdpa_skip_map: null operand");
-    SDVAR_CHECK_ARG(kind == BIAS_F32 || kind == BIAS_U8, "sdpa_skip_map: bias kind %d (1 = fp32 additive, 2 = uint8 keep-mask)", kind);
+    SDVAR_CHECK_ARG(kind >= BIAS_F32 && kind <= BIAS_BF16, "sdpa_skip_map: bias kind %d (1 = fp32 additive, 2 = uint8 keep-mask, 3 = fp16 additive, 4 = bf16 additive)", kind);
     SDVAR_CHECK_ARG(Bb >= 1 && Hb >= 1 && Lq >= 1 && Lk >= 1, "sdpa_skip_map: bad extents Bb=%d Hb=%d Lq=%d Lk=%d", Bb, Hb, Lq, Lk);
     SDVAR_CHECK_ARG(bs[0] >= 0 && bs[1] >= 0 && bs[2] >= 0, "sdpa_skip_map: negative bias stride");
     const int nkt = (Lk + KT - 1) / KT, nqb = (Lq + QB - 1) / QB;
     SDVAR_CHECK_ARG(nqb <= 65535, "sdpa_skip_map: Lq=%d too long", Lq);
     if (kind == BIAS_F32) hipLaunchKernelGGL(sdpa_skip_map_kernel<BIAS_F32>, dim3(nkt, nqb), dim3(256), 0, stream, bias, bs[0], bs[1], bs[2], Bb, Hb, Lq, Lk, map, nkt);
+    else if (kind == BIAS_F16) hipLaunchKernelGGL(sdpa_skip_map_kernel<BIAS_F16>, dim3(nkt, nqb), dim3(256), 0, stream, bias, bs[0], bs[1], bs[2], Bb, Hb, Lq, Lk, map, nkt);
+    else if (kind == BIAS_BF16) hipLaunchKernelGGL(sdpa_skip_map_kernel<BIAS_BF16>, dim3(nkt, nqb), dim3(256), 0, stream, bias, bs[0], bs[1], bs[2], Bb, Hb, Lq, Lk, map, nkt);
     else hipLaunchKernelGGL(sdpa_skip_map_kernel<BIAS_U8>, dim3(nkt, nqb), dim3(256), 0, stream, bias, bs[0], bs[1], bs[2], Bb, Hb, Lq, Lk, map, nkt);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;

@@ -9,8 +9,11 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install(basic_var, model)          # slots + the fused_mlp_func every FFN captured at construction
     seam.enable_flash(basic_var, model)     # optional: flash_attn_func for the cached, unmasked calls under autocast (fp16 / bf16 operands)
 
+    seam.install_amp(basic_var, model)      # a model run under torch.autocast: the two lines above + slow_attn_amp for the MASKED calls (half / mixed operands)
+
 Inference only: no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
-`flash_attn_func` takes fp16 or bf16 operands only (and no mask).  Anything else raises SdvarError - there is no fall-back to torch.
+`flash_attn_func` takes fp16 or bf16 operands only (and no mask); `slow_attn_amp` / `memory_efficient_attention_amp` take a half value with query and key each
+half or fp32, and masks.  Anything else raises SdvarError - there is no fall-back to torch.
 Torch is used for device memory and the current stream only; bool masks go to the kernel as bytes.
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
@@ -32,7 +35,8 @@ import torch
 from . import engine as E
 from .engine import SdvarError
 
-__all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "fused_mlp_func", "install", "enable_flash", "clear_caches"]
+__all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
+           "enable_flash", "install_amp", "clear_caches"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -57,6 +61,9 @@ def configure(gemm_mode: Optional[str] = None) -> None:
 def clear_caches() -> None:
     _SKIP_MAPS.clear()
     _WEIGHT_PLANES.clear()
+
+
+_HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}          # sdvar_op_sdpa_h's dtype codes
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -92,6 +99,43 @@ def _skip_map(mask: torch.Tensor, kind: int, bstr, Bb: int, Hb: int, Lq: int, Lk
     return smap
 
 
+def _mask_args(who: str, mask, B: int, H: int, Lq: int, Lk: int, half):
+    """(mask as the kernel reads it, bias kind, bias strides, skip map) of an attention mask; all None / 0 without one.  half = the operands' half dtype when the kernel
+    also takes an additive mask of that dtype (kind 3; the skip map's kind is 3 for fp16, 4 for bf16), else None."""
+    if mask is None:
+        return None, 0, None, None
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise SdvarError(f"{who}: the mask is a CPU tensor (or no tensor)")
+    if mask.dtype == torch.bool:
+        kind = skind = 2
+    elif mask.dtype == torch.float32:
+        kind = skind = 1
+    elif half is not None and mask.dtype == half:
+        kind, skind = 3, 2 + _HALF_DTYPES[half]
+    elif half is not None and mask.dtype in _HALF_DTYPES:
+        raise SdvarError(f"{who}: the mask is {mask.dtype} but the operands are {half}; a half-precision mask must have the operands' dtype")
+    elif half is not None:
+        raise SdvarError(f"{who}: the mask is {mask.dtype}; float32 (additive), {half} (additive) or bool (keep) only")
+    else:
+        raise SdvarError(f"{who}: the mask is {mask.dtype}; float32 (additive) or bool (keep) only")
+    if mask.dim() > 4:
+        raise SdvarError(f"{who}: the mask has {mask.dim()} dims")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    while mask.dim() < 4:
+        mask = mask.unsqueeze(0)
+    mb, mh, mq, mk = mask.shape
+    if mb not in (1, B) or mh not in (1, H) or mq not in (1, Lq) or mk != Lk:
+        raise SdvarError(f"{who}: a mask of shape {tuple(mask.shape)} does not broadcast to {(B, H, Lq, Lk)} (the key dimension must be materialised)")
+    if mask.stride(3) != 1 and Lk > 1:
+        mask = mask.contiguous()
+    sb, sh, sr = (0 if n == 1 else s for n, s in zip(mask.shape[:3], mask.stride()[:3]))
+    bstr = (C.c_int64 * 3)(sb, sh, sr)
+    # the skip map looks at the bias's OWN batch / head slices (one where it broadcasts or is expanded), every one of the Lq rows
+    smap = _skip_map(mask, skind, bstr, 1 if sb == 0 else B, 1 if sh == 0 else H, Lq, Lk)
+    return mask, kind, bstr, smap
+
+
 def _sdpa(who: str, q, k, v, idx, scale: float, mask: Optional[torch.Tensor]) -> torch.Tensor:
     """idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
     for name, t in (("query", q), ("key", k), ("value", v)):
@@ -109,29 +153,7 @@ def _sdpa(who: str, q, k, v, idx, scale: float, mask: Optional[torch.Tensor]) ->
     q, k, v = (t if _rows_aligned(t) else t.contiguous() for t in (q, k, v))
     out = torch.empty((B, Lq, H, 64), dtype=torch.float32, device=q.device)
     strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
-    kind, bstr, smap = 0, None, None
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise SdvarError(f"{who}: the mask is a CPU tensor (or no tensor)")
-        if mask.dtype == torch.bool:
-            kind, mask = 2, mask.view(torch.uint8)
-        elif mask.dtype == torch.float32:
-            kind = 1
-        else:
-            raise SdvarError(f"{who}: the mask is {mask.dtype}; float32 (additive) or bool (keep) only")
-        if mask.dim() > 4:
-            raise SdvarError(f"{who}: the mask has {mask.dim()} dims")
-        while mask.dim() < 4:
-            mask = mask.unsqueeze(0)
-        mb, mh, mq, mk = mask.shape
-        if mb not in (1, B) or mh not in (1, H) or mq not in (1, Lq) or mk != Lk:
-            raise SdvarError(f"{who}: a mask of shape {tuple(mask.shape)} does not broadcast to {(B, H, Lq, Lk)} (the key dimension must be materialised)")
-        if mask.stride(3) != 1 and Lk > 1:
-            mask = mask.contiguous()
-        sb, sh, sr = (0 if n == 1 else s for n, s in zip(mask.shape[:3], mask.stride()[:3]))
-        bstr = (C.c_int64 * 3)(sb, sh, sr)
-        # the skip map looks at the bias's OWN batch / head slices (one where it broadcasts or is expanded), every one of the Lq rows
-        smap = _skip_map(mask, kind, bstr, 1 if sb == 0 else B, 1 if sh == 0 else H, Lq, Lk)
+    mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, None)
     E._check(E.load_library().sdvar_op_sdpa(_p(q), _p(k), _p(v), _p(out), strides, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale), E._stream()))
     return out
 
@@ -152,9 +174,6 @@ def memory_efficient_attention(q, k, v, attn_bias=None, p: float = 0.0, scale: O
     if p and p > 0:
         raise SdvarError("memory_efficient_attention: p > 0 (dropout) is not supported (inference only)")
     return _sdpa("memory_efficient_attention", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
-
-
-_HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}          # sdvar_op_sdpa_h's dtype codes
 
 
 def _rows_aligned_h(t: torch.Tensor) -> bool:
@@ -211,6 +230,73 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[flo
     scale = 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale)
     E._check(E.load_library().sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[q.dtype], B, H, Lq, Lk, 64, scale, E._stream()))
     return out
+
+
+def _sdpa_amp(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
+    """The attention slots under torch.autocast.  idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
+    for name, t in (("query", q), ("key", k), ("value", v)):
+        if not isinstance(t, torch.Tensor):
+            raise SdvarError(f"{who}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+        if t.requires_grad and torch.is_grad_enabled():
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
+        if t.dim() != 4:
+            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
+        if t.shape[-1] != 64:
+            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+    if v.dtype == torch.float32:
+        if q.dtype != torch.float32 or k.dtype != torch.float32:
+            raise SdvarError(f"{who}: value is torch.float32 next to query {q.dtype} / key {k.dtype}: value fixes the dtype of the product and of the result, and a "
+                             "float32 value only goes with float32 query and key")
+        return _sdpa(who, q, k, v, idx, scale, mask)
+    half = v.dtype
+    for name, t in (("query", q), ("key", k)):
+        if t.dtype != half and t.dtype != torch.float32:
+            raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype}, value is {half} (query and key must each be {half} or float32)")
+    ib, ih, it = idx
+    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
+    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or B < 1 or H < 1 or Lq < 1 or Lk < 1:
+        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
+    if q.device != k.device or q.device != v.device:
+        raise SdvarError(f"{who}: operands live on different devices")
+    mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, half)
+    # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
+    q, k, v = (t if (_rows_aligned(t) if t.dtype == torch.float32 else _rows_aligned_h(t)) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
+    out = torch.empty((B, Lq, H, 64), dtype=half, device=q.device)
+    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
+    qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
+    lib = E.load_library()
+    if kind == 0 and not qf and not kf:                 # what flash_attn_func launches: the same bits
+        E._check(lib.sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[half], B, H, Lq, Lk, 64, float(scale), E._stream()))
+    else:
+        E._check(lib.sdvar_op_sdpa_hm(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[half], qf, kf, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale),
+                                      E._stream()))
+    return out
+
+
+def slow_attn_amp(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
+    """The `slow_attn` slot for a model run under torch.autocast (basic_var.py:117 with half or mixed operands): softmax(scale q k^T + attn_mask) v on the
+    half-precision matrix cores.  query (B, H, Lq, 64), key / value (B, H, Lk, 64) on the GPU.  `value` fixes the dtype: float16 or bfloat16, and then query and key
+    are EACH that dtype or float32 (with attn_l2_norm the reference's normalised q, and on the GPU its k, arrive in float32); a float32 operand is rounded to the half
+    dtype (nearest even) inside the kernel as it is read - the bits of a prior .to(dtype), without the pass over memory.  All three float32: slow_attn itself (same
+    bits, float32 result).  attn_mask: float32 additive, bool keep-mask or additive in the operands' half dtype, broadcastable to (B, H, Lq, Lk) with the key dimension
+    materialised; views and stride-0 expansions are read in place; the mask is added to the fp32 score.  Operands meeting their alignment rule (float32: strides % 4,
+    half: strides % 8, data_ptr % 16) are read in place, any other is copied once into a fresh dense tensor.  Without a mask and with three half operands the call is
+    flash_attn_func's kernel.  Returns a (B, H, Lq, 64) VIEW of a fresh (B, Lq, H, 64) buffer of the half dtype, as torch's SDPA returns under autocast."""
+    if dropout_p and dropout_p > 0:
+        raise SdvarError("slow_attn_amp: dropout_p > 0 is not supported (inference only)")
+    return _sdpa_amp("slow_attn_amp", query, key, value, (0, 1, 2), scale, attn_mask).permute(0, 2, 1, 3)
+
+
+def memory_efficient_attention_amp(q, k, v, attn_bias=None, p: float = 0.0, scale: Optional[float] = None):
+    """The xformers slot under torch.autocast (basic_var.py:115): q (B, Lq, H, 64), k / v (B, Lk, H, 64), dtypes and attn_bias as for slow_attn_amp; an expanded
+    (stride-0) (B, H, Lq, Lk) bias is read through its strides and never materialised.  Returns (B, Lq, H, 64).  The same kernel as slow_attn_amp with other strides."""
+    if p and p > 0:
+        raise SdvarError("memory_efficient_attention_amp: p > 0 (dropout) is not supported (inference only)")
+    return _sdpa_amp("memory_efficient_attention_amp", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
 def _weight_planes(w: torch.Tensor, mode: str):
@@ -303,3 +389,12 @@ def enable_flash(module, model=None) -> None:
         for m in model.modules():
             if hasattr(m, "using_flash"):
                 m.using_flash = True
+
+
+def install_amp(module, model=None) -> None:
+    """For a model run under torch.autocast: install(), then enable_flash(), then `module.slow_attn = slow_attn_amp`, which serves the masked calls (the
+    teacher-forced pass, the verifier's attn_bias, the hand-off prefill) on the half or mixed operands autocast delivers.  `memory_efficient_attention` is left
+    alone for the reason install() documents; assign seam.memory_efficient_attention_amp yourself before building the model if you want the BLHc route."""
+    install(module, model)
+    enable_flash(module, model)
+    module.slow_attn = slow_attn_amp

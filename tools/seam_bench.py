@@ -9,10 +9,13 @@
   flash_attn_func  vs torch's SDPA in the same half dtype             fp16 and bf16, (B, L, H, 64) views of one qkv buffer / torch.cat caches, no mask:
                    and seam.slow_attn on fp32 copies of the           B 16, H 16, Lq 256 on Lk 680;  B 16, H 16, Lq 16 on Lk 91 (cached calls);
                    same operands (the only route before the slot)     B 8, H 16, L 680 (self-attention);  B 4, H 30, Lq 1024 on Lk 2240 (512^2)
+  slow_attn_amp    vs torch's SDPA in the same half dtype with the    fp16 and bf16, (B, H, L, 64) views of one qkv buffer, attn_l2_norm scaling, ten-stage block-causal mask:
+                   same mask, and seam.slow_attn on fp32 copies       B 8, H 16, L 680 with q / k fp32 and v half (what autocast delivers), and with all three half;
+                   with the fp32 mask                                 B 16, H 16, Lq 425 on Lk 680 under rows [255:] of the mask (a two-stage verify chunk)
 
 Every figure is the MEDIAN over --reps windows of --iters back-to-back calls, timed with device events; the candidates of one shape alternate window by window, so
 drift of the machine hits them alike.  min / max of the windows are printed beside the median.  The last line is one JSON object with every median (microseconds).
-python tools/seam_bench.py [--iters 20] [--reps 9] [--rows all|fp32|flash]"""
+python tools/seam_bench.py [--iters 20] [--reps 9] [--rows all|fp32|flash|amp]"""
 import argparse
 import ctypes as C
 import json
@@ -82,11 +85,45 @@ def flash_rows(a, dev, g, results):
             report(f"flash {str(dtype)[6:]} B{B} H{H} Lq{Lq} Lk{Lk} (max |seam - torch| {diff:.1e})", r, results, 4.0 * B * H * Lq * Lk * 64)
 
 
+def amp_rows(a, dev, g, results):
+    """seam.slow_attn_amp on the operands torch.autocast delivers to the slow_attn slot, under the ten-stage block-causal mask: against torch's SDPA on half copies
+    with the mask in the half dtype, and seam.slow_attn on fp32 copies with the fp32 mask (all copies made once, outside the timed region).  The unmasked call of
+    the same operands gives the masked / unmasked ratio, printed beside the fraction of (128-query, 64-key) tiles the skip map leaves."""
+    L = sum(p * p for p in LADDER_256)
+    mask = block_causal(LADDER_256, dev)
+    for B, H, Lq, mixed in ((8, 16, L, True), (8, 16, L, False), (16, 16, L - 255, True)):
+        for dtype in (torch.float16, torch.bfloat16):
+            qkv = torch.randn(B, L, 3, H, 64, device=dev, generator=g)
+            qkv[:, :, 0] = F.normalize(qkv[:, :, 0], dim=-1) * 4
+            qkv[:, :, 1] = F.normalize(qkv[:, :, 1], dim=-1)
+            half = qkv.to(dtype)
+            fq, fk, fv = qkv.permute(2, 0, 3, 1, 4).unbind(0)
+            hq, hk, hv = half.permute(2, 0, 3, 1, 4).unbind(0)
+            fq, hq, m = fq[:, :, L - Lq:], hq[:, :, L - Lq:], mask[:, :, L - Lq:, :]
+            mh = m.to(dtype)
+            q, k = (fq, fk) if mixed else (hq, hk)
+            got = seam.slow_attn_amp(q, k, hv, 1.0, attn_mask=m)
+            diff = (got.float() - F.scaled_dot_product_attention(hq, hk, hv, attn_mask=mh, scale=1.0).float()).abs().max().item()
+            smap = next(e[1] for e in seam._SKIP_MAPS.values() if e[0].data_ptr() == m.data_ptr())
+            frac = 1.0 - smap.float().mean().item()
+            r = windows({"seam.slow_attn_amp": lambda: seam.slow_attn_amp(q, k, hv, 1.0, attn_mask=m),
+                         "seam.slow_attn_amp no mask": lambda: seam.slow_attn_amp(q, k, hv, 1.0),
+                         "torch SDPA same dtype, same mask": lambda: F.scaled_dot_product_attention(hq, hk, hv, attn_mask=mh, scale=1.0),
+                         "seam.slow_attn on fp32 copies": lambda: seam.slow_attn(fq, fk, fv, 1.0, attn_mask=m)}, a.iters, a.reps)
+            title = f"amp {str(dtype)[6:]} B{B} H{H} Lq{Lq} Lk{L} {'q/k fp32, v half' if mixed else 'all half'} (max |seam - torch| {diff:.1e})"
+            report(title, r, results, 4.0 * B * H * Lq * L * 64)
+            ratio = r["seam.slow_attn_amp"][0] / r["seam.slow_attn_amp no mask"][0]
+            print(f"    masked / unmasked time of seam.slow_attn_amp: {ratio:.3f}  (tiles visited: {frac:.3f})")
+            results[f"{title} | masked_to_unmasked_ratio"] = round(ratio, 4)
+            results[f"{title} | tiles_visited_fraction"] = round(frac, 4)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--rows", choices=("all", "fp32", "flash"), default="all", help="fp32: the slow_attn / fused_mlp_func rows; flash: the flash_attn_func rows")
+    ap.add_argument("--rows", choices=("all", "fp32", "flash", "amp"), default="all",
+                    help="fp32: the slow_attn / fused_mlp_func rows; flash: the flash_attn_func rows; amp: the slow_attn_amp rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("seam_bench: no GPU (there is nothing to time on a CPU)")
@@ -94,8 +131,8 @@ def main():
     dev, lib, results = torch.device("cuda:0"), E.load_library(), {}
     P = lambda t: C.c_void_p(t.data_ptr())
     g = torch.Generator(device=dev).manual_seed(0)
-    if a.rows == "flash":
-        flash_rows(a, dev, g, results)
+    if a.rows in ("flash", "amp"):
+        (flash_rows if a.rows == "flash" else amp_rows)(a, dev, g, results)
         print(json.dumps(results))
         return
 
@@ -160,6 +197,7 @@ def main():
     seam.configure(gemm_mode=E.DEFAULT_GEMM_MODE)
     if a.rows == "all":
         flash_rows(a, dev, g, results)
+        amp_rows(a, dev, g, results)
     print(json.dumps(results))
 
 
