@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU); 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
+#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse and sdvar_op_sdpa_bwd; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
 #define SDVAR_MAX_STAGES 16
 
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
@@ -287,6 +287,22 @@ int sdvar_op_sdpa(const float* q, const float* k, const float* v, float* out, co
  * bias_kind 1 / 2 as above; 3 = fp16 additive, 4 = bf16 additive (masked = -inf), for the half biases of sdvar_op_sdpa_hm. */
 int sdvar_op_sdpa_skip_map(const void* bias, int32_t bias_kind, const int64_t* bias_strides /*host*/, int32_t Bb, int32_t Hb, int32_t Lq, int32_t Lk, uint8_t* skip_map,
                            void* stream);
+/* sdvar_op_sdpa under autograd (the reference's trainer, trainer.py, runs loss.backward() through the teacher-forced slow_attn call of models/basic_var.py:117 with the
+ * mask of models/var.py:108-113).  sdvar_op_sdpa_lse = sdvar_op_sdpa (same arguments, same rules, `out` bit-identical) that also writes lse (device, (B, H, Lq) dense
+ * fp32): lse[b][h][i] = ln sum_j exp(scale q_i k_j + bias_ij), for every query row it stores; rows of other buffers are never touched.  A fully masked row: unspecified. */
+int sdvar_op_sdpa_lse(const float* q, const float* k, const float* v, float* out, float* lse, const int64_t* strides /*host, 12*/, const void* bias, int32_t bias_kind,
+                      const int64_t* bias_strides /*host*/, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale,
+                      void* stream);
+/* The backward of sdvar_op_sdpa_lse: with P = exp(scale q k^T + bias - lse) and D_i = sum_d dout_id out_id:  dv = P^T dout,  dS = P o (dout v^T - D),  dq = scale dS k,
+ * dk = scale dS^T q.  q, k, v, bias, bias_kind, bias_strides, skip_map, extents and scale exactly as given to the forward; out and lse as the forward wrote them; dout the
+ * gradient of out.  strides (host, 24 x int64, elements): (batch, head, token) of q, k, v, out, dout, dq, dk, dv; channel stride 1; the forward's alignment rule for every
+ * tensor that is given (pointer % 16 == 0, strides non-negative multiples of 4).  delta (device): workspace of B * H * Lq floats, receives D.  Any of dq, dk, dv may be
+ * NULL and is then not computed (its strides are ignored); with dk and dv both NULL the dK/dV kernel is not launched, with dq NULL the dQ kernel is not; all three NULL is
+ * an argument error.  fp32 arithmetic on the fp32 matrix cores, no score-sized matrix in memory, tiles the skip map marks are not visited (P = 0 there exactly).
+ * Deterministic (no atomics: repeats are bit-identical); no gradient for the bias; a fully masked query row has no defined gradient.  No host synchronisation. */
+int sdvar_op_sdpa_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse, float* delta /*workspace*/, float* dq, float* dk,
+                      float* dv, const int64_t* strides /*host, 24*/, const void* bias, int32_t bias_kind, const int64_t* bias_strides /*host*/, const uint8_t* skip_map,
+                      int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
 /* The reference's flash_attn_func slot (models/basic_var.py:23, called at :112-113 when KV caching is on and qkv is not fp32, :97-98): out = softmax(scale q k^T) v on
  * fp16 or bf16 operands (dtype 1 = fp16, 2 = bf16; q, k, v and out all of it), no bias.  head_dim must be 64; Lq and Lk are independent, any value >= 1.
  * strides as for sdvar_op_sdpa (host, 12 x int64, elements: (batch, head, token) of q, k, v, out; channel stride 1).  A 64-element row is 128 bytes and is moved with 16-byte

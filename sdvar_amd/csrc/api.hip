@@ -46,6 +46,11 @@ int attention_masked(const float* q, const void* kc, const void* vc, int fmt, co
 int attention_sdpa(const float* q, const float* k, const float* v, float* out, const long long* strides, const void* bias, int kind, const long long* bs,
                    const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, hipStream_t stream);
 int sdpa_skip_map(const void* bias, int kind, const long long* bs, int Bb, int Hb, int Lq, int Lk, uint8_t* map, hipStream_t stream);
+int attention_sdpa_lse(const float* q, const float* k, const float* v, float* out, float* lse, const long long* strides, const void* bias, int kind, const long long* bs,
+                       const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, hipStream_t stream);
+int attention_sdpa_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse, float* delta, float* dq, float* dk,
+                       float* dv, const long long* strides, const void* bias, int kind, const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk,
+                       int head_dim, float scale, hipStream_t stream);
 int attention_sdpa_h(const void* q, const void* k, const void* v, void* out, const long long* strides, int dtype, int B, int H, int Lq, int Lk, int head_dim, double scale,
                      hipStream_t stream);
 int attention_sdpa_hm(const void* q, const void* k, const void* v, void* out, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias, int kind,
@@ -934,6 +939,19 @@ int sdvar_op_sdpa(const float* q, const float* k, const float* v, float* out, co
 }
 int sdvar_op_sdpa_skip_map(const void* bias, int32_t bias_kind, const int64_t* bias_strides, int32_t Bb, int32_t Hb, int32_t Lq, int32_t Lk, uint8_t* skip_map, void* stream) {
     return sdpa_skip_map(bias, bias_kind, reinterpret_cast<const long long*>(bias_strides), Bb, Hb, Lq, Lk, skip_map, (hipStream_t)stream);
+}
+// the same slots under autograd (the reference's trainer runs loss.backward() through basic_var.py:117): forward with log-sum-exp, csrc/attention_sdpa.hip; backward,
+// csrc/attention_sdpa_bwd.hip
+int sdvar_op_sdpa_lse(const float* q, const float* k, const float* v, float* out, float* lse, const int64_t* strides, const void* bias, int32_t bias_kind,
+                      const int64_t* bias_strides, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream) {
+    return attention_sdpa_lse(q, k, v, out, lse, reinterpret_cast<const long long*>(strides), bias, bias_kind, reinterpret_cast<const long long*>(bias_strides), skip_map, B, H,
+                              Lq, Lk, head_dim, (float)scale, (hipStream_t)stream);
+}
+int sdvar_op_sdpa_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                      const int64_t* strides, const void* bias, int32_t bias_kind, const int64_t* bias_strides, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq,
+                      int32_t Lk, int32_t head_dim, double scale, void* stream) {
+    return attention_sdpa_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, reinterpret_cast<const long long*>(strides), bias, bias_kind,
+                              reinterpret_cast<const long long*>(bias_strides), skip_map, B, H, Lq, Lk, head_dim, (float)scale, (hipStream_t)stream);
 }
 // the reference's flash_attn_func slot (models/basic_var.py:23, 97-98, 112-113): csrc/attention_sdpa_h.hip
 int sdvar_op_sdpa_h(const void* q, const void* k, const void* v, void* out, const int64_t* strides, int32_t dtype, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim,

@@ -20,6 +20,8 @@
 // Every workgroup (128 queries of one batch and head) streams the K and V rows of the tiles it visits once: B*H*ceil(Lq/128) * visited tiles * 32 KiB.
 #include "common.h"
 
+#include <type_traits>
+
 namespace sdvar {
 
 namespace {
@@ -39,9 +41,14 @@ struct SdpaArgs {
     int B, H, Lq, Lk;
     float scale;
 };
+struct SdpaLseArgs : SdpaArgs {
+    float* lse;                                 // (B, H, Lq) dense, natural log
+};
 
-template <int BIAS>
-__global__ __launch_bounds__(256, 2) void attention_sdpa_kernel(SdpaArgs a) {
+// LSE: each stored query row also writes lse = m_run + ln(l_run), what the backward (attention_sdpa_bwd.hip) recomputes P from.  A compile-time flag with an
+// argument block of its own: the instantiations without it take the arguments they always took and are the kernels they were, instruction for instruction.
+template <int BIAS, bool LSE>
+__global__ __launch_bounds__(256, 2) void attention_sdpa_kernel(typename std::conditional<LSE, SdpaLseArgs, SdpaArgs>::type a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int STAGE = KT * KSTR + KT * 64;              // floats per pipeline stage: K tile then V tile
 
@@ -250,6 +257,9 @@ __global__ __launch_bounds__(256, 2) void attention_sdpa_kernel(SdpaArgs a) {
             *reinterpret_cast<f32x4*>(po + 8 * g) = v0;
             *reinterpret_cast<f32x4*>(po + 32 + 8 * g) = v1;
         }
+        if constexpr (LSE) {
+            if (lh == 0) a.lse[((long long)b * a.H + h) * a.Lq + qi_raw] = m_run + logf(l_run);          // both halves of a query hold the same m_run, l_run
+        }
     }
 }
 
@@ -298,10 +308,12 @@ int sdpa_skip_map(const void* bias, int kind, const long long* bs, int Bb, int H
     return SDVAR_OK;
 }
 
-// strides: 12 element strides, (batch, head, token) of q, k, v, out in that order
-int attention_sdpa(const float* q, const float* k, const float* v, float* out, const long long* strides, const void* bias, int kind, const long long* bs,
-                   const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, hipStream_t stream) {
+// strides: 12 element strides, (batch, head, token) of q, k, v, out in that order.  want_lse: the sdvar_op_sdpa_lse entry (lse must then be given).
+static int attention_sdpa_impl(const float* q, const float* k, const float* v, float* out, const long long* strides, const void* bias, int kind, const long long* bs,
+                               const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, bool want_lse, float* lse, hipStream_t stream) {
     SDVAR_CHECK_ARG(q && k && v && out && strides, "sdpa: null operand");
+    SDVAR_CHECK_ARG(!want_lse || lse, "sdpa: null lse");
+    SDVAR_CHECK_ARG(!want_lse || ((uintptr_t)lse & 3) == 0, "sdpa: lse is not 4-byte aligned");
     SDVAR_CHECK_ARG(head_dim == 64, "sdpa: head dim %d (only 64 is built)", head_dim);
     SDVAR_CHECK_ARG(B >= 1 && H >= 1 && Lq >= 1 && Lk >= 1 && B <= 65535 && H <= 65535, "sdpa: bad extents B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
     static const char* const names[4] = {"q", "k", "v", "out"};
@@ -315,22 +327,44 @@ int attention_sdpa(const float* q, const float* k, const float* v, float* out, c
     SDVAR_CHECK_ARG((kind == BIAS_NONE) == (bias == nullptr), "sdpa: bias pointer and bias kind %d disagree", kind);
     SDVAR_CHECK_ARG(kind == BIAS_NONE || (bs && bs[0] >= 0 && bs[1] >= 0 && bs[2] >= 0), "sdpa: bias strides missing or negative");
     SDVAR_CHECK_ARG(kind != BIAS_NONE || !skip, "sdpa: a skip map needs a bias");
-    SdpaArgs a;
+    SdpaLseArgs a;
     a.q = q; a.k = k; a.v = v; a.out = out;
     for (int i = 0; i < 3; ++i) { a.qs[i] = strides[i]; a.ks[i] = strides[3 + i]; a.vs[i] = strides[6 + i]; a.os[i] = strides[9 + i]; a.bs[i] = kind ? bs[i] : 0; }
     a.bias = bias; a.skip = skip; a.nkt = (Lk + KT - 1) / KT;
     const uintptr_t balign = kind == BIAS_F32 ? 15 : 3;
     a.bias_vec = kind != BIAS_NONE && ((uintptr_t)bias & balign) == 0 && bs[0] % 4 == 0 && bs[1] % 4 == 0 && bs[2] % 4 == 0;
-    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale = scale;
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.lse = want_lse ? lse : nullptr;
     const size_t lds = 2 * (size_t)(KT * KSTR + KT * 64) * sizeof(float);
-    static LdsOptIn opt_in;
-    SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)attention_sdpa_kernel<BIAS_NONE>, (const void*)attention_sdpa_kernel<BIAS_F32>, (const void*)attention_sdpa_kernel<BIAS_U8>);
     const dim3 grid((Lq + QB - 1) / QB, H, B);
-    if (kind == BIAS_F32) hipLaunchKernelGGL(attention_sdpa_kernel<BIAS_F32>, grid, dim3(256), lds, stream, a);
-    else if (kind == BIAS_U8) hipLaunchKernelGGL(attention_sdpa_kernel<BIAS_U8>, grid, dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(attention_sdpa_kernel<BIAS_NONE>, grid, dim3(256), lds, stream, a);
+    if (want_lse) {
+        static LdsOptIn opt_in_lse;
+        SDVAR_LDS_OPT_IN(opt_in_lse, lds, (const void*)attention_sdpa_kernel<BIAS_NONE, true>, (const void*)attention_sdpa_kernel<BIAS_F32, true>,
+                         (const void*)attention_sdpa_kernel<BIAS_U8, true>);
+        if (kind == BIAS_F32) hipLaunchKernelGGL((attention_sdpa_kernel<BIAS_F32, true>), grid, dim3(256), lds, stream, a);
+        else if (kind == BIAS_U8) hipLaunchKernelGGL((attention_sdpa_kernel<BIAS_U8, true>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((attention_sdpa_kernel<BIAS_NONE, true>), grid, dim3(256), lds, stream, a);
+        SDVAR_LAUNCH_CHECK();
+        return SDVAR_OK;
+    }
+    const SdpaArgs& p = a;
+    static LdsOptIn opt_in;
+    SDVAR_LDS_OPT_IN(opt_in, lds, (const void*)attention_sdpa_kernel<BIAS_NONE, false>, (const void*)attention_sdpa_kernel<BIAS_F32, false>,
+                     (const void*)attention_sdpa_kernel<BIAS_U8, false>);
+    if (kind == BIAS_F32) hipLaunchKernelGGL((attention_sdpa_kernel<BIAS_F32, false>), grid, dim3(256), lds, stream, p);
+    else if (kind == BIAS_U8) hipLaunchKernelGGL((attention_sdpa_kernel<BIAS_U8, false>), grid, dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL((attention_sdpa_kernel<BIAS_NONE, false>), grid, dim3(256), lds, stream, p);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
+}
+
+int attention_sdpa(const float* q, const float* k, const float* v, float* out, const long long* strides, const void* bias, int kind, const long long* bs,
+                   const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, hipStream_t stream) {
+    return attention_sdpa_impl(q, k, v, out, strides, bias, kind, bs, skip, B, H, Lq, Lk, head_dim, scale, false, nullptr, stream);
+}
+
+int attention_sdpa_lse(const float* q, const float* k, const float* v, float* out, float* lse, const long long* strides, const void* bias, int kind, const long long* bs,
+                       const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, float scale, hipStream_t stream) {
+    return attention_sdpa_impl(q, k, v, out, strides, bias, kind, bs, skip, B, H, Lq, Lk, head_dim, scale, true, lse, stream);
 }
 
 }  // namespace sdvar

@@ -122,6 +122,8 @@ _SIGNATURES = {
     "sdvar_op_quant_nearest": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     "sdvar_op_noise_fill": (_I, [_P, _I, _I, _I, _U64, _U32, _U32, _P]),
     "sdvar_op_sdpa": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int64), _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
+    "sdvar_op_sdpa_lse": (_I, [_P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
+    "sdvar_op_sdpa_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
     "sdvar_op_sdpa_skip_map": (_I, [_P, _I, C.POINTER(C.c_int64), _I, _I, _I, _I, _P, _P]),
     "sdvar_op_sdpa_h": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _D, _P]),
     "sdvar_op_sdpa_hm": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),

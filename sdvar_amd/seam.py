@@ -11,7 +11,10 @@ maintainer of the reference who wants the kernels without adopting the sampling 
 
     seam.install_amp(basic_var, model)      # a model run under torch.autocast: the two lines above + slow_attn_amp for the MASKED calls (half / mixed operands)
 
-Inference only: no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
+    seam.install_train(basic_var, model)    # fp32 TRAINING: slow_attn_grad (HIP forward + backward under autograd); the FFN goes back to the reference's own fc2(act(fc1(x)))
+
+Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward):
+no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
 `flash_attn_func` takes fp16 or bf16 operands only (and no mask); `slow_attn_amp` / `memory_efficient_attention_amp` take a half value with query and key each
 half or fp32, and masks.  Anything else raises SdvarError - there is no fall-back to torch.
 Torch is used for device memory and the current stream only; bool masks go to the kernel as bytes.
@@ -36,7 +39,7 @@ from . import engine as E
 from .engine import SdvarError
 
 __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
-           "enable_flash", "install_amp", "clear_caches"]
+           "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -174,6 +177,95 @@ def memory_efficient_attention(q, k, v, attn_bias=None, p: float = 0.0, scale: O
     if p and p > 0:
         raise SdvarError("memory_efficient_attention: p > 0 (dropout) is not supported (inference only)")
     return _sdpa("memory_efficient_attention", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
+
+
+class _SdpaGrad(torch.autograd.Function):
+    """softmax(scale q k^T + mask) v with a HIP backward: forward = sdvar_op_sdpa_lse, backward = one sdvar_op_sdpa_bwd call (csrc/attention_sdpa_bwd.hip)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, idx, scale, who):
+        ib, ih, it = idx
+        B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
+        mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, None)
+        q, k, v = (t if _rows_aligned(t) else t.contiguous() for t in (q, k, v))
+        out = torch.empty((B, Lq, H, 64), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+        strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
+        E._check(E.load_library().sdvar_op_sdpa_lse(_p(q), _p(k), _p(v), _p(out), _p(lse), strides, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale),
+                                                    E._stream()))
+        ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask, smap)))
+        ctx.sdpa = (idx, float(scale), kind, bstr, (B, H, Lq, Lk))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse, *rest = ctx.saved_tensors
+        mask, smap = rest if rest else (None, None)
+        idx, scale, kind, bstr, (B, H, Lq, Lk) = ctx.sdpa
+        # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address would come back as itself
+        if not _rows_aligned(dout):
+            dout = dout.clone(memory_format=torch.contiguous_format)
+        dq, dk, dv = (torch.empty((B, L, H, 64), dtype=torch.float32, device=q.device) if need else None
+                      for need, L in zip(ctx.needs_input_grad[:3], (Lq, Lk, Lk)))
+        if dq is None and dk is None and dv is None:
+            return (None,) * 7
+        delta = torch.empty(B * H * Lq, dtype=torch.float32, device=q.device)
+        blhc = lambda t: (0, 0, 0) if t is None else (t.stride(0), t.stride(2), t.stride(1))
+        strides = (C.c_int64 * 24)(*(t.stride(i) for t in (q, k, v) for i in idx), *blhc(out), *blhc(dout), *blhc(dq), *blhc(dk), *blhc(dv))
+        E._check(E.load_library().sdvar_op_sdpa_bwd(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), strides, _p(mask), kind, bstr,
+                                                    _p(smap), B, H, Lq, Lk, 64, scale, E._stream()))
+        if idx == (0, 1, 2):                # (B, H, L, 64) operands: views of the (B, L, H, 64) buffers
+            dq, dk, dv = (None if t is None else t.permute(0, 2, 1, 3) for t in (dq, dk, dv))
+        return dq, dk, dv, None, None, None, None
+
+
+def _sdpa_grad(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
+    """The differentiable attention slots.  idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
+    for name, t in (("query", q), ("key", k), ("value", v)):
+        if not isinstance(t, torch.Tensor):
+            raise SdvarError(f"{who}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+        if t.dtype in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported - the autocast slots (slow_attn_amp, flash_attn_func) have no backward yet")
+        if t.dtype != torch.float32:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
+        if t.dim() != 4:
+            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
+        if t.shape[-1] != 64:
+            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+    ib, ih, it = idx
+    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
+    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or Lq < 1 or Lk < 1:
+        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
+    if q.device != k.device or q.device != v.device:
+        raise SdvarError(f"{who}: operands live on different devices")
+    if isinstance(mask, torch.Tensor) and mask.requires_grad and torch.is_grad_enabled():
+        raise SdvarError(f"{who}: the mask requires grad; there is no gradient for the mask")
+    if not torch.is_grad_enabled() or not (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _sdpa(who, q, k, v, idx, scale, mask)            # what the inference twin launches: the same bits, no LSE
+    return _SdpaGrad.apply(q, k, v, mask, idx, scale, who)
+
+
+def slow_attn_grad(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
+    """slow_attn under autograd (the reference's trainer runs loss.backward() through basic_var.py:117): layouts, mask rules, alignment and copy-once rule and the returned
+    (B, H, Lq, 64) view as for slow_attn.  With grad mode off, or no operand requiring grad, it IS slow_attn (same launch, same bits).  Otherwise the forward also
+    writes the log-sum-exp rows (sdvar_op_sdpa_lse; the output bits do not change) and the backward is one sdvar_op_sdpa_bwd call on the fp32 matrix cores: no score
+    matrix in memory, masked tiles skipped, deterministic.  Gradients come back as (B, H, L, 64) views of fresh dense (B, L, H, 64) buffers; only those autograd asks
+    for are computed.  An upstream gradient that misses the alignment rule is copied once.  No dropout (the reference trains with attn_drop = 0), no gradient for the
+    mask, no double backward, float32 only."""
+    if dropout_p and dropout_p > 0:
+        raise SdvarError("slow_attn_grad: dropout_p > 0 is not supported (the reference trains with attn_drop = 0)")
+    return _sdpa_grad("slow_attn_grad", query, key, value, (0, 1, 2), scale, attn_mask).permute(0, 2, 1, 3)
+
+
+def memory_efficient_attention_grad(q, k, v, attn_bias=None, p: float = 0.0, scale: Optional[float] = None):
+    """memory_efficient_attention under autograd: q (B, Lq, H, 64), k / v (B, Lk, H, 64), attn_bias as for slow_attn_grad; returns (B, Lq, H, 64); gradients are dense
+    (B, L, H, 64).  The same kernels as slow_attn_grad with other strides."""
+    if p and p > 0:
+        raise SdvarError("memory_efficient_attention_grad: p > 0 (dropout) is not supported (the reference trains with attn_drop = 0)")
+    return _sdpa_grad("memory_efficient_attention_grad", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
 def _rows_aligned_h(t: torch.Tensor) -> bool:
@@ -398,3 +490,17 @@ def install_amp(module, model=None) -> None:
     install(module, model)
     enable_flash(module, model)
     module.slow_attn = slow_attn_amp
+
+
+def install_train(module, model=None) -> None:
+    """For TRAINING the reference in fp32 with the seam's attention: `module.slow_attn = slow_attn_grad`, and `module.fused_mlp_func = None` plus
+    `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
+    state it is in without flash-attn installed.  `memory_efficient_attention` is left alone for the reason install() documents; assign
+    seam.memory_efficient_attention_grad yourself before building the model if you want the BLHc route.  Not part of this: a backward for the FFN (fused_mlp_func) and
+    a half-precision (autocast) backward - flash_attn_func and the _amp slots still raise on operands that require grad."""
+    module.slow_attn = slow_attn_grad
+    module.fused_mlp_func = None
+    if model is not None:
+        for m in model.modules():
+            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
+                m.fused_mlp_func = None
