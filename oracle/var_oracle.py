@@ -248,9 +248,11 @@ def token_matches(ids: Tensor, cfg_logits: Tensor, rule: MatchRule, draft_cfg_lo
     if rule.rule == "topk":         # fewer than k vocabulary entries score strictly higher than the draft token
         xd = cfg_logits.gather(-1, ids.unsqueeze(-1))
         return (cfg_logits > xd).sum(-1) < rule.top_k
-    if rule.rule == "kl":           # KL(softmax target || softmax draft), evaluated in float64 from the float32 logits
+    if rule.rule == "kl":           # KL(softmax target || softmax draft), evaluated in float64 from the float32 logits, with 0 * log 0 = 0:
+        # an entry of target probability 0 (-inf in the top-k-masked logits) contributes nothing, whatever the draft holds there
         lt = cfg_logits.double().log_softmax(-1); ld = draft_cfg_logits.double().log_softmax(-1)
-        return (lt.exp() * (lt - ld)).sum(-1) <= float(np.float32(rule.kl_thr))
+        p = lt.exp()
+        return torch.where(p > 0, p * (lt - ld), torch.zeros_like(p)).sum(-1) <= float(np.float32(rule.kl_thr))
     raise ValueError(rule.rule)
 
 
@@ -270,10 +272,12 @@ def accept_scan_ex(draft_ids: List[Tensor], cfg_logits: List[Tensor], thr: float
     return n, matched, total, masks, corrected
 
 
-def gumbel_mix(masked_cfg_logits: Tensor, ratio: float, e: Tensor, codebook: Tensor) -> Tensor:
+def gumbel_mix(masked_cfg_logits: Tensor, ratio: float, e: Tensor, codebook: Tensor, tau: Optional[float] = None) -> Tensor:
     """var.py:206-208 + helpers.py:22-36 (rng given, hard=False): softmax((logits * (1 + ratio) + (-log E)) / tau) @ codebook -> (B, l, Cvae).
-    `masked_cfg_logits` are the logits after the sampler masked them in place (helpers.py:10,15); e ~ Exp(1), shape (B, l, V)."""
-    tau = max(0.27 * (1 - ratio * 0.95), 0.005)
+    `masked_cfg_logits` are the logits after the sampler masked them in place (helpers.py:10,15); e ~ Exp(1), shape (B, l, V).
+    tau: the reference's schedule of `ratio` unless given (tests reach its floor 0.005 at ratio <= 1 this way)."""
+    if tau is None:
+        tau = max(0.27 * (1 - ratio * 0.95), 0.005)
     gumbels = (masked_cfg_logits.mul(1 + ratio) + (-e.log())) / tau
     return gumbels.softmax(-1) @ codebook.unsqueeze(0)
 

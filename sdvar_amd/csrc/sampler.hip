@@ -9,7 +9,8 @@
 // Exactness notes (the ids must equal the reference's):
 //   * CFG is (1+t)*cond - t*uncond with two roundings then a subtraction, as torch evaluates it: no fma contraction.
 //   * top-k keeps ties at the k-th value (logits < kth are dropped); the k-th value comes from an exact radix select.
-//   * top-p follows helpers.py:12-15: ascending sort (bitonic, keys (value, index)), softmax of the sorted row,
+//   * top-p follows helpers.py:12-15: ascending sort (bitonic, keys (value, index): equal values - both zeros are one value - go by index,
+//     the lowest indices are removed first; torch's sort is not stable, so on ties only the number and the values kept equal the reference's), softmax of the sorted row,
 //     cumulative sum accumulated in double and rounded to float per element (ATen's CPU cumsum accumulates float in
 //     double), removed iff cumsum <= float(1 - top_p), last element always kept.
 //   * the draw is argmax(p / q), q ~ Exp(1): torch.multinomial's own formulation; q is either an explicit
@@ -28,6 +29,9 @@ __device__ __forceinline__ uint32_t f2key(float f) {
 __device__ __forceinline__ float key2f(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
+// key of the top-p sort: -0.0 and +0.0 are one value there (as in torch.sort's comparison), so zeros of either sign go by index like every other tie;
+// the logits themselves keep their bits
+__device__ __forceinline__ uint32_t sortkey(float f) { return f2key(f == 0.0f ? 0.0f : f); }
 
 // block-wide helpers over 256 threads (4 waves); `red` is LDS scratch of >= 8 doubles
 __device__ __forceinline__ float block_max(float v, float* red) {
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
 #pragma unroll
             for (int i = 0; i < VPT; ++i) {
                 const int v = 4 * (tid + 256 * (i >> 2)) + (i & 3);
-                if (x[i] > -INFINITY) sbuf[slot++] = ((unsigned long long)f2key(x[i]) << 32) | (unsigned)v;
+                if (x[i] > -INFINITY) sbuf[slot++] = ((unsigned long long)sortkey(x[i]) << 32) | (unsigned)v;
             }
             __syncthreads();
             for (int k = 2; k <= NC; k <<= 1) {
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
             const int v = 4 * (tid + 256 * (i >> 2)) + (i & 3);
-            sbuf[v] = (v < V) ? (((unsigned long long)f2key(x[i]) << 32) | (unsigned)v) : (unsigned long long)(unsigned)v;
+            sbuf[v] = (v < V) ? (((unsigned long long)sortkey(x[i]) << 32) | (unsigned)v) : (unsigned long long)(unsigned)v;
         }
         __syncthreads();
         for (int k = 2; k <= NV; k <<= 1) {
