@@ -303,6 +303,29 @@ int sdvar_op_sdpa_lse(const float* q, const float* k, const float* v, float* out
 int sdvar_op_sdpa_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse, float* delta /*workspace*/, float* dq, float* dk,
                       float* dv, const int64_t* strides /*host, 24*/, const void* bias, int32_t bias_kind, const int64_t* bias_strides /*host*/, const uint8_t* skip_map,
                       int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
+/* Operand producers of the FFN backward (models/basic_var.py:33-52 under autograd; sdvar_amd/seam.py fused_mlp_func_grad; csrc/mlp_bwd.hip).  `format` is the GEMM mode's
+ * operand format: 0 = plain fp32 row-major (sdvar_op_gemm), 2 = two K-blocked fp16 planes (sdvar_op_gemm_f16x2), 3 = three K-blocked bf16 planes (sdvar_op_gemm_bf16x3), with
+ * the arithmetic of sdvar_op_split_planes_f16 / sdvar_op_split_planes.  Plane strides are in elements, multiples of 8; every pointer 16-byte aligned.  Added without an ABI
+ * bump (purely additive).
+ * sdvar_op_transpose_operand: x fp32 (rows, cols) with leading dimension ldx (cols % 8 == 0, ldx % 4 == 0) -> the operand of x^T: (cols x Kp), Kp = rows rounded up to 32;
+ * format 0: out = float[cols][Kp]; 2 / 3: planes with element (c, k) at ((k/32)*cols + c)*32 + k%32, plane_stride >= cols * Kp.  The tail k >= rows is written as zeros by
+ * this kernel in every plane.  scale (format 2 only, may be NULL): device float multiplied into x before the split (element 0 of a scale quadruple). */
+int sdvar_op_transpose_operand(const float* x, int32_t ldx, int32_t rows, int32_t cols, int32_t format, void* out, uint64_t plane_stride, const float* scale, void* stream);
+/* pre fp32 (M, N) dense, N % 32 == 0 -> the row-major operand of gelu_tanh(pre): format 0 float[M][N], else planes of (M x N).  gelu_kind: 0 = the tanhf form of
+ * sdvar_op_gemm / sdvar_op_gemm_bf16x3's epilogue 1, 1 = the exp / rcp form of sdvar_op_gemm_f16x2's - the result has the bits that epilogue writes. */
+int sdvar_op_gelu_operand(const float* pre, int32_t M, int32_t N, int32_t format, int32_t gelu_kind, void* out, uint64_t plane_stride, void* stream);
+/* dh, pre fp32 (M, N) dense, N % 32 == 0, read once: dpre = dh * gelu_tanh'(pre), h = gelu_tanh(pre) (gelu_kind as above; the derivative is 0 / 1 and finite at large |pre|).
+ * Outputs, each may be NULL: dpre = row-major operand (M x N); dpre_t, h_t = transposed operands (N x Mp), Mp = M rounded up to 32, zero tail written here;
+ * colsum_part = float[Mp/32][N], the column sums of dpre over each block of 32 rows (finish with sdvar_op_colsum).  scale (format 2 only, may be NULL): device
+ * {2^S, 2^-S}; the dpre operands hold dpre * 2^S, h_t and colsum_part are unscaled.  dh may be NULL when only h_t is asked for. */
+int sdvar_op_gelu_bwd(const float* dh, const float* pre, int32_t M, int32_t N, int32_t format, int32_t gelu_kind, const float* scale, void* dpre, uint64_t dpre_plane_stride,
+                      void* dpre_t, uint64_t dpre_t_plane_stride, void* h_t, uint64_t h_t_plane_stride, float* colsum_part, void* stream);
+/* out[n] = sum_m x[m][n], x fp32 (M, N) with leading dimension ldx (N % 4 == 0, ldx % 4 == 0): double accumulation in a fixed order, no atomics (repeats are bit-identical) */
+int sdvar_op_colsum(const float* x, int32_t ldx, int32_t M, int32_t N, float* out, void* stream);
+/* The scale quadruple {2^S, 2^-S, scratch, 2^-S * other[1]} of an f16x2 operand (4 device floats).  x != NULL: S from max|x| over n values as sdvar_op_split_planes_f16
+ * chooses it (all-zero x: S = 0); x == NULL: scale[0..1] are kept.  halve: S -= 1.  scale[3] = 2^-S * (other ? other[1] : 1) is what a GEMM whose two operands are both
+ * scaled must undo: hand it `scale + 2` as w_scale. */
+int sdvar_op_scale_pair(const float* x, uint64_t n, float* scale, int32_t halve, const float* other, void* stream);
 /* The reference's flash_attn_func slot (models/basic_var.py:23, called at :112-113 when KV caching is on and qkv is not fp32, :97-98): out = softmax(scale q k^T) v on
  * fp16 or bf16 operands (dtype 1 = fp16, 2 = bf16; q, k, v and out all of it), no bias.  head_dim must be 64; Lq and Lk are independent, any value >= 1.
  * strides as for sdvar_op_sdpa (host, 12 x int64, elements: (batch, head, token) of q, k, v, out; channel stride 1).  A 64-element row is 128 bytes and is moved with 16-byte

@@ -140,6 +140,25 @@ __device__ __forceinline__ void split4h_pk(const float* v, uint2& h, uint2& l) {
     split2h_pk_raw(c[0], c[1], h.x, l.x); split2h_pk_raw(c[2], c[3], h.y, l.y);
 }
 
+// ---- GELU(tanh), the two forms of the GEMM epilogues (gemm.hip / gemm_bf16x3.hip: gelu_tanh; gemm_f16x2.hip: gelu_tanh_h) - here so that the FFN backward's
+// producers (mlp_bwd.hip) recompute the forward's h bit for bit
+__device__ __forceinline__ float gelu_tanh(float x) {
+    // 0.5 x (1 + tanh( sqrt(2/pi) (x + 0.044715 x^3) ))   (nn.GELU(approximate='tanh'))
+    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
+    const float inner = k0 * (x + k1 * x * x * x);
+    return 0.5f * x * (1.0f + tanhf(inner));
+}
+// GELU(tanh) (basic_var.py:40): 0.5 x (1 + tanh(u)) = x sigmoid(2u) = x / (1 + 2^(-2u log2 e)) with v_exp_f32 and v_rcp_f32 (1 ulp each, ~2e-7
+// relative on the result): libm's tanhf costs ~40 vector instructions per value and the epilogue of a 256 x 128 tile evaluates 64 of them per lane
+// with nothing to hide them under (12 us per round of workgroups at M = 4096, fc1)
+__device__ __forceinline__ float gelu_tanh_h(float x) {
+    // -2 u log2 e = x (C0 + C1 x^2), C0 = -2 log2(e) sqrt(2 / pi), C1 = 0.044715 C0: 7 vector instructions (mul, fma, mul, exp2, add, rcp, mul)
+    const float C0 = -2.3022081986f, C1 = -0.10294324f;
+    const float w = x * __builtin_fmaf(x * x, C1, C0);
+    const float e = __builtin_amdgcn_exp2f(w);                               // exp(-2u); +inf for very negative x: the quotient is then 0
+    return x * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
 // Output-plane format of the producers of GEMM operands (ln_modulate, attention, GELU epilogues): none, three bf16 planes, two fp16 planes
 enum { PLANES_NONE = 0, PLANES_F16X2 = 2, PLANES_BF16X3 = 3 };
 // four consecutive values of one row -> the packed 8-byte words of each plane, written at the K-blocked position

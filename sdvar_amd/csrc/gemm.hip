@@ -31,13 +31,6 @@ enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_GATED_RES = 2, EPI_PARTIAL = 3 };
 constexpr int BK = 32;
 constexpr int LDS_STRIDE = BK + 4;   // floats
 
-__device__ __forceinline__ float gelu_tanh(float x) {
-    // 0.5 x (1 + tanh( sqrt(2/pi) (x + 0.044715 x^3) ))   (nn.GELU(approximate='tanh'))
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    const float inner = k0 * (x + k1 * x * x * x);
-    return 0.5f * x * (1.0f + tanhf(inner));
-}
-
 struct GemmArgs {
     const float* X; const float* W; const float* bias; float* out;
     const float* res; const float* gate;

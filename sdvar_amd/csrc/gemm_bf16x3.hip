@@ -29,10 +29,7 @@ constexpr int PBK = 32;             // k per LDS stage
 constexpr int PROW = 40;            // padded row, in bf16 elements (80 bytes)
 constexpr int PBN = 128;
 
-__device__ __forceinline__ float gelu_tanh_p(float x) {
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    return 0.5f * x * (1.0f + tanhf(k0 * (x + k1 * x * x * x)));
-}
+__device__ __forceinline__ float gelu_tanh_p(float x) { return gelu_tanh(x); }          // common.h
 
 struct GemmPArgs {
     const uint16_t* X; const uint16_t* W;        // K-blocked planes [3][K/32][M][32], [3][K/32][N][32]

@@ -43,17 +43,6 @@ enum { HEPI_BIAS = 0, HEPI_BIAS_GELU_PLANES = 1, HEPI_GATED_RES = 2, HEPI_PARTIA
 constexpr int HBK = 32;             // k per LDS stage
 constexpr int HBN = 128;
 
-// GELU(tanh) (basic_var.py:40): 0.5 x (1 + tanh(u)) = x sigmoid(2u) = x / (1 + 2^(-2u log2 e)) with v_exp_f32 and v_rcp_f32 (1 ulp each, ~2e-7
-// relative on the result): libm's tanhf costs ~40 vector instructions per value and the epilogue of a 256 x 128 tile evaluates 64 of them per lane
-// with nothing to hide them under (12 us per round of workgroups at M = 4096, fc1)
-__device__ __forceinline__ float gelu_tanh_h(float x) {
-    // -2 u log2 e = x (C0 + C1 x^2), C0 = -2 log2(e) sqrt(2 / pi), C1 = 0.044715 C0: 7 vector instructions (mul, fma, mul, exp2, add, rcp, mul)
-    const float C0 = -2.3022081986f, C1 = -0.10294324f;
-    const float w = x * __builtin_fmaf(x * x, C1, C0);
-    const float e = __builtin_amdgcn_exp2f(w);                               // exp(-2u); +inf for very negative x: the quotient is then 0
-    return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
 // HEPI_QKV (the unsplit QKV launch of a transformer block, N = 3 H 64): the q and k thirds leave the epilogue finished - bias, per-head L2 norm, q scale
 // (basic_var.py:101-109), q as fp32 (R, H, l, 64), k and v as planes of the KV cache at positions pos0 + t (both row-major [position][64]: the attention kernel
 // takes V^T fragments with ds_read_b64_tr_b16, so no transposed copy exists).  Nothing goes to `out`: the launch replaces qk_norm_append altogether

@@ -124,6 +124,11 @@ _SIGNATURES = {
     "sdvar_op_sdpa": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int64), _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
     "sdvar_op_sdpa_lse": (_I, [_P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
     "sdvar_op_sdpa_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
+    "sdvar_op_transpose_operand": (_I, [_P, _I, _I, _I, _I, _P, _U64, _P, _P]),
+    "sdvar_op_gelu_operand": (_I, [_P, _I, _I, _I, _I, _P, _U64, _P]),
+    "sdvar_op_gelu_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _U64, _P, _U64, _P, _U64, _P, _P]),
+    "sdvar_op_colsum": (_I, [_P, _I, _I, _I, _P, _P]),
+    "sdvar_op_scale_pair": (_I, [_P, _U64, _P, _I, _P, _P]),
     "sdvar_op_sdpa_skip_map": (_I, [_P, _I, C.POINTER(C.c_int64), _I, _I, _I, _I, _P, _P]),
     "sdvar_op_sdpa_h": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _D, _P]),
     "sdvar_op_sdpa_hm": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),

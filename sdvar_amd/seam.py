@@ -12,8 +12,10 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install_amp(basic_var, model)      # a model run under torch.autocast: the two lines above + slow_attn_amp for the MASKED calls (half / mixed operands)
 
     seam.install_train(basic_var, model)    # fp32 TRAINING: slow_attn_grad (HIP forward + backward under autograd); the FFN goes back to the reference's own fc2(act(fc1(x)))
+    seam.install_train(basic_var, model, ffn=True)      # ... and fused_mlp_func_grad: the FFN's forward and backward on HIP too
 
-Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward):
+Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward) and
+fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward):
 no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
 `flash_attn_func` takes fp16 or bf16 operands only (and no mask); `slow_attn_amp` / `memory_efficient_attention_amp` take a half value with query and key each
 half or fp32, and masks.  Anything else raises SdvarError - there is no fall-back to torch.
@@ -39,14 +41,16 @@ from . import engine as E
 from .engine import SdvarError
 
 __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
-           "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train"]
+           "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
+           "fused_mlp_func_grad"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
 # a key can never describe two different masks.  Small on purpose: a model has a handful of masks (teacher forcing: one; the hand-off sampler: five).
 _SKIP_MAPS: "OrderedDict[tuple, tuple]" = OrderedDict()
 _SKIP_MAPS_MAX = 8
-# (mode, data_ptr, _version, shape) -> (weight, planes, scale): GEMM operand planes of a weight (none in mode f32).  A d30 model has 60 FFN weights.
+# (kind, mode, data_ptr, shape) -> (weight, _version, planes, scale): GEMM operand planes of a weight ("n": as stored, none in mode f32; "t": of its transpose, for the
+# backward).  A weight updated in place replaces its own entry.  A d30 model has 60 FFN weights.
 _WEIGHT_PLANES: "OrderedDict[tuple, tuple]" = OrderedDict()
 _WEIGHT_PLANES_MAX = 256
 
@@ -391,33 +395,67 @@ def memory_efficient_attention_amp(q, k, v, attn_bias=None, p: float = 0.0, scal
     return _sdpa_amp("memory_efficient_attention_amp", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
-def _weight_planes(w: torch.Tensor, mode: str):
-    key = (mode, w.data_ptr(), w._version, tuple(w.shape))
+def _cached_planes(kind: str, w: torch.Tensor, mode: str, make):
+    """One entry per (kind, mode, weight): an entry whose weight has been updated in place since (its _version moved - every step of a training loop) is REPLACED,
+    so a loop strands no stale plane sets."""
+    key = (kind, mode, w.data_ptr(), tuple(w.shape))
     hit = _WEIGHT_PLANES.get(key)
-    if hit is not None:
+    if hit is not None and hit[1] == w._version:
         _WEIGHT_PLANES.move_to_end(key)
-        return hit[1], hit[2]
-    lib = E.load_library()
-    N, K = w.shape
-    wc = w.detach().contiguous()
-    if mode == "f16x2":
-        planes, sc = torch.empty(2, N * K, dtype=torch.int16, device=w.device), torch.zeros(4, dtype=torch.float32, device=w.device)
-        E._check(lib.sdvar_op_split_planes_f16(_p(wc), _p(planes), N, K, N * K, _p(sc), E._stream()))
-    else:
-        planes, sc = torch.empty(3, N * K, dtype=torch.int16, device=w.device), None
-        E._check(lib.sdvar_op_split_planes(_p(wc), _p(planes), N, K, N * K, E._stream()))
-    _WEIGHT_PLANES[key] = (w, planes, sc)
+        return hit[2], hit[3]
+    planes, sc = make()
+    _WEIGHT_PLANES[key] = (w, w._version, planes, sc)
+    _WEIGHT_PLANES.move_to_end(key)
     while len(_WEIGHT_PLANES) > _WEIGHT_PLANES_MAX:
         _WEIGHT_PLANES.popitem(last=False)
     return planes, sc
 
 
-def fused_mlp_func(x, weight1, weight2, bias1=None, bias2=None, activation: str = "gelu_approx", save_pre_act: bool = False, return_residual: bool = False,
-                   checkpoint_lvl: int = 0, heuristic=0, process_group=None):
-    """The `fused_mlp_func` slot (flash_attn.ops.fused_dense signature; basic_var.py:46-50): fc2(gelu_tanh(fc1(x))), x (..., C) fp32 on the GPU, weight1 (hidden, C),
-    weight2 (out, hidden).  Two launches of the operator GEMMs of the configured mode (seam.configure): fc1 with the GELU epilogue writing the operand planes of fc2
-    directly.  C and hidden must be multiples of 32.  save_pre_act / checkpoint_lvl / heuristic only matter to a backward and are ignored."""
-    who = "fused_mlp_func"
+def _weight_planes(w: torch.Tensor, mode: str):
+    def make():
+        lib = E.load_library()
+        N, K = w.shape
+        wc = w.detach().contiguous()
+        if mode == "f16x2":
+            planes, sc = torch.empty(2, N * K, dtype=torch.int16, device=w.device), torch.zeros(4, dtype=torch.float32, device=w.device)
+            E._check(lib.sdvar_op_split_planes_f16(_p(wc), _p(planes), N, K, N * K, _p(sc), E._stream()))
+        else:
+            planes, sc = torch.empty(3, N * K, dtype=torch.int16, device=w.device), None
+            E._check(lib.sdvar_op_split_planes(_p(wc), _p(planes), N, K, N * K, E._stream()))
+        return planes, sc
+    return _cached_planes("n", w, mode, make)
+
+
+_OPERAND_FORMAT = {"f32": 0, "f16x2": 2, "bf16x3": 3}       # csrc/mlp_bwd.hip
+_OPERAND_PLANES = {"f32": 1, "f16x2": 2, "bf16x3": 3}
+
+
+def _pad32(n: int) -> int:
+    return (n + 31) // 32 * 32
+
+
+def _transposed_operand(t: torch.Tensor, mode: str, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The GEMM operand of t^T for a dense, 16-byte aligned fp32 (rows, cols) tensor: (cols x pad32(rows)), fp32 in mode f32, else K-blocked planes; the kernel
+    writes the zero tail."""
+    rows, cols = t.shape
+    n = cols * _pad32(rows)
+    out = torch.empty(_OPERAND_PLANES[mode], n, dtype=torch.float32 if mode == "f32" else torch.int16, device=t.device)
+    E._check(E.load_library().sdvar_op_transpose_operand(_p(t), t.stride(0), rows, cols, _OPERAND_FORMAT[mode], _p(out), n, _p(scale), E._stream()))
+    return out
+
+
+def _weight_planes_t(w: torch.Tensor, mode: str):
+    """(operand of w^T, scale): the dgrad GEMMs' weight operand, cached like the forward's.  In mode f16x2 it carries the forward planes' scale."""
+    def make():
+        sc = _weight_planes(w, mode)[1] if mode == "f16x2" else None
+        wc = w.detach().contiguous()
+        if wc.data_ptr() % 16:
+            wc = wc.clone()
+        return _transposed_operand(wc, mode, sc), sc
+    return _cached_planes("t", w, mode, make)
+
+
+def _mlp_check(who: str, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, grad: bool):
     if activation != "gelu_approx":
         raise SdvarError(f"{who}: activation {activation!r}; only 'gelu_approx' (tanh GELU) is built")
     if return_residual:
@@ -425,39 +463,200 @@ def fused_mlp_func(x, weight1, weight2, bias1=None, bias2=None, activation: str 
     if process_group is not None:
         raise SdvarError(f"{who}: a process group (tensor-parallel MLP) is not supported")
     for name, t in (("x", x), ("weight1", weight1), ("weight2", weight2)) + tuple((n, b) for n, b in (("bias1", bias1), ("bias2", bias2)) if b is not None):
-        _check_operand(name, t, who)
+        if grad:
+            if not isinstance(t, torch.Tensor):
+                raise SdvarError(f"{who}: {name} is not a tensor")
+            if not t.is_cuda:
+                raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+            if t.dtype != torch.float32:
+                raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
+        else:
+            _check_operand(name, t, who)
     if weight1.dim() != 2 or weight2.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight1.shape[1] or weight2.shape[1] != weight1.shape[0]:
         raise SdvarError(f"{who}: shapes do not chain: x {tuple(x.shape)}, weight1 {tuple(weight1.shape)}, weight2 {tuple(weight2.shape)}")
     Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
     if Cin % 32 or hid % 32:
         raise SdvarError(f"{who}: in_features {Cin} and hidden_features {hid} must be multiples of 32")
-    lib, st, mode = E.load_library(), E._stream(), _gemm_mode
+    for name, b, n in (("bias1", bias1, hid), ("bias2", bias2, Cout)):
+        if grad and b is not None and tuple(b.shape) != (n,):
+            raise SdvarError(f"{who}: {name} has shape {tuple(b.shape)}, expected ({n},)")
+    return Cin, hid, Cout
+
+
+def _mlp_forward(x, weight1, weight2, bias1, bias2, mode: str, keep_pre: bool):
+    """(out, xr, pre).  keep_pre False: the inference launches (fc1 with the GELU epilogue).  True: fc1 with the bias epilogue leaves pre (M, hid) in memory and
+    sdvar_op_gelu_operand writes what the GELU epilogue would have - the same bits, so `out` is the same in both."""
+    Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
+    lib, st = E.load_library(), E._stream()
     xr = x.detach().reshape(-1, Cin).contiguous()
     M = xr.shape[0]
     out = torch.empty(tuple(x.shape[:-1]) + (Cout,), dtype=torch.float32, device=x.device)
     if M == 0:
-        return out
+        return out, xr, None
     b1 = torch.zeros(hid, dtype=torch.float32, device=x.device) if bias1 is None else bias1.detach().contiguous()
     b2 = torch.zeros(Cout, dtype=torch.float32, device=x.device) if bias2 is None else bias2.detach().contiguous()
+    pre = torch.empty(M, hid, dtype=torch.float32, device=x.device) if keep_pre else None
+    fmt = _OPERAND_FORMAT[mode]
     if mode == "f32":
         w1, w2 = weight1.detach().contiguous(), weight2.detach().contiguous()
         h = torch.empty(M, hid, dtype=torch.float32, device=x.device)
-        E._check(lib.sdvar_op_gemm(_p(xr), Cin, _p(w1), _p(b1), _p(h), hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
+        if keep_pre:
+            E._check(lib.sdvar_op_gemm(_p(xr), Cin, _p(w1), _p(b1), _p(pre), hid, M, hid, Cin, 0, None, 0, None, 1, 0, st))
+            E._check(lib.sdvar_op_gelu_operand(_p(pre), M, hid, fmt, 0, _p(h), 0, st))
+        else:
+            E._check(lib.sdvar_op_gemm(_p(xr), Cin, _p(w1), _p(b1), _p(h), hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
         E._check(lib.sdvar_op_gemm(_p(h), hid, _p(w2), _p(b2), _p(out), Cout, M, Cout, hid, 0, None, 0, None, 1, 0, st))
-        return out
+        return out, xr, pre
     (w1p, s1), (w2p, s2) = _weight_planes(weight1, mode), _weight_planes(weight2, mode)
     npl = 2 if mode == "f16x2" else 3
     xp = torch.empty(npl, M * Cin, dtype=torch.int16, device=x.device)
     hp = torch.empty(npl, M * hid, dtype=torch.int16, device=x.device)
     if mode == "f16x2":
         E._check(lib.sdvar_op_split_planes_f16(_p(xr), _p(xp), M, Cin, M * Cin, None, st))
-        E._check(lib.sdvar_op_gemm_f16x2(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(s1), _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
+        if keep_pre:
+            E._check(lib.sdvar_op_gemm_f16x2(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(s1), _p(b1), _p(pre), hid, None, 0, M, hid, Cin, 0, None, 0, None, 1, 0, st))
+            E._check(lib.sdvar_op_gelu_operand(_p(pre), M, hid, fmt, 1, _p(hp), M * hid, st))
+        else:
+            E._check(lib.sdvar_op_gemm_f16x2(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(s1), _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
         E._check(lib.sdvar_op_gemm_f16x2(_p(hp), M * hid, _p(w2p), Cout * hid, _p(s2), _p(b2), _p(out), Cout, None, 0, M, Cout, hid, 0, None, 0, None, 1, 0, st))
     else:
         E._check(lib.sdvar_op_split_planes(_p(xr), _p(xp), M, Cin, M * Cin, st))
-        E._check(lib.sdvar_op_gemm_bf16x3(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
+        if keep_pre:
+            E._check(lib.sdvar_op_gemm_bf16x3(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(b1), _p(pre), hid, None, 0, M, hid, Cin, 0, None, 0, None, 1, 0, st))
+            E._check(lib.sdvar_op_gelu_operand(_p(pre), M, hid, fmt, 0, _p(hp), M * hid, st))
+        else:
+            E._check(lib.sdvar_op_gemm_bf16x3(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
         E._check(lib.sdvar_op_gemm_bf16x3(_p(hp), M * hid, _p(w2p), Cout * hid, _p(b2), _p(out), Cout, None, 0, M, Cout, hid, 0, None, 0, None, 1, 0, st))
-    return out
+    return out, xr, pre
+
+
+def fused_mlp_func(x, weight1, weight2, bias1=None, bias2=None, activation: str = "gelu_approx", save_pre_act: bool = False, return_residual: bool = False,
+                   checkpoint_lvl: int = 0, heuristic=0, process_group=None):
+    """The `fused_mlp_func` slot (flash_attn.ops.fused_dense signature; basic_var.py:46-50): fc2(gelu_tanh(fc1(x))), x (..., C) fp32 on the GPU, weight1 (hidden, C),
+    weight2 (out, hidden).  Two launches of the operator GEMMs of the configured mode (seam.configure): fc1 with the GELU epilogue writing the operand planes of fc2
+    directly.  C and hidden must be multiples of 32.  save_pre_act / checkpoint_lvl / heuristic only matter to a backward and are ignored."""
+    _mlp_check("fused_mlp_func", x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, False)
+    return _mlp_forward(x, weight1, weight2, bias1, bias2, _gemm_mode, False)[0]
+
+
+def _gemm_nt(mode: str, A, B, wscale, out, M: int, N: int, K: int) -> None:
+    """out (M, N) fp32 = A (M x K) . B (N x K)^T on operands of `mode` (fp32 dense, or K-blocked planes); wscale: the f16x2 GEMM's device scale pointer or None."""
+    lib, st = E.load_library(), E._stream()
+    if mode == "f32":
+        E._check(lib.sdvar_op_gemm(_p(A), K, _p(B), None, _p(out), N, M, N, K, 0, None, 0, None, 1, 0, st))
+    elif mode == "f16x2":
+        E._check(lib.sdvar_op_gemm_f16x2(_p(A), M * K, _p(B), N * K, wscale, None, _p(out), N, None, 0, M, N, K, 0, None, 0, None, 1, 0, st))
+    else:
+        E._check(lib.sdvar_op_gemm_bf16x3(_p(A), M * K, _p(B), N * K, None, _p(out), N, None, 0, M, N, K, 0, None, 0, None, 1, 0, st))
+
+
+class _MlpGrad(torch.autograd.Function):
+    """fc2(gelu_tanh(fc1(x))) with a HIP backward: four NT GEMMs of the forward's mode on operands produced by csrc/mlp_bwd.hip.  Saved: x, the weights and pre."""
+
+    @staticmethod
+    def forward(ctx, x, weight1, weight2, bias1, bias2, mode):
+        out, xr, pre = _mlp_forward(x, weight1, weight2, bias1, bias2, mode, True)
+        ctx.save_for_backward(xr, weight1, weight2, pre)
+        ctx.mlp = (mode, tuple(x.shape))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        xr, weight1, weight2, pre = ctx.saved_tensors
+        mode, xshape = ctx.mlp
+        nx, nw1, nw2, nb1, nb2 = ctx.needs_input_grad[:5]
+        Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
+        M, dev = xr.shape[0], xr.device
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        if M == 0:
+            z = lambda need, *shape: torch.zeros(*shape, dtype=torch.float32, device=dev) if need else None
+            return z(nx, *xshape), z(nw1, hid, Cin), z(nw2, Cout, hid), z(nb1, hid), z(nb2, Cout), None
+        lib, st, fmt, npl, Mp = E.load_library(), E._stream(), _OPERAND_FORMAT[mode], _OPERAND_PLANES[mode], _pad32(M)
+        kind, h16, el = int(mode == "f16x2"), mode == "f16x2", torch.float32 if mode == "f32" else torch.int16
+        operand = lambda n: torch.empty(npl, n, dtype=el, device=dev)
+        dy = dy.reshape(M, Cout)
+        if not dy.is_contiguous() or dy.data_ptr() % 16:      # stride-0 expansions, transposed consumers, a dense tensor at a misaligned address: one fresh dense copy
+            dy = dy.clone(memory_format=torch.contiguous_format)
+        if xr.data_ptr() % 16:
+            xr = xr.clone()
+        need_dh = nx or nw1 or nb1
+        dx = dw1 = dw2 = db1 = db2 = None
+        if nb2:
+            db2 = f32(Cout)
+            E._check(lib.sdvar_op_colsum(_p(dy), Cout, M, Cout, _p(db2), st))
+        # f16x2: the gradient operands carry a per-tensor power-of-two scale (gradients of an fp32 run sit far below the range the unscaled split resolves)
+        sdy = torch.zeros(4, dtype=torch.float32, device=dev) if h16 and (need_dh or nw2) else None
+        sdp = torch.zeros(4, dtype=torch.float32, device=dev) if h16 and need_dh else None
+        off = lambda sc, floats: None if sc is None else C.c_void_p(sc.data_ptr() + 4 * floats)
+        dpre = dpre_t = h_t = part = None
+        if need_dh:
+            w2t, s2 = _weight_planes_t(weight2, mode)
+            if mode == "f32":
+                dyo = dy
+            elif h16:
+                dyo = operand(M * Cout)
+                E._check(lib.sdvar_op_split_planes_f16(_p(dy), _p(dyo), M, Cout, M * Cout, _p(sdy), st))
+                E._check(lib.sdvar_op_scale_pair(None, 0, _p(sdy), 0, _p(s2), st))
+            else:
+                dyo = operand(M * Cout)
+                E._check(lib.sdvar_op_split_planes(_p(dy), _p(dyo), M, Cout, M * Cout, st))
+            dh = f32(M, hid)
+            _gemm_nt(mode, dyo, w2t, off(sdy, 2), dh, M, hid, Cout)
+            if h16:          # |gelu'| <= 1.13: half of dh's scale keeps dpre inside the range without a second pass
+                E._check(lib.sdvar_op_scale_pair(_p(dh), M * hid, _p(sdp), 1, _p(_weight_planes(weight1, mode)[1]) if nx else None, st))
+            if nx:
+                dpre = operand(M * hid)
+            if nw1:
+                dpre_t = operand(hid * Mp)
+            if nb1:
+                part = f32(Mp // 32, hid)
+        else:
+            dh = None
+            if h16 and nw2:
+                E._check(lib.sdvar_op_scale_pair(_p(dy), M * Cout, _p(sdy), 0, None, st))
+        if nw2:
+            h_t = operand(hid * Mp)
+        if need_dh or nw2:
+            E._check(lib.sdvar_op_gelu_bwd(_p(dh), _p(pre), M, hid, fmt, kind, _p(sdp), _p(dpre), M * hid, _p(dpre_t), hid * Mp, _p(h_t), hid * Mp, _p(part), st))
+        if nx:
+            w1t, _ = _weight_planes_t(weight1, mode)
+            dx = f32(M, Cin)
+            _gemm_nt(mode, dpre, w1t, off(sdp, 2), dx, M, Cin, hid)
+            dx = dx.view(xshape)
+        if nw2:
+            dw2 = f32(Cout, hid)
+            _gemm_nt(mode, _transposed_operand(dy, mode, sdy), h_t, off(sdy, 0), dw2, Cout, hid, Mp)
+        if nw1:
+            dw1 = f32(hid, Cin)
+            _gemm_nt(mode, dpre_t, _transposed_operand(xr, mode), off(sdp, 0), dw1, hid, Cin, Mp)
+        if nb1:
+            db1 = f32(hid)
+            E._check(lib.sdvar_op_colsum(_p(part), hid, Mp // 32, hid, _p(db1), st))
+        return dx, dw1, dw2, db1, db2, None
+
+
+def fused_mlp_func_grad(x, weight1, weight2, bias1=None, bias2=None, activation: str = "gelu_approx", save_pre_act: bool = False, return_residual: bool = False,
+                        checkpoint_lvl: int = 0, heuristic=0, process_group=None):
+    """fused_mlp_func under autograd (the reference's trainer runs loss.backward() through basic_var.py:46-50): signature, operand rules and argument errors as
+    fused_mlp_func, plus out_features % 32 == 0.  With grad mode off, or no operand requiring grad, it IS fused_mlp_func (same launches, same bits).  Otherwise fc1
+    runs with the bias epilogue and leaves the pre-activation (M, hidden) fp32 in memory - the only saved tensor besides x and the weights - and one more kernel
+    writes the GELU operand the fused epilogue would have written: the output has fused_mlp_func's bits in every mode.  Backward: dh = dy W2, dpre = dh gelu'(pre),
+    dx = dpre W1, dW2 = dy^T h, dW1 = dpre^T x as four NT GEMMs of the configured mode (the mode of the forward call) on operands written by csrc/mlp_bwd.hip
+    (transposed, zero-padded to K % 32 == 0; h recomputed from pre with the forward's bits), db2 / db1 by a fixed-order column sum.  Deterministic; only the
+    gradients autograd asks for are computed (frozen weights cost no wgrad GEMM, an x without grad no dgrad GEMM), and a gradient computed alone has the bits it
+    has in the full run.  Mode f16x2 splits the gradient operands with a per-tensor power-of-two scale.  No double backward, float32 only; save_pre_act /
+    checkpoint_lvl / heuristic are accepted and ignored."""
+    who = "fused_mlp_func_grad"
+    Cin, hid, Cout = _mlp_check(who, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, True)
+    tensors = [t for t in (x, weight1, weight2, bias1, bias2) if t is not None]
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors):
+        return _mlp_forward(x, weight1, weight2, bias1, bias2, _gemm_mode, False)[0]            # what the inference twin launches: the same bits
+    if Cout % 32:
+        raise SdvarError(f"{who}: out_features {Cout} must be a multiple of 32 under grad (it is K of the dh = dy W2 product)")
+    if any(t.device != x.device for t in tensors):
+        raise SdvarError(f"{who}: operands live on different devices")
+    return _MlpGrad.apply(x, weight1, weight2, bias1, bias2, _gemm_mode)
 
 
 def install(module, model=None) -> None:
@@ -492,15 +691,17 @@ def install_amp(module, model=None) -> None:
     module.slow_attn = slow_attn_amp
 
 
-def install_train(module, model=None) -> None:
-    """For TRAINING the reference in fp32 with the seam's attention: `module.slow_attn = slow_attn_grad`, and `module.fused_mlp_func = None` plus
+def install_train(module, model=None, ffn: bool = False) -> None:
+    """For TRAINING the reference in fp32 with the seam's operators: `module.slow_attn = slow_attn_grad`.  ffn=False (default): `module.fused_mlp_func = None` plus
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
-    state it is in without flash-attn installed.  `memory_efficient_attention` is left alone for the reason install() documents; assign
-    seam.memory_efficient_attention_grad yourself before building the model if you want the BLHc route.  Not part of this: a backward for the FFN (fused_mlp_func) and
-    a half-precision (autocast) backward - flash_attn_func and the _amp slots still raise on operands that require grad."""
+    state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
+    == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_grad yourself before building the
+    model if you want the BLHc route.  Not part of this: a half-precision (autocast) backward - flash_attn_func and the _amp slots still raise on operands that
+    require grad."""
+    slot = fused_mlp_func_grad if ffn else None
     module.slow_attn = slow_attn_grad
-    module.fused_mlp_func = None
+    module.fused_mlp_func = slot
     if model is not None:
         for m in model.modules():
             if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
-                m.fused_mlp_func = None
+                m.fused_mlp_func = slot
