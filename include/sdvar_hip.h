@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse and sdvar_op_sdpa_bwd; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
+#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
 #define SDVAR_MAX_STAGES 16
 
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
@@ -446,6 +446,39 @@ int sdvar_prof_collect(double* ms /*host[SDVAR_PROF_CLASSES]*/, int64_t* launche
 int sdvar_op_sdpa_hm(const void* q, const void* k, const void* v, void* out, const int64_t* strides /*host, 12*/, int32_t dtype /*1 fp16 | 2 bf16*/, int32_t q_f32,
                      int32_t k_f32, const void* bias, int32_t bias_kind /*0 none | 1 fp32 | 2 uint8 keep | 3 additive in dtype*/, const int64_t* bias_strides /*host, 3*/,
                      const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
+
+/* The same slots under torch.autocast AND autograd (the reference's mixed-precision trainer: utils/amp_sc.py wraps the step in torch.autocast; sdvar_amd/seam.py:
+ * slow_attn_amp_grad, memory_efficient_attention_amp_grad, flash_attn_func_grad).  Both entries were added WITHOUT an ABI bump (purely additive).
+ * sdvar_op_sdpa_hm_lse = sdvar_op_sdpa_hm (same arguments and rules; it also accepts bias_kind 0 with three half operands, and `out` is then bit-identical to
+ * sdvar_op_sdpa_h's, otherwise to sdvar_op_sdpa_hm's) that also writes lse (device, (B, H, Lq) dense fp32): lse[b][h][i] = ln sum_j exp(scale q_i k_j + bias_ij) from the
+ * fp32 scores of the rounded operands (the kernel's running maximum and fp32 row sum, converted from base 2), for every query row it stores; rows past Lq are never
+ * written.  A fully masked row: -inf. */
+int sdvar_op_sdpa_hm_lse(const void* q, const void* k, const void* v, void* out, float* lse, const int64_t* strides /*host, 12*/, int32_t dtype /*1 fp16 | 2 bf16*/,
+                         int32_t q_f32, int32_t k_f32, const void* bias, int32_t bias_kind /*0 none | 1 fp32 | 2 uint8 keep | 3 additive in dtype*/,
+                         const int64_t* bias_strides /*host, 3*/, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale,
+                         void* stream);
+/* The backward of sdvar_op_sdpa_hm_lse on the half-precision matrix cores (csrc/attention_sdpa_h_bwd.hip).  q, k, v, dtype, q_f32, k_f32, bias, bias_kind, bias_strides,
+ * skip_map, extents and scale exactly as given to the forward; out and lse as the forward wrote them; dout the gradient of out.  Three launches (D, dK/dV, dQ), no
+ * score-sized matrix in memory, tiles the skip map marks are not visited, no atomics (every output element is reduced in a fixed order: repeats are bit-identical), no
+ * host synchronisation.  delta (device): workspace of B * H * Lq floats, receives D.  Any of dq, dk, dv may be NULL and is then not computed (its strides are ignored);
+ * with dk and dv both NULL the dK/dV kernel is not launched, with dq NULL the dQ kernel is not; all three NULL is an argument error.
+ * strides (host, 24 x int64): (batch, head, token) of q, k, v, out, dout, dq, dk, dv, each in ITS tensor's elements; channel stride 1; every given pointer % 16 == 0;
+ * strides of a half tensor are non-negative multiples of 8, of an fp32 tensor of 4.  head_dim must be 64; any Lq, Lk >= 1.
+ * Arithmetic contract:
+ *   - dtype (1 fp16, 2 bf16) is the type of v, out, dout and dv.  q and k may each be fp32 (q_f32 / k_f32) and are then rounded to dtype (nearest even) as they are read:
+ *     the same bits as in the forward.
+ *   - P = exp(scale q k^T + bias - lse) is recomputed in fp32 from the half-precision matrix-core scores, with the forward's score expression in base 2.
+ *   - D_i = sum_d dout_id out_id, accumulated in fp32 from the stored half values.
+ *   - dV = P^T dout with P rounded to dtype (nearest even), fp32 accumulation.  dP = dout v^T on the half matrix cores, fp32 accumulation.
+ *   - dS = P o (dP - D) in fp32, rounded once to dtype (nearest even).  dQ = scale (dS K), dK = scale (dS^T Q), fp32 accumulation; scale multiplies the fp32 accumulator.
+ *   - each gradient is stored once: dv in dtype; dq in q's type and dk in k's type - fp32 (unrounded) when that operand was fp32, else rounded once to dtype.
+ *   - no clamping: a value beyond fp16's range becomes +-inf exactly as a cast would (a GradScaler relies on seeing inf to skip a step).
+ *   - a -inf bias entry inside a visited tile gives P = dS = 0.  A fully masked query row has no defined gradient; it does not fault and does not disturb other rows.
+ * No gradient for the bias. */
+int sdvar_op_sdpa_h_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta /*workspace*/, void* dq, void* dk,
+                        void* dv, const int64_t* strides /*host, 24*/, int32_t dtype /*1 fp16 | 2 bf16*/, int32_t q_f32, int32_t k_f32, const void* bias,
+                        int32_t bias_kind /*0 none | 1 fp32 | 2 uint8 keep | 3 additive in dtype*/, const int64_t* bias_strides /*host, 3*/, const uint8_t* skip_map,
+                        int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,11 @@ int attention_sdpa_h(const void* q, const void* k, const void* v, void* out, con
                      hipStream_t stream);
 int attention_sdpa_hm(const void* q, const void* k, const void* v, void* out, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias, int kind,
                       const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, double scale, hipStream_t stream);
+int attention_sdpa_hm_lse(const void* q, const void* k, const void* v, void* out, float* lse, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias,
+                          int kind, const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, double scale, hipStream_t stream);
+int attention_sdpa_h_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                         const long long* strides, int dtype, int q_f32, int k_f32, const void* bias, int kind, const long long* bs, const uint8_t* skip, int B, int H,
+                         int Lq, int Lk, int head_dim, double scale, hipStream_t stream);
 int split_planes(const float* x, uint16_t* planes, int rows, int cols, size_t plane_stride, hipStream_t stream);
 int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                   int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -964,6 +969,20 @@ int sdvar_op_sdpa_hm(const void* q, const void* k, const void* v, void* out, con
                      void* stream) {
     return attention_sdpa_hm(q, k, v, out, reinterpret_cast<const long long*>(strides), dtype, q_f32, k_f32, bias, bias_kind, reinterpret_cast<const long long*>(bias_strides),
                              skip_map, B, H, Lq, Lk, head_dim, scale, (hipStream_t)stream);
+}
+// the same slots under autocast AND autograd (the reference's mixed-precision trainer, utils/amp_sc.py): forward with log-sum-exp, csrc/attention_sdpa_h.hip; backward,
+// csrc/attention_sdpa_h_bwd.hip
+int sdvar_op_sdpa_hm_lse(const void* q, const void* k, const void* v, void* out, float* lse, const int64_t* strides, int32_t dtype, int32_t q_f32, int32_t k_f32,
+                         const void* bias, int32_t bias_kind, const int64_t* bias_strides, const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
+                         int32_t head_dim, double scale, void* stream) {
+    return attention_sdpa_hm_lse(q, k, v, out, lse, reinterpret_cast<const long long*>(strides), dtype, q_f32, k_f32, bias, bias_kind,
+                                 reinterpret_cast<const long long*>(bias_strides), skip_map, B, H, Lq, Lk, head_dim, scale, (hipStream_t)stream);
+}
+int sdvar_op_sdpa_h_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                        const int64_t* strides, int32_t dtype, int32_t q_f32, int32_t k_f32, const void* bias, int32_t bias_kind, const int64_t* bias_strides,
+                        const uint8_t* skip_map, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream) {
+    return attention_sdpa_h_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, reinterpret_cast<const long long*>(strides), dtype, q_f32, k_f32, bias, bias_kind,
+                                reinterpret_cast<const long long*>(bias_strides), skip_map, B, H, Lq, Lk, head_dim, scale, (hipStream_t)stream);
 }
 
 int sdvar_debug_set_gemm_cfg(int32_t bm, int32_t split) {

@@ -222,6 +222,9 @@ bool aligned_strides_h(const long long* s) { return s[0] % 8 == 0 && s[1] % 8 ==
 //     tile contributes exp2(-inf) = 0 and never exp2(-inf - (-inf)).  A row with every key masked ends as 0 / 0 (unspecified; no fault, other rows untouched).
 //   * skip map (sdpa_skip_map's format: one byte per (128-query block, 64-key tile)): marked tiles are never staged, prefetched or multiplied; the one-tile-ahead
 //     prefetch targets the next UNMARKED tile.
+//   * LSE (template, sdvar_op_sdpa_hm_lse): each stored query row also writes lse = ln 2 (m_run + log2 l_run), the natural log-sum-exp of its fp32 scores, what the
+//     backward (attention_sdpa_h_bwd.hip) recomputes P from.  A compile-time flag: the instantiations without it keep their code and their bits, and the ones with it
+//     change nothing in front of the final store, so `out` is the same bits.
 enum { HB_NONE = 0, HB_F32 = 1, HB_U8 = 2, HB_HALF = 3 };
 
 struct SdpaHmArgs {
@@ -233,6 +236,7 @@ struct SdpaHmArgs {
     int q_f32, k_f32;
     int B, H, Lq, Lk;
     float scale_l2e;
+    float* lse;                                 // LSE instantiations only: (B, H, Lq) dense fp32; last, so the other instantiations' argument offsets do not move
 };
 
 // eight fp32 -> eight halves (one 16-byte chunk), round to nearest even
@@ -249,7 +253,7 @@ __device__ __forceinline__ float half_bits_to_float(uint32_t h) {
     return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
 }
 
-template <bool BF16, int BIAS>
+template <bool BF16, int BIAS, bool LSE>
 __global__ __launch_bounds__(256, 2) void attention_sdpa_hm_kernel(SdpaHmArgs a) {
     // [stage][K | V][64 keys x 8 chunks of 16 bytes]
     __shared__ __attribute__((aligned(16))) u32x4 smem[2][2][KT * 8];
@@ -483,19 +487,21 @@ __global__ __launch_bounds__(256, 2) void attention_sdpa_hm_kernel(SdpaHmArgs a)
             *reinterpret_cast<u32x2*>(po + 8 * g) = w0;
             *reinterpret_cast<u32x2*>(po + 32 + 8 * g) = w1;
         }
+        // both halves of the lane pair hold the same m_run and l_run; a fully masked row writes -inf + log2(0) = -inf
+        if (LSE && lh == 0) a.lse[((long long)b * a.H + h) * a.Lq + qi_raw] = (m_run + __builtin_amdgcn_logf(l_run)) * 0.6931471805599453f;
     }
 }
 
 bool aligned_strides_f(const long long* s) { return s[0] % 4 == 0 && s[1] % 4 == 0 && s[2] % 4 == 0 && s[0] >= 0 && s[1] >= 0 && s[2] >= 0; }
 
 typedef void (*SdpaHmKernel)(SdpaHmArgs);
-template <bool BF16>
+template <bool BF16, bool LSE>
 SdpaHmKernel sdpa_hm_variant(int kind) {
     switch (kind) {
-        case HB_F32: return attention_sdpa_hm_kernel<BF16, HB_F32>;
-        case HB_U8: return attention_sdpa_hm_kernel<BF16, HB_U8>;
-        case HB_HALF: return attention_sdpa_hm_kernel<BF16, HB_HALF>;
-        default: return attention_sdpa_hm_kernel<BF16, HB_NONE>;
+        case HB_F32: return attention_sdpa_hm_kernel<BF16, HB_F32, LSE>;
+        case HB_U8: return attention_sdpa_hm_kernel<BF16, HB_U8, LSE>;
+        case HB_HALF: return attention_sdpa_hm_kernel<BF16, HB_HALF, LSE>;
+        default: return attention_sdpa_hm_kernel<BF16, HB_NONE, LSE>;
     }
 }
 
@@ -528,8 +534,9 @@ int attention_sdpa_h(const void* q, const void* k, const void* v, void* out, con
 
 // strides: 12 element strides, (batch, head, token) of q, k, v, out in that order (q / k in THEIR elements: fp32 where flagged); dtype 1 = fp16, 2 = bf16 (v, out and
 // the unflagged operands); bias kind 0 none | 1 fp32 additive | 2 uint8 keep | 3 additive in dtype; bs: (batch, head, query row) element strides, 0 = broadcast
-int attention_sdpa_hm(const void* q, const void* k, const void* v, void* out, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias, int kind,
-                      const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, double scale, hipStream_t stream) {
+// lse: nullptr = sdvar_op_sdpa_hm; else sdvar_op_sdpa_hm_lse, which also writes the (B, H, Lq) log-sum-exp rows
+static int sdpa_hm_launch(const void* q, const void* k, const void* v, void* out, float* lse, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias,
+                          int kind, const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, double scale, hipStream_t stream) {
     SDVAR_CHECK_ARG(q && k && v && out && strides, "sdpa_hm: null operand");
     SDVAR_CHECK_ARG(dtype == 1 || dtype == 2, "sdpa_hm: dtype %d (1 = fp16, 2 = bf16)", dtype);
     SDVAR_CHECK_ARG((q_f32 == 0 || q_f32 == 1) && (k_f32 == 0 || k_f32 == 1), "sdpa_hm: q_f32 = %d, k_f32 = %d (0 or 1)", q_f32, k_f32);
@@ -562,10 +569,25 @@ int attention_sdpa_hm(const void* q, const void* k, const void* v, void* out, co
     a.q_f32 = q_f32; a.k_f32 = k_f32;
     a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale_l2e = (float)(scale * 1.4426950408889634);
     const dim3 grid((Lq + QB - 1) / QB, H, B);
-    const SdpaHmKernel kern = dtype == 2 ? sdpa_hm_variant<true>(kind) : sdpa_hm_variant<false>(kind);
+    a.lse = lse;
+    const SdpaHmKernel kern = lse ? (dtype == 2 ? sdpa_hm_variant<true, true>(kind) : sdpa_hm_variant<false, true>(kind))
+                                  : (dtype == 2 ? sdpa_hm_variant<true, false>(kind) : sdpa_hm_variant<false, false>(kind));
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
+}
+
+int attention_sdpa_hm(const void* q, const void* k, const void* v, void* out, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias, int kind,
+                      const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, double scale, hipStream_t stream) {
+    return sdpa_hm_launch(q, k, v, out, nullptr, strides, dtype, q_f32, k_f32, bias, kind, bs, skip, B, H, Lq, Lk, head_dim, scale, stream);
+}
+
+// attention_sdpa_hm that also writes lse (device, (B, H, Lq) dense fp32); with kind 0 and three half operands `out` has attention_sdpa_h's bits (the same arithmetic:
+// no bias, so the running maximum is finite from the first tile on)
+int attention_sdpa_hm_lse(const void* q, const void* k, const void* v, void* out, float* lse, const long long* strides, int dtype, int q_f32, int k_f32, const void* bias,
+                          int kind, const long long* bs, const uint8_t* skip, int B, int H, int Lq, int Lk, int head_dim, double scale, hipStream_t stream) {
+    SDVAR_CHECK_ARG(lse && ((uintptr_t)lse & 3) == 0, "sdpa_hm_lse: lse is NULL or not 4-byte aligned");
+    return sdpa_hm_launch(q, k, v, out, lse, strides, dtype, q_f32, k_f32, bias, kind, bs, skip, B, H, Lq, Lk, head_dim, scale, stream);
 }
 
 }  // namespace sdvar

@@ -14,7 +14,10 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install_train(basic_var, model)    # fp32 TRAINING: slow_attn_grad (HIP forward + backward under autograd); the FFN goes back to the reference's own fc2(act(fc1(x)))
     seam.install_train(basic_var, model, ffn=True)      # ... and fused_mlp_func_grad: the FFN's forward and backward on HIP too
 
-Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward) and
+    seam.install_train_amp(basic_var, model)    # TRAINING under torch.autocast (fp16 + GradScaler, or bf16): slow_attn_amp_grad + flash_attn_func_grad
+
+Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
+slow_attn_amp_grad / memory_efficient_attention_amp_grad / flash_attn_func_grad (the half and mixed operands of autocast; backward = sdvar_op_sdpa_h_bwd) and
 fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward):
 no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
 `flash_attn_func` takes fp16 or bf16 operands only (and no mask); `slow_attn_amp` / `memory_efficient_attention_amp` take a half value with query and key each
@@ -42,7 +45,7 @@ from .engine import SdvarError
 
 __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
-           "fused_mlp_func_grad"]
+           "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -232,7 +235,7 @@ def _sdpa_grad(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
         if not t.is_cuda:
             raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
         if t.dtype in _HALF_DTYPES:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported - the autocast slots (slow_attn_amp, flash_attn_func) have no backward yet")
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported - the autocast slots (slow_attn_amp, flash_attn_func) have no backward; use slow_attn_amp_grad / flash_attn_func_grad")
         if t.dtype != torch.float32:
             raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
         if t.dim() != 4:
@@ -282,9 +285,20 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[flo
     q (B, Lq, H, 64), k / v (B, Lk, H, 64), all three float16 or all three bfloat16 on the GPU; operands meeting the alignment rule are read in place, any other is
     copied once into a dense, freshly allocated tensor.  softmax_scale=None means 1/sqrt(64).  Returns a contiguous (B, Lq, H, 64) tensor of the operand dtype.  fp32 accumulation, the
     softmax weights rounded to the operand dtype (nearest even) for the P V product; deterministic always (`deterministic` is accepted and ignored)."""
-    who = "flash_attn_func"
+    q, k, v = _flash_check("flash_attn_func", q, k, v, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, False)
+    B, Lq, H, _ = q.shape
+    Lk = k.shape[1]
+    out = torch.empty((B, Lq, H, 64), dtype=q.dtype, device=q.device)
+    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, out) for i in (0, 2, 1)))
+    scale = 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale)
+    E._check(E.load_library().sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[q.dtype], B, H, Lq, Lk, 64, scale, E._stream()))
+    return out
+
+
+def _flash_check(who: str, q, k, v, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, grad: bool):
+    """The argument checks of the flash_attn_func slots; grad = the caller has a backward.  Returns the operands, each read in place or copied once."""
     if dropout_p and dropout_p > 0:
-        raise SdvarError(f"{who}: dropout_p > 0 is not supported (inference only)")
+        raise SdvarError(f"{who}: dropout_p > 0 is not supported " + ("(the reference trains with attn_drop = 0)" if grad else "(inference only)"))
     if causal:
         raise SdvarError(f"{who}: causal=True is not supported (the reference's cached calls pass no mask)")
     if window_size is not None and tuple(window_size) != (-1, -1):
@@ -304,8 +318,8 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[flo
             raise SdvarError(f"{who}: {name} is torch.float32; this slot takes float16 / bfloat16 operands - use slow_attn or memory_efficient_attention for float32")
         if t.dtype not in _HALF_DTYPES:
             raise SdvarError(f"{who}: {name} is {t.dtype}; only float16 and bfloat16 operands are supported")
-        if t.requires_grad and torch.is_grad_enabled():
-            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
+        if not grad and t.requires_grad and torch.is_grad_enabled():
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use flash_attn_func_grad)")
         if t.dim() != 4:
             raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
     if q.dtype != k.dtype or q.dtype != v.dtype:
@@ -319,13 +333,10 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[flo
         raise SdvarError(f"{who}: shapes do not match: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
     if q.device != k.device or q.device != v.device:
         raise SdvarError(f"{who}: operands live on different devices")
+    if grad:                # the autograd function copies what it must itself (its inputs stay the caller's tensors)
+        return q, k, v
     # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
-    q, k, v = (t if _rows_aligned_h(t) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
-    out = torch.empty((B, Lq, H, 64), dtype=q.dtype, device=q.device)
-    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, out) for i in (0, 2, 1)))
-    scale = 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale)
-    E._check(E.load_library().sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[q.dtype], B, H, Lq, Lk, 64, scale, E._stream()))
-    return out
+    return tuple(t if _rows_aligned_h(t) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
 
 
 def _sdpa_amp(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
@@ -338,7 +349,7 @@ def _sdpa_amp(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
         if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
             raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
         if t.requires_grad and torch.is_grad_enabled():
-            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use slow_attn_amp_grad / memory_efficient_attention_amp_grad)")
         if t.dim() != 4:
             raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
         if t.shape[-1] != 64:
@@ -393,6 +404,125 @@ def memory_efficient_attention_amp(q, k, v, attn_bias=None, p: float = 0.0, scal
     if p and p > 0:
         raise SdvarError("memory_efficient_attention_amp: p > 0 (dropout) is not supported (inference only)")
     return _sdpa_amp("memory_efficient_attention_amp", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
+
+
+class _SdpaAmpGrad(torch.autograd.Function):
+    """softmax(scale q k^T + mask) v on half / mixed operands with a HIP backward: forward = sdvar_op_sdpa_hm_lse, backward = one sdvar_op_sdpa_h_bwd call
+    (csrc/attention_sdpa_h_bwd.hip)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, idx, scale, who):
+        ib, ih, it = idx
+        B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
+        half = v.dtype
+        mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, half)
+        # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
+        q, k, v = (t if (_rows_aligned(t) if t.dtype == torch.float32 else _rows_aligned_h(t)) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
+        out = torch.empty((B, Lq, H, 64), dtype=half, device=q.device)
+        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+        strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
+        qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
+        E._check(E.load_library().sdvar_op_sdpa_hm_lse(_p(q), _p(k), _p(v), _p(out), _p(lse), strides, _HALF_DTYPES[half], qf, kf, _p(mask), kind, bstr, _p(smap), B, H,
+                                                       Lq, Lk, 64, float(scale), E._stream()))
+        ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask, smap)))
+        ctx.sdpa = (idx, float(scale), kind, bstr, (B, H, Lq, Lk), half, who)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        idx, scale, kind, bstr, (B, H, Lq, Lk), half, who = ctx.sdpa
+        if dout.dtype != half:
+            raise SdvarError(f"{who}: the gradient of the output is {dout.dtype} but the output is {half}; the backward reads dout in the output's dtype")
+        q, k, v, out, lse, *rest = ctx.saved_tensors
+        mask, smap = rest if rest else (None, None)
+        # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address would come back as itself
+        if not _rows_aligned_h(dout):
+            dout = dout.clone(memory_format=torch.contiguous_format)
+        dq, dk, dv = (torch.empty((B, L, H, 64), dtype=t.dtype, device=q.device) if need else None
+                      for need, L, t in zip(ctx.needs_input_grad[:3], (Lq, Lk, Lk), (q, k, v)))
+        if dq is None and dk is None and dv is None:
+            return (None,) * 7
+        delta = torch.empty(B * H * Lq, dtype=torch.float32, device=q.device)
+        blhc = lambda t: (0, 0, 0) if t is None else (t.stride(0), t.stride(2), t.stride(1))
+        strides = (C.c_int64 * 24)(*(t.stride(i) for t in (q, k, v) for i in idx), *blhc(out), *blhc(dout), *blhc(dq), *blhc(dk), *blhc(dv))
+        qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
+        E._check(E.load_library().sdvar_op_sdpa_h_bwd(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), strides, _HALF_DTYPES[half],
+                                                      qf, kf, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, scale, E._stream()))
+        if idx == (0, 1, 2):                # (B, H, L, 64) operands: views of the (B, L, H, 64) buffers
+            dq, dk, dv = (None if t is None else t.permute(0, 2, 1, 3) for t in (dq, dk, dv))
+        return dq, dk, dv, None, None, None, None
+
+
+def _sdpa_amp_grad(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
+    """The differentiable attention slots under torch.autocast: _sdpa_amp's operand rules, minus its refusal of operands that require grad.  Returns the
+    (B, Lq, H, 64) output buffer."""
+    for name, t in (("query", q), ("key", k), ("value", v)):
+        if not isinstance(t, torch.Tensor):
+            raise SdvarError(f"{who}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+        if t.dim() != 4:
+            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
+        if t.shape[-1] != 64:
+            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+    if isinstance(mask, torch.Tensor) and mask.requires_grad and torch.is_grad_enabled():
+        raise SdvarError(f"{who}: the mask requires grad; there is no gradient for the mask")
+    if v.dtype == torch.float32:
+        if q.dtype != torch.float32 or k.dtype != torch.float32:
+            raise SdvarError(f"{who}: value is torch.float32 next to query {q.dtype} / key {k.dtype}: value fixes the dtype of the product and of the result, and a "
+                             "float32 value only goes with float32 query and key")
+        return _sdpa_grad(who, q, k, v, idx, scale, mask)           # three fp32 operands: the fp32 slots' path, unchanged
+    half = v.dtype
+    for name, t in (("query", q), ("key", k)):
+        if t.dtype != half and t.dtype != torch.float32:
+            raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype}, value is {half} (query and key must each be {half} or float32)")
+    if not torch.is_grad_enabled() or not (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _sdpa_amp(who, q, k, v, idx, scale, mask)            # what the inference twin launches: the same bits, no LSE
+    ib, ih, it = idx
+    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
+    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or B < 1 or H < 1 or Lq < 1 or Lk < 1:
+        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
+    if q.device != k.device or q.device != v.device:
+        raise SdvarError(f"{who}: operands live on different devices")
+    return _SdpaAmpGrad.apply(q, k, v, mask, idx, scale, who)
+
+
+def slow_attn_amp_grad(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
+    """slow_attn_amp under autograd (the reference's mixed-precision trainer runs loss.backward() through basic_var.py:117 under torch.autocast): layouts, dtype rules
+    (value fixes the half dtype; query and key each that dtype or float32), mask rules, alignment and copy-once rule and the returned (B, H, Lq, 64) view as for
+    slow_attn_amp.  With grad mode off, or no operand requiring grad, it IS slow_attn_amp (same launch, same bits); three float32 operands go to slow_attn_grad's path.
+    Otherwise the forward is sdvar_op_sdpa_hm_lse (slow_attn_amp's output bits, plus the log-sum-exp rows) and the backward one sdvar_op_sdpa_h_bwd call on the
+    half-precision matrix cores: P recomputed in fp32 from the rounded operands, P and dS rounded once to the half dtype for the second products, fp32 accumulation,
+    no clamping (an fp16 overflow is +-inf, which a GradScaler needs to see), no score matrix in memory, masked tiles skipped, deterministic.  Gradients come back as
+    (B, H, L, 64) views of fresh dense (B, L, H, 64) buffers in each operand's OWN dtype (float32 for a float32 query / key, unrounded); only those autograd asks for
+    are computed.  An upstream gradient that misses the alignment rule is copied once; one whose dtype is not the output's raises.  No dropout, no gradient for the
+    mask, no double backward."""
+    if dropout_p and dropout_p > 0:
+        raise SdvarError("slow_attn_amp_grad: dropout_p > 0 is not supported (the reference trains with attn_drop = 0)")
+    return _sdpa_amp_grad("slow_attn_amp_grad", query, key, value, (0, 1, 2), scale, attn_mask).permute(0, 2, 1, 3)
+
+
+def memory_efficient_attention_amp_grad(q, k, v, attn_bias=None, p: float = 0.0, scale: Optional[float] = None):
+    """memory_efficient_attention_amp under autograd: q (B, Lq, H, 64), k / v (B, Lk, H, 64), dtypes and attn_bias as for slow_attn_amp_grad; returns (B, Lq, H, 64);
+    gradients are dense (B, L, H, 64).  The same kernels as slow_attn_amp_grad with other strides."""
+    if p and p > 0:
+        raise SdvarError("memory_efficient_attention_amp_grad: p > 0 (dropout) is not supported (the reference trains with attn_drop = 0)")
+    return _sdpa_amp_grad("memory_efficient_attention_amp_grad", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
+
+
+def flash_attn_func_grad(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[float] = None, causal: bool = False, window_size=(-1, -1), softcap: float = 0.0,
+                         alibi_slopes=None, deterministic: bool = False, return_attn_probs: bool = False):
+    """flash_attn_func under autograd: signature, operand rules (three float16 or three bfloat16 (B, L, H, 64) operands, no mask) and rejections as flash_attn_func.
+    With grad mode off, or no operand requiring grad, it IS flash_attn_func (same launch, same bits).  Otherwise memory_efficient_attention_amp_grad's function
+    without a bias: the output has flash_attn_func's bits, gradients are dense (B, L, H, 64) tensors of the operand dtype."""
+    who = "flash_attn_func_grad"
+    q, k, v = _flash_check(who, q, k, v, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, True)
+    if not torch.is_grad_enabled() or not (q.requires_grad or k.requires_grad or v.requires_grad):
+        return flash_attn_func(q, k, v, softmax_scale=softmax_scale)
+    return _SdpaAmpGrad.apply(q, k, v, None, (0, 2, 1), 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale), who)
 
 
 def _cached_planes(kind: str, w: torch.Tensor, mode: str, make):
@@ -696,12 +826,33 @@ def install_train(module, model=None, ffn: bool = False) -> None:
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
     state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
     == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_grad yourself before building the
-    model if you want the BLHc route.  Not part of this: a half-precision (autocast) backward - flash_attn_func and the _amp slots still raise on operands that
-    require grad."""
+    model if you want the BLHc route.  A model trained under torch.autocast needs install_train_amp instead: the slots set here are float32 only, and flash_attn_func
+    and the _amp slots still raise on operands that require grad."""
     slot = fused_mlp_func_grad if ffn else None
     module.slow_attn = slow_attn_grad
     module.fused_mlp_func = slot
     if model is not None:
         for m in model.modules():
+            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
+                m.fused_mlp_func = slot
+
+
+def install_train_amp(module, model=None, ffn: bool = False) -> None:
+    """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
+    `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
+    the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
+    reference runs its own fc2(act(fc1(x))) under autocast; ffn=True sets them to fused_mlp_func_grad.  That function takes float32 operands ONLY and is not
+    autocast-aware: it runs its own fp32-operand GEMMs whatever autocast says, and RAISES SdvarError on a half-precision x.  The reference's FFN input is the output
+    of a LayerNorm and the adaLN modulation, which autocast keeps in float32, so ffn=True works there; a model that hands its FFN a half x must use ffn=False.
+    `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_amp_grad yourself before building the model
+    if you want the BLHc route."""
+    slot = fused_mlp_func_grad if ffn else None
+    module.slow_attn = slow_attn_amp_grad
+    module.flash_attn_func = flash_attn_func_grad
+    module.fused_mlp_func = slot
+    if model is not None:
+        for m in model.modules():
+            if hasattr(m, "using_flash"):
+                m.using_flash = True
             if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
                 m.fused_mlp_func = slot
