@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
+#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd, and after them sdvar_xent_train_fwd and sdvar_xent_train_bwd; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
 #define SDVAR_MAX_STAGES 16
 
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
@@ -238,6 +238,26 @@ int sdvar_xent_stats(const float* logits, const int64_t* targets, int32_t B, int
  * 16-byte loads when a and b are 16-byte aligned.  Uses a scratch of 2048 doubles per (host thread, device), on the device that is current at the call:
  * calls of one host thread on one device share it and must be on one stream, or ordered by the caller. */
 int sdvar_img_err_stats(const float* a, const float* b, int64_t n, double* sums, int32_t accumulate, void* stream);
+/* The trainer's loss (VARTrainer, trainer.py:37-38: nn.CrossEntropyLoss(label_smoothing=eps, reduction='none') and (label_smoothing=0, reduction='mean'); called at
+ * trainer.py:112 and weighted, summed and averaged at :116-120) on logits (rows, V) fp32 with row stride `ld` elements (unit column stride; a row-sliced view is read in
+ * place) against targets (rows) int64, one wave64 per row, ONE pass over the logits:
+ *     loss = (1 - eps) (lse - x_t) + eps (lse - sum_j x_j / V)          (torch's label_smoothing = eps; eps == 0 evaluates lse - x_t alone)
+ * loss (rows) fp32; lse (rows) fp32 or NULL - the only thing the backward needs beside logits and targets.  target == ignore_index: loss 0, row not counted; any other
+ * target outside [0, V): loss NaN (x_t is never read), row counted.  part / sums / reduced may be NULL (all three; reduction 'none'): otherwise part is a caller workspace
+ * of 2 * ceil(rows / 4) doubles receiving per-workgroup partials, and a second, single-workgroup launch adds them in a fixed order (no atomics: repeats are
+ * bit-identical) into sums (2 doubles) = {sum of loss over counted rows, counted rows} and, if given, reduced (1 float) = sum / count (mean != 0; 0 / 0 = NaN as torch)
+ * or sum (mean == 0).  V >= 4, V % 4 == 0, ld >= V, ld % 4 == 0, logits 16-byte aligned, 1 <= rows <= 2^31 - 1, 0 <= eps <= 1: argument errors otherwise, checked
+ * before any GPU call.  No allocation, no host synchronisation.  Added without an ABI bump (purely additive).  csrc/xent_train.hip */
+int sdvar_xent_train_fwd(const float* logits, int64_t ld, const int64_t* targets, int64_t rows, int32_t V, double label_smoothing, int64_t ignore_index, float* loss,
+                         float* lse, double* part /*workspace*/, double* sums, float* reduced, int32_t mean, void* stream);
+/* The backward of sdvar_xent_train_fwd (loss.backward() of trainer.py:120 reaching the logits of :112): one read of the logits, one write,
+ *     dlogits[row, j] = g_row (exp(x_j - lse_row) - (1 - eps) [j == t_row] - eps / V),
+ * dlogits (rows, V) fp32 dense, 16-byte aligned, every element written by exactly one lane.  reduction 0 ('none'): g_row = grad[row]; 2 ('sum'): g_row = grad[0];
+ * 1 ('mean'): g_row = grad[0] / sums[1], the counted-row count the forward left on the device.  grad and sums are DEVICE pointers: nothing is read on the host.
+ * Ignored rows get zeros (their logits are not read), out-of-range rows NaN.  logits, ld, targets, V, label_smoothing and ignore_index as given to the forward, lse as
+ * it wrote it; the same argument checks.  flags bit 0: non-temporal stores for dlogits (same values).  Deterministic. */
+int sdvar_xent_train_bwd(const float* logits, int64_t ld, const int64_t* targets, const float* lse, const float* grad, int32_t reduction, const double* sums, int64_t rows,
+                         int32_t V, double label_smoothing, int64_t ignore_index, float* dlogits, int32_t flags, void* stream);
 
 /* ---- single operators (kernel-level parity tests and micro-benchmarks) ---------------------------------------------- */
 /* out[M,N] = epi(X[M,K] W[N,K]^T + bias); epi 0 bias, 1 bias+GELU(tanh), 2 res + (.)*gate[row / rows_per_gate] */

@@ -38,6 +38,10 @@ int build_lvl_pos(const float* lvl_embed, const float* pos, const int* stage_of_
 int embed_next(const float* nxt, const float* Ww, const float* bw, const float* lvl_pos, float* x, int B, int l, int C, int t0, int ltot, int tok_off, int pair, hipStream_t stream);
 int xent_stats(const float* logits, const long long* targets, int B, int L, int V, int tail, float* nll_out, long long* argmax_out, double* sums, int accumulate,
                hipStream_t stream);
+int xent_train_fwd(const float* logits, long long ld, const long long* targets, long long rows, int V, double eps, long long ignore_index, float* loss, float* lse,
+                   double* part, double* sums, float* reduced, int mean, hipStream_t stream);
+int xent_train_bwd(const float* logits, long long ld, const long long* targets, const float* lse, const float* grad, int reduction, const double* sums, long long rows,
+                   int V, double eps, long long ignore_index, float* dlogits, int flags, hipStream_t stream);
 int attention_f32(const float* q, const void* kc, const void* vc, int kv_f16, float* out, uint16_t* outp, size_t ops, int pfmt, int R, int H, int l, int Lmax, int Ktot, int n_chunk, const int* qbeg, const int* vis, hipStream_t stream);
 int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -524,6 +528,16 @@ int sdvar_xent_stats(const float* logits, const int64_t* targets, int32_t B, int
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(5, 6.0 * B * (double)L * V, 4.0 * B * (double)L * V + 20.0 * B * L, s);
     return xent_stats(logits, (const long long*)targets, B, L, V, tail, nll_out, (long long*)argmax_out, sums, accumulate, s);
+}
+
+// the trainer's label-smoothed cross-entropy under autograd (trainer.py:37-38, 112-120; sdvar_amd/seam.py cross_entropy): csrc/xent_train.hip
+int sdvar_xent_train_fwd(const float* logits, int64_t ld, const int64_t* targets, int64_t rows, int32_t V, double label_smoothing, int64_t ignore_index, float* loss,
+                         float* lse, double* part, double* sums, float* reduced, int32_t mean, void* stream) {
+    return xent_train_fwd(logits, ld, (const long long*)targets, rows, V, label_smoothing, ignore_index, loss, lse, part, sums, reduced, mean, (hipStream_t)stream);
+}
+int sdvar_xent_train_bwd(const float* logits, int64_t ld, const int64_t* targets, const float* lse, const float* grad, int32_t reduction, const double* sums, int64_t rows,
+                         int32_t V, double label_smoothing, int64_t ignore_index, float* dlogits, int32_t flags, void* stream) {
+    return xent_train_bwd(logits, ld, (const long long*)targets, lse, grad, reduction, sums, rows, V, label_smoothing, ignore_index, dlogits, flags, (hipStream_t)stream);
 }
 
 static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream);

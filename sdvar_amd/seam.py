@@ -16,6 +16,8 @@ maintainer of the reference who wants the kernels without adopting the sampling 
 
     seam.install_train_amp(basic_var, model)    # TRAINING under torch.autocast (fp16 + GradScaler, or bf16): slow_attn_amp_grad + flash_attn_func_grad
 
+    seam.install_trainer(trainer)           # the VARTrainer's train_loss / val_loss (trainer.py:37-38): label-smoothed cross-entropy, HIP forward + backward
+
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
 slow_attn_amp_grad / memory_efficient_attention_amp_grad / flash_attn_func_grad (the half and mixed operands of autocast; backward = sdvar_op_sdpa_h_bwd) and
 fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward):
@@ -23,6 +25,8 @@ no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention`
 `flash_attn_func` takes fp16 or bf16 operands only (and no mask); `slow_attn_amp` / `memory_efficient_attention_amp` take a half value with query and key each
 half or fp32, and masks.  Anything else raises SdvarError - there is no fall-back to torch.
 Torch is used for device memory and the current stream only; bool masks go to the kernel as bytes.
+cross_entropy / CrossEntropyLoss / install_trainer are the trainer's loss slots (trainer.py:37-38): label-smoothed cross-entropy on float32 logits, differentiable
+(forward = sdvar_xent_train_fwd, backward = sdvar_xent_train_bwd; one float per row saved, no double backward).
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
 reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
@@ -45,7 +49,8 @@ from .engine import SdvarError
 
 __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
-           "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp"]
+           "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
+           "cross_entropy", "CrossEntropyLoss", "install_trainer"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -787,6 +792,110 @@ def fused_mlp_func_grad(x, weight1, weight2, bias1=None, bias2=None, activation:
     if any(t.device != x.device for t in tensors):
         raise SdvarError(f"{who}: operands live on different devices")
     return _MlpGrad.apply(x, weight1, weight2, bias1, bias2, _gemm_mode)
+
+
+class _XentGrad(torch.autograd.Function):
+    """Label-smoothed cross-entropy with a HIP backward: forward = sdvar_xent_train_fwd, backward = one sdvar_xent_train_bwd call (csrc/xent_train.hip).  Saved: the
+    logits, the targets and lse (one float per row); reduction 'mean' also keeps the forward's two doubles {sum, counted rows}."""
+
+    @staticmethod
+    def forward(ctx, logits, target, eps, reduction, ignore_index):
+        loss, lse, sums, reduced = E.xent_train_fwd(logits, target, eps, ignore_index, reduction, True)
+        ctx.save_for_backward(logits, target, lse, *(() if sums is None else (sums,)))
+        ctx.xent = (eps, reduction, ignore_index)
+        return loss if reduction == "none" else reduced
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise SdvarError("cross_entropy: double backward (backward(create_graph=True), or torch.autograd.grad of a gradient) is not supported; "
+                             "call backward() without create_graph")
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        logits, target, lse, *rest = ctx.saved_tensors
+        eps, reduction, ignore_index = ctx.xent
+        if g.dtype != torch.float32:
+            raise SdvarError(f"cross_entropy: the gradient of the loss is {g.dtype} but the loss is float32")
+        g = g.contiguous()            # a stride-0 expansion (loss.sum().backward()) becomes rows floats; a dense gradient is read in place
+        return E.xent_train_bwd(logits, target, lse, g, reduction, rest[0] if rest else None, eps, ignore_index), None, None, None, None
+
+
+def cross_entropy(input, target, label_smoothing: float = 0.0, reduction: str = "none", ignore_index: int = -100, weight=None):
+    """The loss of the reference's trainer (trainer.py:37-38, called at :112 and reduced at :116-120) with torch's definition of label smoothing:
+    loss = (1 - eps)(lse - x_t) + eps (lse - mean_j x_j).  input (N, V) float32 on the GPU, V a multiple of 4; rows with unit column stride, a row stride that is a
+    multiple of 4 and 16-byte alignment are read in place (logits[:n], logits[:, :V] of a wider buffer), anything else is copied once.  target (N,) int64 class
+    indices.  reduction 'none' -> (N,) float32; 'mean' (divided by the rows whose target is not ignore_index, as torch) / 'sum' -> a 0-dim float32 tensor, reduced in
+    float64 in a fixed order.  A target == ignore_index gives loss 0 and gradient 0; any other target outside [0, V) gives NaN for that row's loss and gradient (torch
+    asserts on the device instead) and leaves every other row alone.  One pass over the logits, one float per row saved for the backward, which is one read and one
+    write; deterministic; neither direction synchronises with the host.  Under torch.no_grad(), or when input does not require grad, the same kernel runs without
+    writing lse: the same loss bits.  Not autocast-aware: the input must already be float32 (the reference's get_logits ends in .float(), var.py:125).  No class
+    weights, no soft targets, no double backward."""
+    who = "cross_entropy"
+    if weight is not None:
+        raise SdvarError(f"{who}: weight= (per-class weights) is not supported; pass weight=None (the reference's trainer uses none) and weigh the 'none' losses yourself")
+    if reduction not in E.XENT_REDUCTIONS:
+        raise SdvarError(f"{who}: reduction {reduction!r} is not one of {E.XENT_REDUCTIONS}")
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise SdvarError(f"{who}: label_smoothing {label_smoothing} is outside [0, 1]")
+    if not isinstance(input, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise SdvarError(f"{who}: input and target must be tensors")
+    if input.dtype in _HALF_DTYPES or input.dtype == torch.float64:
+        raise SdvarError(f"{who}: input is {input.dtype}; only float32 logits are supported - pass input.float() (the reference's get_logits already ends in .float())")
+    if input.dtype != torch.float32:
+        raise SdvarError(f"{who}: input is {input.dtype}; only float32 logits are supported")
+    if input.dim() != 2:
+        raise SdvarError(f"{who}: input has {input.dim()} dims, expected (N, V) - flatten it as the trainer does: input.view(-1, V), target.view(-1)")
+    if not input.is_cuda or not target.is_cuda or input.device != target.device:
+        raise SdvarError(f"{who}: input ({input.device}) and target ({target.device}) must be on one GPU (the kernels run on the GPU; there is no CPU path)")
+    if target.dtype != torch.int64 or target.dim() != 1 or target.shape[0] != input.shape[0]:
+        raise SdvarError(f"{who}: target is {target.dtype} of shape {tuple(target.shape)}; expected int64 class indices of shape ({input.shape[0]},) (no soft targets)")
+    N, V = input.shape
+    if N < 1 or V < 4 or V % 4:
+        raise SdvarError(f"{who}: input of shape {(N, V)}: N must be at least 1 and V a positive multiple of 4")
+    target = target.detach().contiguous()
+    grad = torch.is_grad_enabled() and input.requires_grad
+    x = input if grad else input.detach()
+    ld = V if N == 1 else x.stride(0)
+    if x.stride(1) != 1 or ld < V or ld % 4 or x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.contiguous_format)           # differentiable: the gradient flows back through the copy
+    if grad:
+        return _XentGrad.apply(x, target, eps, reduction, int(ignore_index))
+    loss, _, _, reduced = E.xent_train_fwd(x, target, eps, int(ignore_index), reduction, False)
+    return loss if reduction == "none" else reduced
+
+
+class CrossEntropyLoss:
+    """nn.CrossEntropyLoss's call shape on cross_entropy: a plain callable (no parameters, no buffers) for the trainer's `train_loss` / `val_loss` attributes
+    (trainer.py:37-38)."""
+
+    def __init__(self, label_smoothing: float = 0.0, reduction: str = "mean", ignore_index: int = -100, weight=None):
+        if weight is not None:
+            raise SdvarError("CrossEntropyLoss: weight= (per-class weights) is not supported; pass weight=None")
+        if reduction not in E.XENT_REDUCTIONS:
+            raise SdvarError(f"CrossEntropyLoss: reduction {reduction!r} is not one of {E.XENT_REDUCTIONS}")
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise SdvarError(f"CrossEntropyLoss: label_smoothing {label_smoothing} is outside [0, 1]")
+        self.label_smoothing, self.reduction, self.ignore_index = float(label_smoothing), reduction, int(ignore_index)
+
+    def __call__(self, input, target):
+        return cross_entropy(input, target, self.label_smoothing, self.reduction, self.ignore_index)
+
+    forward = __call__
+
+    def __repr__(self) -> str:
+        return f"seam.CrossEntropyLoss(label_smoothing={self.label_smoothing}, reduction={self.reduction!r}, ignore_index={self.ignore_index})"
+
+
+def install_trainer(trainer) -> None:
+    """Set the two loss attributes of a VARTrainer-like object (trainer.py:36-38): `train_loss` = CrossEntropyLoss(label_smoothing=trainer.label_smooth,
+    reduction='none') - the loss train_step backpropagates (:112-120) - and `val_loss` = CrossEntropyLoss(label_smoothing=0.0, reduction='mean'), which eval_ep and
+    the log lines call.  The trainer's code is not edited: both are instance attributes it looks up at every call."""
+    if not hasattr(trainer, "label_smooth"):
+        raise SdvarError("install_trainer: the object has no `label_smooth` attribute (a VARTrainer sets it at trainer.py:36); set train_loss / val_loss yourself "
+                         "with seam.CrossEntropyLoss")
+    trainer.train_loss = CrossEntropyLoss(label_smoothing=trainer.label_smooth, reduction="none")
+    trainer.val_loss = CrossEntropyLoss(label_smoothing=0.0, reduction="mean")
 
 
 def install(module, model=None) -> None:
