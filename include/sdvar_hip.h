@@ -284,7 +284,16 @@ int sdvar_op_gemm_f16x2(const uint16_t* Xp, uint64_t x_plane_stride, const uint1
  *   2  bf16x3 planes: K (R, H, 3, Lmax, 64), V^T (R, H, 3, 64, Lmax) with bits 2 and 3 of the key position swapped inside every 16 keys (attention_bf16x3.hip)
  *   3  f16x2 planes:  K AND V (R, H, 2, Lmax, 64) fp16, high plane then low plane, one 128-byte row per position (gemm mode f16x2, the default)
  *   4  one fp16 plane: K and V (R, H, 1, Lmax, 64) = the fp16 KV cache of BASELINE config P4 in the layout of format 3
- * Formats 2-4 need Lmax % 64 == 0 and a zero-initialised cache (whole 32-key tiles are streamed; rows past the valid keys must be finite). */
+ * Formats 2-4 need Lmax % 64 == 0 and a zero-initialised cache (whole 32-key tiles are streamed; rows past the valid keys must be finite).
+ * "Finite" is all that is asked of rows [Ktot, Lmax): after sdvar_kv_set_len rolls the cursor back (a rejected round of the speculative sampler) they still hold that
+ * round's keys and values, and the next append overwrites only its own window.  Attention replaces the scores of those rows before the softmax and gives them a weight
+ * of exactly 0: outputs over +-65504 (formats 3, 4) or +-3e38 (format 2) in every plane of the tail are bit-identical to outputs over a zero tail; an inf or NaN there
+ * (0 x inf) is not.  Formats 0 and 1 never read past Ktot.
+ * Range: formats 3 AND 4 store a finite |k| or |v| beyond 65504 as +-65504 (the append clamps before the fp16 cast; the low plane of format 3 is then zero), so no
+ * append of finite values can put an inf into the planes; format 1 casts as torch's .half() does (inf beyond 65520).  Format 2 has no range limit.
+ * Every format normalises with the same fp32 arithmetic: q_out and the fp32 value of k that the format then rounds or splits are the same bits in all five formats
+ * (format 2 sums to format 0's bits exactly, format 3 to 2^-21.9 relative / 2^-24.9 absolute, formats 1 and 4 are its fp16 rounding).
+ * scale_mul == NULL (attn_l2_norm = False): q_out = q * 2^-5 exactly, k is stored as it comes; a zero q or k vector gives zeros (the norm is clamped at 1e-12). */
 int sdvar_op_qk_norm_append(const float* qkv, const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int32_t kv_f16, int32_t R,
                             int32_t l, int32_t H, int32_t Lmax, int32_t pos0, void* stream);
 /* q (R,H,l,64), caches in format kv_f16 (above) with Ktot valid keys, out (R,l,H*64) fp32 or out_planes (K-blocked operand planes); queries >= qbeg[j] see keys < vis[j] */

@@ -233,6 +233,20 @@ int ln_modulate(float* x, const float* scale, const float* shift, float* out, ui
 }
 
 // ------------------------------------------------------------------------------------------------ qk_norm_append
+// Sum of one value per channel over the 64 channels of a head (lane = channel), in the order in which the two planes kernels below add their squares: eight
+// consecutive channels left to right, then the eight partial sums pairwise at distances 8, 16, 32.  wave_sum adds at distances 32 .. 1 instead, which gave the fp32 and
+// fp16 caches a norm one ulp away from the planes caches' on some vectors (tests/test_gpu_block_hard.py, sampler append pattern and edge vectors, formats 2 and 3
+// against format 0): now every cache format normalises q and k to the same fp32 bits.  The eight gathers do not depend on each other.
+__device__ __forceinline__ float head_sum(float x, int lane) {
+    const int base = lane & ~7;
+    float s = __shfl(x, base, 64);
+#pragma unroll
+    for (int e = 1; e < 8; ++e) s += __shfl(x, base + e, 64);
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+
 // qkv (R*l, 3C) with the bias already added.  One wave per (row, head); lane = channel.
 // q_out (R, H, l, 64); k_cache / v_cache (R, H, Lmax, 64) written at positions pos0 .. pos0+l-1.
 template <typename KV>
@@ -259,8 +273,8 @@ __global__ __launch_bounds__(256) void qk_norm_append_kernel(const float* __rest
     // attn_l2_norm=False models (scale_mul == null, basic_var.py:71-72): q and k stay as they are and the softmax scale 0.25 / sqrt(64) = 2^-5 is
     // folded into q (exact)
     const bool l2 = scale_mul != nullptr;
-    const float qn = l2 ? fmaxf(sqrtf(wave_sum(q * q)), 1e-12f) : 1.0f;
-    const float kn = l2 ? fmaxf(sqrtf(wave_sum(k * k)), 1e-12f) : 1.0f;
+    const float qn = l2 ? fmaxf(sqrtf(head_sum(q * q, lane)), 1e-12f) : 1.0f;
+    const float kn = l2 ? fmaxf(sqrtf(head_sum(k * k, lane)), 1e-12f) : 1.0f;
     const float sm = l2 ? expf(fminf(scale_mul[h], 4.605170249938965f)) : 0.03125f;    // log(100) as the reference's float32 clamp
     q_out[(((size_t)r * H + h) * l + t) * 64 + lane] = l2 ? (q / qn) * sm : q * sm;
     const size_t c = (((size_t)r * H + h) * Lmax + pos0 + t) * 64 + lane;
