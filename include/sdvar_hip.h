@@ -509,6 +509,35 @@ int sdvar_op_sdpa_h_bwd(const void* q, const void* k, const void* v, const void*
                         int32_t bias_kind /*0 none | 1 fp32 | 2 uint8 keep | 3 additive in dtype*/, const int64_t* bias_strides /*host, 3*/, const uint8_t* skip_map,
                         int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, double scale, void* stream);
 
+/* The half-precision FFN of a model run under torch.autocast (sdvar_amd/seam.py fused_mlp_func_amp / fused_mlp_func_amp_grad; csrc/gemm_half.hip, csrc/mlp_half.hip).
+ * Added without an ABI bump (purely additive).  dtype: 1 = fp16, 2 = bf16.  An OPERAND is one K-blocked plane of that dtype: element (row, k) of a (rows x K) matrix at
+ * ((k/32)*rows + row)*32 + k%32, K % 32 == 0, rows * K elements; every pointer 16-byte aligned.  Nothing is scaled or clamped anywhere: an fp16 overflow is +-inf.
+ *
+ * sdvar_op_gemm_h: out[M,N] = epilogue(X[M,K] . W[N,K]^T + bias[N]), x = operand (M x K), w = operand (N x K).  Arithmetic contract:
+ *   - every product on the half matrix cores (v_mfma_f32_32x32x16_f16 / _bf16: exact products, fp32 accumulation over k in ascending order, one chain per output element;
+ *     fp16 subnormal inputs are kept); the fp32 bias (may be NULL) is added to the fp32 sum; nothing is rounded before that.
+ *   - epilogue 0: out (row-major, leading dimension ldo, ldo % 4 == 0) = that fp32 value (out_dtype 0) or the value rounded once to dtype, nearest even, overflow = inf
+ *     (out_dtype = dtype).  h_out and pre_out must be NULL.
+ *   - epilogue 1 (fc1; N % 32 == 0): p = dtype(sum + bias); h = dtype(gelu_tanh(float(p))) with the exp / rcp form of sdvar_op_gemm_f16x2's GELU; h_out = the OPERAND
+ *     (M x N) of the next GEMM; pre_out (may be NULL) = p row-major dense (M, N) in dtype.  out must be NULL.
+ *   - any M >= 1 (edge rows are clamped on load and never stored), N % 8 == 0, K % 32 == 0.  No split-K, no atomics: repeats are bit-identical, and an element's bits do
+ *     not depend on M or N.  Argument errors (NULL / misaligned pointers, K % 32, N % 8, unknown dtype / epilogue / out_dtype) are reported before any launch. */
+int sdvar_op_gemm_h(const void* x, const void* w, int32_t dtype, const float* bias, void* out, int32_t out_dtype, int32_t ldo, void* h_out, void* pre_out, int32_t M, int32_t N,
+                    int32_t K, int32_t epilogue, void* stream);
+/* x row-major (rows, cols), leading dimension ldx, fp32 (x_dtype 0; ldx % 4 == 0) or already of dtype (x_dtype = dtype; ldx % 8 == 0) -> an OPERAND of dtype.  fp32 values are
+ * rounded to nearest even - the bits of a cast - and an fp16 overflow becomes inf; half values are copied bit for bit.  transpose 0: the operand (rows x cols), cols % 32 == 0.
+ * transpose 1: the operand of x^T, (cols x Kp), Kp = rows rounded up to 32, cols % 8 == 0; the tail k >= rows is written as zeros by this kernel.  colsum_part (transpose 1 only,
+ * may be NULL) = float[Kp/32][cols]: the column sums of the ROUNDED x over each block of 32 rows, added in row order in fp32 (finish with sdvar_op_colsum); with it, out may be
+ * NULL. */
+int sdvar_op_half_operand(const void* x, int32_t x_dtype, int32_t ldx, int32_t rows, int32_t cols, int32_t dtype, int32_t transpose, void* out, float* colsum_part, void* stream);
+/* dh fp32 (M, N) dense and pre = the half pre-activation p (M, N) dense in dtype (sdvar_op_gemm_h epilogue 1), N % 32 == 0, read once:
+ *   dpre = dtype(dh * g'(float(p))), h = dtype(gelu_tanh(float(p))) - the bits the fc1 epilogue wrote; g' is the exp / rcp formulation of sdvar_op_gelu_bwd (gelu_kind 1): finite
+ *   at both ends (0 / 1 at large |p|, no 0 * inf), so dpre is inf or NaN only where dh is.
+ * Outputs, each may be NULL: dpre = OPERAND (M x N); dpre_t, h_t = OPERANDS (N x Mp) of the transposes, Mp = M rounded up to 32, zero tail written here; colsum_part =
+ * float[Mp/32][N], the column sums of the ROUNDED dpre over each block of 32 rows, added in row order in fp32 (finish with sdvar_op_colsum).  dh may be NULL when only h_t is
+ * asked for. */
+int sdvar_op_gelu_bwd_h(const float* dh, const void* pre, int32_t M, int32_t N, int32_t dtype, void* dpre, void* dpre_t, void* h_t, float* colsum_part, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

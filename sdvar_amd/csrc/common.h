@@ -140,6 +140,17 @@ __device__ __forceinline__ void split4h_pk(const float* v, uint2& h, uint2& l) {
     split2h_pk_raw(c[0], c[1], h.x, l.x); split2h_pk_raw(c[2], c[3], h.y, l.y);
 }
 
+// ---- one fp16 / bf16 plane (gemm_half.hip, mlp_half.hip): two fp32 -> the packed halves of the dtype, round to nearest even (v_cvt_pk_f16_f32: an overflow is inf, nothing
+// is clamped; v_cvt_pk_bf16_f32), and the two halves of a packed word back as fp32 (exact).  bf is a compile-time constant or wave-uniform.
+typedef __bf16 bf16x2h __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t half_pack2(float a, float b, bool bf) {
+    const f32x2p v = {a, b};
+    if (bf) return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2h));
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2p));
+}
+__device__ __forceinline__ float half_lo(uint32_t w, bool bf) { return bf ? __uint_as_float(w << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)); }
+__device__ __forceinline__ float half_hi(uint32_t w, bool bf) { return bf ? __uint_as_float(w & 0xFFFF0000u) : (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
+
 // ---- GELU(tanh), the two forms of the GEMM epilogues (gemm.hip / gemm_bf16x3.hip: gelu_tanh; gemm_f16x2.hip: gelu_tanh_h) - here so that the FFN backward's
 // producers (mlp_bwd.hip) recompute the forward's h bit for bit
 __device__ __forceinline__ float gelu_tanh(float x) {
@@ -157,6 +168,21 @@ __device__ __forceinline__ float gelu_tanh_h(float x) {
     const float w = x * __builtin_fmaf(x * x, C1, C0);
     const float e = __builtin_amdgcn_exp2f(w);                               // exp(-2u); +inf for very negative x: the quotient is then 0
     return x * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
+// g(x) as the forward of the mode computes it (kind 0: gelu_tanh, modes f32 and bf16x3; 1: gelu_tanh_h, mode f16x2) and g'(x).  With u = sqrt(2/pi)(x + 0.044715 x^3) and
+// s = sigmoid(2u) = 1 / (1 + e), e = exp(-2u):  g = x s,  g' = s + x s (1 - s) 2u',  1 - s = e s.  e is +inf for very negative x (s = 0) and 0 for very positive x;
+// e is clamped to 2^126 and x to +-1e5 in the second term, so every factor is finite and the term is exactly 0 at both ends (no 0 * inf): g' -> 0 / 1.
+__device__ __forceinline__ void gelu_val_grad(float x, int kind, float& g, float& dg) {
+    const float C0 = -2.3022081986f, C1 = -0.10294324f;            // gelu_tanh_h's constants: -2 u log2 e = x (C0 + C1 x^2)
+    const float e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, C1, C0));
+    const float s = __builtin_amdgcn_rcpf(1.0f + e);
+    g = kind ? x * s : gelu_tanh(x);
+    const float xc = fminf(fmaxf(x, -1e5f), 1e5f);
+    const float q = xc * (1.5957691216f + 0.2140644488f * (xc * xc));       // x 2u' = x 2 sqrt(2/pi) (1 + 3 * 0.044715 x^2)
+    const float t = fminf(e, 0x1p126f) * s;                                 // 1 - s
+    dg = s + (q * t) * s;
+    dg = x != x ? x : dg;
 }
 
 // Output-plane format of the producers of GEMM operands (ln_modulate, attention, GELU epilogues): none, three bf16 planes, two fp16 planes

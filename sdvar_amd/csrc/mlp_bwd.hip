@@ -27,20 +27,7 @@ int weight_scale_f16(const float* w, size_t n, float* sc, hipStream_t stream);  
 enum { OPF_F32 = 0 };               // next to PLANES_F16X2 / PLANES_BF16X3
 constexpr int TK = 32, TC = 64, TS = 65;
 
-// g(x) as the forward of the mode computes it (kind 0: gelu_tanh, modes f32 and bf16x3; 1: gelu_tanh_h, mode f16x2) and g'(x).  With u = sqrt(2/pi)(x + 0.044715 x^3) and
-// s = sigmoid(2u) = 1 / (1 + e), e = exp(-2u):  g = x s,  g' = s + x s (1 - s) 2u',  1 - s = e s.  e is +inf for very negative x (s = 0) and 0 for very positive x;
-// e is clamped to 2^126 and x to +-1e5 in the second term, so every factor is finite and the term is exactly 0 at both ends (no 0 * inf): g' -> 0 / 1.
-__device__ __forceinline__ void gelu_val_grad(float x, int kind, float& g, float& dg) {
-    const float C0 = -2.3022081986f, C1 = -0.10294324f;            // gelu_tanh_h's constants: -2 u log2 e = x (C0 + C1 x^2)
-    const float e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, C1, C0));
-    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-    g = kind ? x * s : gelu_tanh(x);
-    const float xc = fminf(fmaxf(x, -1e5f), 1e5f);
-    const float q = xc * (1.5957691216f + 0.2140644488f * (xc * xc));       // x 2u' = x 2 sqrt(2/pi) (1 + 3 * 0.044715 x^2)
-    const float t = fminf(e, 0x1p126f) * s;                                 // 1 - s
-    dg = s + (q * t) * s;
-    dg = x != x ? x : dg;
-}
+// gelu_val_grad (g and g' of both GELU forms) lives in common.h: the half-precision producers (mlp_half.hip) share it.
 
 // eight consecutive values of one operand row -> memory, at element (row, k) of a (rows x K) operand; k % 8 == 0
 __device__ __forceinline__ void store_operand8(void* out, size_t ps, int fmt, int row, int k, int rows, int ldo, const float* v, bool live) {

@@ -138,6 +138,9 @@ _SIGNATURES = {
     "sdvar_op_sdpa_hm_lse": (_I, [_P, _P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D, _P]),
     "sdvar_op_sdpa_h_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D,
                                  _P]),
+    "sdvar_op_gemm_h": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "sdvar_op_half_operand": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "sdvar_op_gelu_bwd_h": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
     "sdvar_debug_set_gemm_stamps": (_I, [_P]),
     "sdvar_debug_set_qkv_fuse": (_I, [_I]),

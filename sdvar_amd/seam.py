@@ -16,11 +16,15 @@ maintainer of the reference who wants the kernels without adopting the sampling 
 
     seam.install_train_amp(basic_var, model)    # TRAINING under torch.autocast (fp16 + GradScaler, or bf16): slow_attn_amp_grad + flash_attn_func_grad
 
+    seam.install_train_amp(basic_var, model, ffn="half")     # ... and fused_mlp_func_amp_grad: the FFN on the half matrix cores too, forward and backward
+    seam.install_amp(basic_var, model, ffn_half=True)        # inference under autocast with fused_mlp_func_amp in the FFN slots
+
     seam.install_trainer(trainer)           # the VARTrainer's train_loss / val_loss (trainer.py:37-38): label-smoothed cross-entropy, HIP forward + backward
 
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
 slow_attn_amp_grad / memory_efficient_attention_amp_grad / flash_attn_func_grad (the half and mixed operands of autocast; backward = sdvar_op_sdpa_h_bwd) and
-fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward):
+fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward) and fused_mlp_func_amp_grad (autocast's half dtype;
+sdvar_op_gemm_h on operands from csrc/mlp_half.hip):
 no backward, no dropout, head dim 64.  `slow_attn`, `memory_efficient_attention` and `fused_mlp_func` take fp32 operands only;
 `flash_attn_func` takes fp16 or bf16 operands only (and no mask); `slow_attn_amp` / `memory_efficient_attention_amp` take a half value with query and key each
 half or fp32, and masks.  Anything else raises SdvarError - there is no fall-back to torch.
@@ -50,7 +54,7 @@ from .engine import SdvarError
 __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
            "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
-           "cross_entropy", "CrossEntropyLoss", "install_trainer"]
+           "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -794,6 +798,211 @@ def fused_mlp_func_grad(x, weight1, weight2, bias1=None, bias2=None, activation:
     return _MlpGrad.apply(x, weight1, weight2, bias1, bias2, _gemm_mode)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the half-precision FFN (torch.autocast)
+def _autocast_gpu_dtype():
+    """The autocast dtype of the GPU when autocast is enabled for it, else None."""
+    if hasattr(torch, "get_autocast_dtype"):
+        return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+    return torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None
+
+
+def _mlp_amp_check(who: str, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, grad: bool):
+    """The argument checks of the half-precision FFN slots; grad = the caller has a backward.  Returns (half dtype, Cin, hid, Cout).  Nothing here touches the library."""
+    if activation != "gelu_approx":
+        raise SdvarError(f"{who}: activation {activation!r}; only 'gelu_approx' (tanh GELU) is built")
+    if return_residual:
+        raise SdvarError(f"{who}: return_residual=True is not supported")
+    if process_group is not None:
+        raise SdvarError(f"{who}: a process group (tensor-parallel MLP) is not supported")
+    named = (("x", x), ("weight1", weight1), ("weight2", weight2)) + tuple((n, b) for n, b in (("bias1", bias1), ("bias2", bias2)) if b is not None)
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise SdvarError(f"{who}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
+        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+    half = x.dtype if x.dtype in _HALF_DTYPES else _autocast_gpu_dtype()
+    if half not in _HALF_DTYPES:
+        twin = "fused_mlp_func_grad" if grad else "fused_mlp_func"
+        raise SdvarError(f"{who}: x is {x.dtype} and torch.autocast is not enabled for the GPU with float16 / bfloat16: there is no half dtype to compute in - "
+                         f"call it under torch.autocast or with a half x, or use fused_mlp_func / {twin} for float32 arithmetic")
+    for name, t in named:
+        if t.dtype != torch.float32 and t.dtype != half:
+            raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype} but the half dtype of the call is {half} (every operand must be {half} or float32)")
+        if not grad and t.requires_grad and torch.is_grad_enabled():
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use fused_mlp_func_amp_grad)")
+    if weight1.dim() != 2 or weight2.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight1.shape[1] or weight2.shape[1] != weight1.shape[0]:
+        raise SdvarError(f"{who}: shapes do not chain: x {tuple(x.shape)}, weight1 {tuple(weight1.shape)}, weight2 {tuple(weight2.shape)}")
+    Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
+    if Cin % 32 or hid % 32:
+        raise SdvarError(f"{who}: in_features {Cin} and hidden_features {hid} must be multiples of 32")
+    if Cout % 8:
+        raise SdvarError(f"{who}: out_features {Cout} must be a multiple of 8")
+    for name, b, n in (("bias1", bias1, hid), ("bias2", bias2, Cout)):
+        if b is not None and tuple(b.shape) != (n,):
+            raise SdvarError(f"{who}: {name} has shape {tuple(b.shape)}, expected ({n},)")
+    if any(t.device != x.device for _, t in named):
+        raise SdvarError(f"{who}: operands live on different devices")
+    return half, Cin, hid, Cout
+
+
+def _dense16(t: torch.Tensor) -> torch.Tensor:
+    """t itself when it is dense and 16-byte aligned, else one fresh dense copy (.contiguous() would hand back a dense tensor at a misaligned address)."""
+    return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _in_code(t: torch.Tensor) -> int:
+    """sdvar_op_half_operand's input code: 0 = float32, else the half dtype's."""
+    return 0 if t.dtype == torch.float32 else _HALF_DTYPES[t.dtype]
+
+
+def _half_operand(t: torch.Tensor, half, transpose: bool, part: Optional[torch.Tensor] = None, want_out: bool = True):
+    """The K-blocked `half` operand of a dense, 16-byte aligned 2-D tensor (fp32: rounded to nearest even as it is read; half: its bits) or of its transpose
+    ((cols x pad32(rows)), zero tail written by the kernel)."""
+    rows, cols = t.shape
+    out = torch.empty(cols * _pad32(rows) if transpose else rows * cols, dtype=torch.int16, device=t.device) if want_out else None
+    # ldx = cols, not t.stride(0): a one-row tensor counts as dense whatever its row stride is
+    E._check(E.load_library().sdvar_op_half_operand(_p(t), _in_code(t), cols, rows, cols, _HALF_DTYPES[half], int(transpose), _p(out), _p(part), E._stream()))
+    return out
+
+
+def _weight_operand_h(w: torch.Tensor, half, transpose: bool) -> torch.Tensor:
+    """The half operand of a weight ("hn") or of its transpose ("ht"), cached per (kind, half dtype, weight); an entry whose weight moved on is replaced."""
+    return _cached_planes("ht" if transpose else "hn", w, f"{half}/{w.dtype}", lambda: (_half_operand(_dense16(w.detach()), half, transpose), None))[0]
+
+
+def _bias_f32(b: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if b is None else _dense16(b.detach().float())
+
+
+def _gemm_h(half, A, B, bias, out, M: int, N: int, K: int) -> None:
+    """out (M, N) dense, fp32 or `half` = A (M x K) . B (N x K)^T + bias on half operands (sdvar_op_gemm_h, epilogue 0)."""
+    dt = _HALF_DTYPES[half]
+    E._check(E.load_library().sdvar_op_gemm_h(_p(A), _p(B), dt, _p(bias), _p(out), 0 if out.dtype == torch.float32 else dt, N, None, None, M, N, K, 0, E._stream()))
+
+
+def _mlp_amp_forward(x, weight1, weight2, bias1, bias2, half, keep_pre: bool):
+    """(out, xr, p).  The two launches of sdvar_op_gemm_h behind one operand pass over x; keep_pre: fc1's epilogue also writes p (M, hid) row-major in `half` -
+    the other outputs keep their bits."""
+    Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
+    lib, st, dt = E.load_library(), E._stream(), _HALF_DTYPES[half]
+    xr = _dense16(x.detach().reshape(-1, Cin))
+    M = xr.shape[0]
+    out = torch.empty(tuple(x.shape[:-1]) + (Cout,), dtype=half, device=x.device)
+    if M == 0:
+        return out, xr, None
+    xop = _half_operand(xr, half, False)
+    w1op, w2op = _weight_operand_h(weight1, half, False), _weight_operand_h(weight2, half, False)
+    b1, b2 = _bias_f32(bias1), _bias_f32(bias2)
+    hop = torch.empty(M * hid, dtype=torch.int16, device=x.device)
+    p = torch.empty(M, hid, dtype=half, device=x.device) if keep_pre else None
+    E._check(lib.sdvar_op_gemm_h(_p(xop), _p(w1op), dt, _p(b1), None, 0, 0, _p(hop), _p(p), M, hid, Cin, 1, st))
+    E._check(lib.sdvar_op_gemm_h(_p(hop), _p(w2op), dt, _p(b2), _p(out), dt, Cout, None, None, M, Cout, hid, 0, st))
+    return out, xr, p
+
+
+def fused_mlp_func_amp(x, weight1, weight2, bias1=None, bias2=None, activation: str = "gelu_approx", save_pre_act: bool = False, return_residual: bool = False,
+                       checkpoint_lvl: int = 0, heuristic=0, process_group=None):
+    """The `fused_mlp_func` slot for a model run under torch.autocast: fc2(gelu_tanh(fc1(x))) on the HALF matrix cores, what autocast's own F.linear / F.gelu pair
+    computes.  The half dtype is x.dtype when x is float16 / bfloat16, else the GPU's autocast dtype; with neither it raises (use fused_mlp_func).  x (..., C), weight1
+    (hidden, C), weight2 (out, hidden) are each float32 or that dtype - a float32 operand is rounded to nearest even as it is read, the bits of .to(dtype) without the
+    pass over memory - and the biases are float32 or half and enter as float32.  Contract: p = half(fp32acc(x_h W1_h^T) + b1), h = half(gelu_tanh(float(p))),
+    y = half(fp32acc(h W2_h^T) + b2); nothing is clamped, an fp16 overflow is +-inf.  Two launches of sdvar_op_gemm_h (one fp16 / bf16 MFMA per product where mode f16x2
+    issues three); weight operands are cached per (weight, dtype) and replaced when the weight is updated in place.  C and hidden must be multiples of 32, out of 8.
+    Returns (..., out) in the half dtype.  Deterministic.  save_pre_act / checkpoint_lvl / heuristic are accepted and ignored."""
+    half, _, _, _ = _mlp_amp_check("fused_mlp_func_amp", x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, False)
+    return _mlp_amp_forward(x, weight1, weight2, bias1, bias2, half, False)[0]
+
+
+class _MlpAmpGrad(torch.autograd.Function):
+    """The half-precision FFN with a HIP backward: four launches of sdvar_op_gemm_h on operands produced by csrc/mlp_half.hip.  Saved: x, the weights and the half
+    pre-activation p."""
+
+    @staticmethod
+    def forward(ctx, x, weight1, weight2, bias1, bias2, half):
+        out, xr, p = _mlp_amp_forward(x, weight1, weight2, bias1, bias2, half, True)
+        ctx.save_for_backward(xr, weight1, weight2, *(() if p is None else (p,)))
+        ctx.mlp = (half, tuple(x.shape), None if bias1 is None else bias1.dtype, None if bias2 is None else bias2.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        xr, weight1, weight2, *rest = ctx.saved_tensors
+        half, xshape, b1dt, b2dt = ctx.mlp
+        nx, nw1, nw2, nb1, nb2 = ctx.needs_input_grad[:5]
+        Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
+        M, dev = xr.shape[0], xr.device
+        if dy.dtype != half:
+            raise SdvarError(f"fused_mlp_func_amp_grad: the gradient of the output is {dy.dtype} but the output is {half}; the backward reads dy in the output's dtype")
+        if M == 0:
+            z = lambda need, dtype, *shape: torch.zeros(*shape, dtype=dtype, device=dev) if need else None
+            return z(nx, xr.dtype, *xshape), z(nw1, weight1.dtype, hid, Cin), z(nw2, weight2.dtype, Cout, hid), z(nb1, b1dt, hid), z(nb2, b2dt, Cout), None
+        p = rest[0]
+        lib, st, dt, Mp = E.load_library(), E._stream(), _HALF_DTYPES[half], _pad32(M)
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        operand = lambda n: torch.empty(n, dtype=torch.int16, device=dev)
+        dy = _dense16(dy.reshape(M, Cout))          # stride-0 expansions, transposed consumers, a dense tensor at a misaligned address: one fresh dense copy
+        need_dh = nx or nw1 or nb1
+        dx = dw1 = dw2 = db1 = db2 = None
+        dyt = None
+        if nw2 or nb2:                               # dy^T, and db2's 32-row partials from the same pass
+            part2 = f32(Mp // 32, Cout) if nb2 else None
+            dyt = _half_operand(dy, half, True, part2, want_out=bool(nw2))
+            if nb2:
+                db2 = f32(Cout)
+                E._check(lib.sdvar_op_colsum(_p(part2), Cout, Mp // 32, Cout, _p(db2), st))
+                db2 = db2.to(b2dt)
+        dh = dpre = dpre_t = h_t = part = None
+        if need_dh:
+            dh = f32(M, hid)
+            _gemm_h(half, _half_operand(dy, half, False), _weight_operand_h(weight2, half, True), None, dh, M, hid, Cout)
+            dpre = operand(M * hid) if nx else None
+            dpre_t = operand(hid * Mp) if nw1 else None
+            part = f32(Mp // 32, hid) if nb1 else None
+        if nw2:
+            h_t = operand(hid * Mp)
+        if need_dh or nw2:
+            E._check(lib.sdvar_op_gelu_bwd_h(_p(dh), _p(p), M, hid, dt, _p(dpre), _p(dpre_t), _p(h_t), _p(part), st))
+        if nx:
+            dx = torch.empty(M, Cin, dtype=xr.dtype, device=dev)
+            _gemm_h(half, dpre, _weight_operand_h(weight1, half, True), None, dx, M, Cin, hid)
+            dx = dx.view(xshape)
+        if nw2:
+            dw2 = torch.empty(Cout, hid, dtype=weight2.dtype, device=dev)
+            _gemm_h(half, dyt, h_t, None, dw2, Cout, hid, Mp)
+        if nw1:
+            dw1 = torch.empty(hid, Cin, dtype=weight1.dtype, device=dev)
+            _gemm_h(half, dpre_t, _half_operand(xr, half, True), None, dw1, hid, Cin, Mp)
+        if nb1:
+            db1 = f32(hid)
+            E._check(lib.sdvar_op_colsum(_p(part), hid, Mp // 32, hid, _p(db1), st))
+            db1 = db1.to(b1dt)
+        return dx, dw1, dw2, db1, db2, None
+
+
+def fused_mlp_func_amp_grad(x, weight1, weight2, bias1=None, bias2=None, activation: str = "gelu_approx", save_pre_act: bool = False, return_residual: bool = False,
+                            checkpoint_lvl: int = 0, heuristic=0, process_group=None):
+    """fused_mlp_func_amp under autograd (the reference's mixed-precision trainer runs loss.backward() through basic_var.py:46-50 under torch.autocast): signature,
+    dtype rule, operand rules and argument errors as fused_mlp_func_amp, plus out_features % 32 == 0 under grad.  With grad mode off, or no operand requiring grad, it
+    IS fused_mlp_func_amp (same launches, same bits).  Otherwise fc1's epilogue also writes the half pre-activation p (M, hidden) - the only tensor saved besides x and
+    the weights, half of what fused_mlp_func_grad saves - and the output keeps its bits.  Backward: dh = fp32acc(dy W2_h), dpre = half(dh gelu'(p)), dx = dpre W1_h,
+    dW2 = dy^T h, dW1 = dpre^T x_h as four launches of sdvar_op_gemm_h on operands written by csrc/mlp_half.hip (transposed, zero-padded to K % 32 == 0; h recomputed
+    from p with the forward's bits), db1 = sum dpre and db2 = sum dy by fixed-order column sums of the rounded values.  Gradients come back in each operand's OWN dtype:
+    unrounded float32 for a float32 x / weight / bias (the reference's case: float32 x and master weights), half otherwise.  dy must have the output's dtype; one that
+    is not dense or not 16-byte aligned is copied once.  Deterministic; only the gradients autograd asks for are computed, and each has the bits it has in the full
+    run.  Nothing is clamped: an fp16 overflow is +-inf and reaches the GradScaler.  No double backward."""
+    who = "fused_mlp_func_amp_grad"
+    half, Cin, hid, Cout = _mlp_amp_check(who, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, True)
+    tensors = [t for t in (x, weight1, weight2, bias1, bias2) if t is not None]
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors):
+        return _mlp_amp_forward(x, weight1, weight2, bias1, bias2, half, False)[0]            # what the inference twin launches: the same bits
+    if Cout % 32:
+        raise SdvarError(f"{who}: out_features {Cout} must be a multiple of 32 under grad (it is K of the dh = dy W2 product)")
+    return _MlpAmpGrad.apply(x, weight1, weight2, bias1, bias2, half)
+
+
 class _XentGrad(torch.autograd.Function):
     """Label-smoothed cross-entropy with a HIP backward: forward = sdvar_xent_train_fwd, backward = one sdvar_xent_train_bwd call (csrc/xent_train.hip).  Saved: the
     logits, the targets and lse (one float per row); reduction 'mean' also keeps the forward's two doubles {sum, counted rows}."""
@@ -898,16 +1107,21 @@ def install_trainer(trainer) -> None:
     trainer.val_loss = CrossEntropyLoss(label_smoothing=0.0, reduction="mean")
 
 
+def _set_ffn_slots(module, model, slot) -> None:
+    """The `fused_mlp_func` global of the module and, with a model, every `ffn.fused_mlp_func` its FFN modules captured at construction (basic_var.py:36)."""
+    module.fused_mlp_func = slot
+    if model is not None:
+        for m in model.modules():
+            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
+                m.fused_mlp_func = slot
+
+
 def install(module, model=None) -> None:
     """Set the `slow_attn` and `fused_mlp_func` globals of a basic_var-like module; with a model, also every `ffn.fused_mlp_func` its FFN modules captured at
     construction (basic_var.py:36).  `memory_efficient_attention` is left alone: setting it would not switch an existing model to it (using_xform is decided at
     construction, basic_var.py:82); assign seam.memory_efficient_attention yourself before building the model if you want the BLHc route."""
     module.slow_attn = slow_attn
-    module.fused_mlp_func = fused_mlp_func
-    if model is not None:
-        for m in model.modules():
-            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
-                m.fused_mlp_func = fused_mlp_func
+    _set_ffn_slots(module, model, fused_mlp_func)
 
 
 def enable_flash(module, model=None) -> None:
@@ -921,13 +1135,17 @@ def enable_flash(module, model=None) -> None:
                 m.using_flash = True
 
 
-def install_amp(module, model=None) -> None:
+def install_amp(module, model=None, ffn_half: bool = False) -> None:
     """For a model run under torch.autocast: install(), then enable_flash(), then `module.slow_attn = slow_attn_amp`, which serves the masked calls (the
-    teacher-forced pass, the verifier's attn_bias, the hand-off prefill) on the half or mixed operands autocast delivers.  `memory_efficient_attention` is left
-    alone for the reason install() documents; assign seam.memory_efficient_attention_amp yourself before building the model if you want the BLHc route."""
+    teacher-forced pass, the verifier's attn_bias, the hand-off prefill) on the half or mixed operands autocast delivers.  ffn_half=False (default): the FFN slots
+    keep install()'s float32 fused_mlp_func.  ffn_half=True: they become fused_mlp_func_amp, the FFN on the half matrix cores in autocast's dtype.
+    `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_amp yourself before building the model if
+    you want the BLHc route."""
     install(module, model)
     enable_flash(module, model)
     module.slow_attn = slow_attn_amp
+    if ffn_half:
+        _set_ffn_slots(module, model, fused_mlp_func_amp)
 
 
 def install_train(module, model=None, ffn: bool = False) -> None:
@@ -937,31 +1155,30 @@ def install_train(module, model=None, ffn: bool = False) -> None:
     == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_grad yourself before building the
     model if you want the BLHc route.  A model trained under torch.autocast needs install_train_amp instead: the slots set here are float32 only, and flash_attn_func
     and the _amp slots still raise on operands that require grad."""
-    slot = fused_mlp_func_grad if ffn else None
     module.slow_attn = slow_attn_grad
-    module.fused_mlp_func = slot
-    if model is not None:
-        for m in model.modules():
-            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
-                m.fused_mlp_func = slot
+    _set_ffn_slots(module, model, fused_mlp_func_grad if ffn else None)
 
 
-def install_train_amp(module, model=None, ffn: bool = False) -> None:
+def install_train_amp(module, model=None, ffn=False) -> None:
     """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
     `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
     the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
     reference runs its own fc2(act(fc1(x))) under autocast; ffn=True sets them to fused_mlp_func_grad.  That function takes float32 operands ONLY and is not
     autocast-aware: it runs its own fp32-operand GEMMs whatever autocast says, and RAISES SdvarError on a half-precision x.  The reference's FFN input is the output
-    of a LayerNorm and the adaLN modulation, which autocast keeps in float32, so ffn=True works there; a model that hands its FFN a half x must use ffn=False.
-    `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_amp_grad yourself before building the model
-    if you want the BLHc route."""
-    slot = fused_mlp_func_grad if ffn else None
+    of a LayerNorm and the adaLN modulation, which autocast keeps in float32, so ffn=True works there; a model that hands its FFN a half x must use ffn=False or
+    ffn="half".  ffn="half" sets them to fused_mlp_func_amp_grad: the FFN's forward and backward on the half matrix cores in autocast's dtype (float32 or half x,
+    float32 master weights; out_features % 32 == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign
+    seam.memory_efficient_attention_amp_grad yourself before building the model if you want the BLHc route."""
+    if isinstance(ffn, str):
+        if ffn != "half":
+            raise SdvarError(f"install_train_amp: ffn={ffn!r}; expected False, True or 'half'")
+        slot = fused_mlp_func_amp_grad
+    else:
+        slot = fused_mlp_func_grad if ffn else None
     module.slow_attn = slow_attn_amp_grad
     module.flash_attn_func = flash_attn_func_grad
-    module.fused_mlp_func = slot
     if model is not None:
         for m in model.modules():
             if hasattr(m, "using_flash"):
                 m.using_flash = True
-            if hasattr(m, "fused_mlp_func") and not callable(getattr(type(m), "fused_mlp_func", None)):
-                m.fused_mlp_func = slot
+    _set_ffn_slots(module, model, slot)
