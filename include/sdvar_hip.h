@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd, and after them sdvar_xent_train_fwd and sdvar_xent_train_bwd; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
+#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd, and after them sdvar_xent_train_fwd and sdvar_xent_train_bwd, and the six sdvar_op_adaln_* / sdvar_op_gate_add_* entry points; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
 #define SDVAR_MAX_STAGES 16
 
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
@@ -537,6 +537,40 @@ int sdvar_op_half_operand(const void* x, int32_t x_dtype, int32_t ldx, int32_t r
  * float[Mp/32][N], the column sums of the ROUNDED dpre over each block of 32 rows, added in row order in fp32 (finish with sdvar_op_colsum).  dh may be NULL when only h_t is
  * asked for. */
 int sdvar_op_gelu_bwd_h(const float* dh, const void* pre, int32_t M, int32_t N, int32_t dtype, void* dpre, void* dpre_t, void* h_t, float* colsum_part, void* stream);
+
+/* ---- the adaLN modulation and the gated residual of a block under autograd (AdaLNSelfAttn.forward, basic_var.py:152-159; AdaLNBeforeHead.forward, :172-174) ----------
+ * csrc/adaln_train.hip.  Added without an ABI bump (purely additive).  Common to the six entry points:
+ *   - x, out, g, dx are (B, L, C) fp32, dense, 16-byte aligned; C % 4 == 0, 4 <= C <= 3072, B, L >= 1, B * L <= 2^29.  One wave64 per row, float4 accesses.
+ *   - a modulation vector (scale, shift, gamma) is one row of C values per image: dtype code 0 fp32, 1 fp16, 2 bf16 (each vector on its own), row b at
+ *     base + b * batch_stride ELEMENTS (0: one row for every image); the base and every row 16-byte aligned.  A half value is widened to fp32 before any arithmetic.
+ *   - argument errors (shape, NULL, dtype code, alignment) are reported before any launch; no allocation, no host synchronisation, no atomics: repeats are
+ *     bit-identical.  Nothing is clamped.
+ * sdvar_op_adaln_fwd: out = ((x - mean) * rstd) * (scale + 1) + shift, mean = the row mean, rstd = 1 / sqrt(biased two-pass variance + eps), every operation in fp32 in the
+ * order of sdvar_op_ln_modulate's row kernel (its lane map for C % 8 != 0). */
+int sdvar_op_adaln_fwd(const float* x, const void* scale, int32_t scale_dtype, int64_t scale_batch_stride, const void* shift, int32_t shift_dtype, int64_t shift_batch_stride,
+                       float* out, int32_t B, int32_t L, int32_t C, double eps, void* stream);
+/* Bytes of the workspace of sdvar_op_adaln_bwd: B * ceil(L / 32) * 2 * C floats (32 = rows of one image per workgroup, a compile-time constant); -1 on a bad shape.  Host only. */
+int64_t sdvar_op_adaln_bwd_ws_bytes(int32_t B, int32_t L, int32_t C);
+/* The backward of sdvar_op_adaln_fwd for the upstream gradient g.  mean and rstd are recomputed from x with the forward's code (the same bits).  With a = g (1 + scale) and
+ * xhat = (x - mean) rstd:
+ *     dx = rstd (a - mean_c(a) - xhat mean_c(a xhat));   dscale[b, c] = sum_l g xhat;   dshift[b, c] = sum_l g
+ * dx (B, L, C) fp32, dscale (dscale_rows, C) dense in scale_dtype, dshift (dshift_rows, C) dense in shift_dtype; *_rows is B, or 1 to sum over the images as well.  Each of the
+ * three may be NULL: it is then not stored (at least one must be given).  The sums are fp32 in a fixed order that depends on (B, L, C) alone - per workgroup of 32 rows of one
+ * image: rows w, w + 4, ... per wave, the waves in order; then the partial rows s, s + 4, ... per slice in index order, the 4 slices in order - and are rounded once to the
+ * operand's dtype (an fp16 overflow is inf).  ws: the workspace above, needed for dscale / dshift. */
+int sdvar_op_adaln_bwd(const float* x, const void* scale, int32_t scale_dtype, int64_t scale_batch_stride, const float* g, float* dx, void* dscale, int32_t dscale_rows,
+                       void* dshift, int32_t shift_dtype, int32_t dshift_rows, float* ws /*workspace*/, int32_t B, int32_t L, int32_t C, double eps, void* stream);
+/* out = x + (y * gamma) * row_scale[b]  (row_scale NULL: x + y * gamma).  y (B, L, C) dense in y_dtype (0 fp32, 1 fp16, 2 bf16), 16-byte aligned, widened to fp32; row_scale
+ * (B) fp32 or NULL: DropPath's per-image factor.  The products and the sum are fp32 operations in this order. */
+int sdvar_op_gate_add_fwd(const float* x, const void* y, int32_t y_dtype, const void* gamma, int32_t gamma_dtype, int64_t gamma_batch_stride, const float* row_scale, float* out,
+                          int32_t B, int32_t L, int32_t C, void* stream);
+/* Bytes of the workspace of sdvar_op_gate_add_bwd: B * ceil(L / 32) * C floats; -1 on a bad shape.  Host only. */
+int64_t sdvar_op_gate_add_bwd_ws_bytes(int32_t B, int32_t L, int32_t C);
+/* The backward of sdvar_op_gate_add_fwd (the gradient of x is g itself): dy = (g * gamma) * row_scale[b], (B, L, C) dense in y_dtype; dgamma[b, c] = sum_l row_scale[b] g y,
+ * (dgamma_rows, C) dense in gamma_dtype, dgamma_rows = B, or 1 to sum over the images as well; row_scale[b] multiplies each 32-row partial sum, the order of the sums is
+ * sdvar_op_adaln_bwd's.  dy or dgamma may be NULL (not stored; y is then not read for a NULL dgamma). */
+int sdvar_op_gate_add_bwd(const float* g, const void* y, int32_t y_dtype, const void* gamma, int32_t gamma_dtype, int64_t gamma_batch_stride, const float* row_scale, void* dy,
+                          void* dgamma, int32_t dgamma_rows, float* ws /*workspace*/, int32_t B, int32_t L, int32_t C, void* stream);
 
 #ifdef __cplusplus
 }

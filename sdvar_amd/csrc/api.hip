@@ -42,6 +42,16 @@ int xent_train_fwd(const float* logits, long long ld, const long long* targets, 
                    double* part, double* sums, float* reduced, int mean, hipStream_t stream);
 int xent_train_bwd(const float* logits, long long ld, const long long* targets, const float* lse, const float* grad, int reduction, const double* sums, long long rows,
                    int V, double eps, long long ignore_index, float* dlogits, int flags, hipStream_t stream);
+int adaln_fwd(const float* x, const void* scale, int sdt, long long sbs, const void* shift, int hdt, long long hbs, float* out, int B, int L, int C, double eps,
+              hipStream_t stream);
+int adaln_bwd(const float* x, const void* scale, int sdt, long long sbs, const float* g, float* dx, void* dscale, int dscale_rows, void* dshift, int hdt, int dshift_rows,
+              float* ws, int B, int L, int C, double eps, hipStream_t stream);
+long long adaln_bwd_ws_bytes(int B, int L, int C);
+int gate_add_fwd(const float* x, const void* y, int ydt, const void* gamma, int gdt, long long gbs, const float* row_scale, float* out, int B, int L, int C,
+                 hipStream_t stream);
+int gate_add_bwd(const float* g, const void* y, int ydt, const void* gamma, int gdt, long long gbs, const float* row_scale, void* dy, void* dgamma, int dgamma_rows,
+                 float* ws, int B, int L, int C, hipStream_t stream);
+long long gate_add_bwd_ws_bytes(int B, int L, int C);
 int attention_f32(const float* q, const void* kc, const void* vc, int kv_f16, float* out, uint16_t* outp, size_t ops, int pfmt, int R, int H, int l, int Lmax, int Ktot, int n_chunk, const int* qbeg, const int* vis, hipStream_t stream);
 int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -538,6 +548,26 @@ int sdvar_xent_train_fwd(const float* logits, int64_t ld, const int64_t* targets
 int sdvar_xent_train_bwd(const float* logits, int64_t ld, const int64_t* targets, const float* lse, const float* grad, int32_t reduction, const double* sums, int64_t rows,
                          int32_t V, double label_smoothing, int64_t ignore_index, float* dlogits, int32_t flags, void* stream) {
     return xent_train_bwd(logits, ld, (const long long*)targets, lse, grad, reduction, sums, rows, V, label_smoothing, ignore_index, dlogits, flags, (hipStream_t)stream);
+}
+
+// the adaLN modulation and the gated residual of a block under autograd (basic_var.py:152-159, 172-174; sdvar_amd/seam.py adaln_modulate / gated_residual): csrc/adaln_train.hip
+int sdvar_op_adaln_fwd(const float* x, const void* scale, int32_t scale_dtype, int64_t scale_batch_stride, const void* shift, int32_t shift_dtype, int64_t shift_batch_stride,
+                       float* out, int32_t B, int32_t L, int32_t C, double eps, void* stream) {
+    return adaln_fwd(x, scale, scale_dtype, scale_batch_stride, shift, shift_dtype, shift_batch_stride, out, B, L, C, eps, (hipStream_t)stream);
+}
+int64_t sdvar_op_adaln_bwd_ws_bytes(int32_t B, int32_t L, int32_t C) { return adaln_bwd_ws_bytes(B, L, C); }
+int sdvar_op_adaln_bwd(const float* x, const void* scale, int32_t scale_dtype, int64_t scale_batch_stride, const float* g, float* dx, void* dscale, int32_t dscale_rows,
+                       void* dshift, int32_t shift_dtype, int32_t dshift_rows, float* ws, int32_t B, int32_t L, int32_t C, double eps, void* stream) {
+    return adaln_bwd(x, scale, scale_dtype, scale_batch_stride, g, dx, dscale, dscale_rows, dshift, shift_dtype, dshift_rows, ws, B, L, C, eps, (hipStream_t)stream);
+}
+int sdvar_op_gate_add_fwd(const float* x, const void* y, int32_t y_dtype, const void* gamma, int32_t gamma_dtype, int64_t gamma_batch_stride, const float* row_scale, float* out,
+                          int32_t B, int32_t L, int32_t C, void* stream) {
+    return gate_add_fwd(x, y, y_dtype, gamma, gamma_dtype, gamma_batch_stride, row_scale, out, B, L, C, (hipStream_t)stream);
+}
+int64_t sdvar_op_gate_add_bwd_ws_bytes(int32_t B, int32_t L, int32_t C) { return gate_add_bwd_ws_bytes(B, L, C); }
+int sdvar_op_gate_add_bwd(const float* g, const void* y, int32_t y_dtype, const void* gamma, int32_t gamma_dtype, int64_t gamma_batch_stride, const float* row_scale, void* dy,
+                          void* dgamma, int32_t dgamma_rows, float* ws, int32_t B, int32_t L, int32_t C, void* stream) {
+    return gate_add_bwd(g, y, y_dtype, gamma, gamma_dtype, gamma_batch_stride, row_scale, dy, dgamma, dgamma_rows, ws, B, L, C, (hipStream_t)stream);
 }
 
 static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream);

@@ -141,6 +141,12 @@ _SIGNATURES = {
     "sdvar_op_gemm_h": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "sdvar_op_half_operand": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sdvar_op_gelu_bwd_h": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "sdvar_op_adaln_fwd": (_I, [_P, _P, _I, C.c_int64, _P, _I, C.c_int64, _P, _I, _I, _I, _D, _P]),
+    "sdvar_op_adaln_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
+    "sdvar_op_adaln_bwd": (_I, [_P, _P, _I, C.c_int64, _P, _P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _D, _P]),
+    "sdvar_op_gate_add_fwd": (_I, [_P, _P, _I, _P, _I, C.c_int64, _P, _P, _I, _I, _I, _P]),
+    "sdvar_op_gate_add_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
+    "sdvar_op_gate_add_bwd": (_I, [_P, _P, _I, _P, _I, C.c_int64, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
     "sdvar_debug_set_gemm_stamps": (_I, [_P]),
     "sdvar_debug_set_qkv_fuse": (_I, [_I]),
@@ -754,6 +760,176 @@ def xent_train_bwd(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Tenso
         _check(lib.sdvar_xent_train_bwd(C.c_void_p(logits.data_ptr()), ld, _ptr(targets), _ptr(lse), _ptr(grad), XENT_REDUCTIONS.index(reduction),
                                         _ptr(sums) if reduction == "mean" else None, rows, V, eps, int(ignore_index), _ptr(dlogits), int(nt), _stream()))
     return dlogits
+
+
+TRAIN_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}          # dtype codes of csrc/adaln_train.hip
+TRAIN_MAX_C = 3072
+TRAIN_CHUNK = 32          # rows of one image per workgroup of the two backward kernels: fixes the workspace size and the order of the column sums
+
+
+def _train_rows(who: str, name: str, t, dtypes, like: Optional[torch.Tensor] = None):
+    """A (B, L, C) operand of the adaln / gate_add calls, read in place: a GPU tensor of one of `dtypes`, dense and 16-byte aligned, C % 4 == 0 in [4, TRAIN_MAX_C];
+    with `like`, of its shape and on its GPU.  Returns (B, L, C)."""
+    if not isinstance(t, torch.Tensor):
+        raise SdvarError(f"{who}: {name} is not a tensor")
+    if not t.is_cuda:
+        raise SdvarError(f"{who}: {name} is a CPU tensor; the kernels run on the GPU and there is no CPU path (move it with .cuda())")
+    if t.dtype not in dtypes:
+        want = " or ".join(str(d) for d in dtypes)
+        hint = f"pass {name}.float()" if torch.float32 in dtypes else f"pass a {want} tensor"
+        raise SdvarError(f"{who}: {name} is {t.dtype}; it must be {want} ({hint})")
+    if t.dim() != 3:
+        raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}; expected (B, L, C)")
+    B, L, Cc = t.shape
+    if Cc < 4 or Cc > TRAIN_MAX_C or Cc % 4:
+        raise SdvarError(f"{who}: C = {Cc} of {name} is outside the supported range: C must be a multiple of 4 in [4, {TRAIN_MAX_C}] (pad the channel dimension)")
+    if B < 1 or L < 1 or B * L > 2 ** 29:
+        raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}; B and L must be at least 1 and B * L at most 2^29 (split the batch)")
+    if like is not None and (tuple(t.shape) != tuple(like.shape) or t.device != like.device):
+        raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)} on {t.device}; expected {tuple(like.shape)} on {like.device}")
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise SdvarError(f"{who}: {name} with strides {tuple(t.stride())} at address % 16 == {t.data_ptr() % 16} is not dense and 16-byte aligned "
+                         f"(pass {name}.clone(memory_format=torch.contiguous_format))")
+    return B, L, Cc
+
+
+def train_vec_in_place(t: torch.Tensor) -> bool:
+    """The 16-byte rule of a modulation vector (B, 1, C) / (1, 1, C) / (B, C): unit last stride, a 16-byte aligned base and, with more than one row, a batch stride
+    that is a non-negative multiple of 16 bytes.  The unbind(2) views of a (B, 1, 6, C) or (B, 1, 2, C) buffer meet it."""
+    per16 = 16 // t.element_size()
+    bs = t.stride(0) if t.shape[0] > 1 else 0
+    return (t.shape[-1] == 1 or t.stride(-1) == 1) and t.data_ptr() % 16 == 0 and bs >= 0 and bs % per16 == 0
+
+
+def _train_vec(who: str, name: str, t, B: int, Cc: int, dev):
+    """A modulation vector of the adaln / gate_add calls -> (dtype code, batch stride in elements, rows = B or 1)."""
+    if not isinstance(t, torch.Tensor):
+        raise SdvarError(f"{who}: {name} is not a tensor")
+    if not t.is_cuda or t.device != dev:
+        raise SdvarError(f"{who}: {name} is on {t.device}; every operand must be on x's GPU ({dev}); there is no CPU path")
+    if t.dtype not in TRAIN_DTYPES:
+        raise SdvarError(f"{who}: {name} is {t.dtype}; it must be float32, float16 or bfloat16 (pass {name}.float())")
+    shp = tuple(t.shape)
+    if not (shp in ((B, 1, Cc), (1, 1, Cc), (B, Cc))):
+        raise SdvarError(f"{who}: {name} of shape {shp} does not broadcast against (B, L, C) = ({B}, L, {Cc}); expected ({B}, 1, {Cc}), (1, 1, {Cc}) or ({B}, {Cc}) "
+                         f"(reshape it to one row of C values per image)")
+    if not train_vec_in_place(t):
+        raise SdvarError(f"{who}: {name} with strides {tuple(t.stride())} at address % 16 == {t.data_ptr() % 16} breaks the 16-byte rule: unit last stride, base and "
+                         f"batch stride multiples of 16 bytes (pass {name}.contiguous())")
+    rows = shp[0]
+    return TRAIN_DTYPES[t.dtype], (t.stride(0) if rows > 1 else 0), rows
+
+
+def _train_one_half(who: str, **named) -> None:
+    halves = {n: t.dtype for n, t in named.items() if isinstance(t, torch.Tensor) and t.dtype in (torch.float16, torch.bfloat16)}
+    if len(set(halves.values())) > 1:
+        raise SdvarError(f"{who}: float16 mixed with bfloat16 ({', '.join(f'{n} is {d}' for n, d in halves.items())}); use one half dtype, or pass .float()")
+
+
+def _train_row_scale(who: str, rs, B: int, dev):
+    if rs is None:
+        return None
+    if not isinstance(rs, torch.Tensor) or not rs.is_cuda or rs.device != dev:
+        raise SdvarError(f"{who}: row_scale must be a tensor on x's GPU ({dev}); there is no CPU path")
+    if rs.dtype != torch.float32 or tuple(rs.shape) != (B,) or not rs.is_contiguous():
+        raise SdvarError(f"{who}: row_scale is {rs.dtype} of shape {tuple(rs.shape)}; expected a dense float32 ({B},) tensor (pass row_scale.float().reshape({B}))")
+    return rs
+
+
+def adaln_bwd_ws_bytes(B: int, L: int, Cc: int) -> int:
+    """Bytes of sdvar_op_adaln_bwd's workspace: B * ceil(L / TRAIN_CHUNK) * 2 * C floats."""
+    n = int(load_library().sdvar_op_adaln_bwd_ws_bytes(B, L, Cc))
+    if n < 0:
+        raise SdvarError(f"adaln_bwd_ws_bytes: {_lib.sdvar_last_error().decode()}")
+    return n
+
+
+def gate_add_bwd_ws_bytes(B: int, L: int, Cc: int) -> int:
+    """Bytes of sdvar_op_gate_add_bwd's workspace: B * ceil(L / TRAIN_CHUNK) * C floats."""
+    n = int(load_library().sdvar_op_gate_add_bwd_ws_bytes(B, L, Cc))
+    if n < 0:
+        raise SdvarError(f"gate_add_bwd_ws_bytes: {_lib.sdvar_last_error().decode()}")
+    return n
+
+
+def adaln_fwd(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """sdvar_op_adaln_fwd: ((x - mean) * rstd) * (scale + 1) + shift for x (B, L, C) fp32 dense; scale / shift (B, 1, C), (1, 1, C) or (B, C), each fp32 / fp16 / bf16,
+    read in place under the 16-byte rule (train_vec_in_place).  Returns (B, L, C) fp32.  No host synchronisation."""
+    who = "adaln_fwd"
+    B, L, Cc = _train_rows(who, "x", x, (torch.float32,))
+    _train_one_half(who, scale=scale, shift=shift)
+    sdt, sbs, _ = _train_vec(who, "scale", scale, B, Cc, x.device)
+    hdt, hbs, _ = _train_vec(who, "shift", shift, B, Cc, x.device)
+    out = torch.empty(B, L, Cc, dtype=torch.float32, device=x.device)
+    lib = load_library()
+    with _on_device(x.device):
+        _check(lib.sdvar_op_adaln_fwd(_ptr(x), C.c_void_p(scale.data_ptr()), sdt, sbs, C.c_void_p(shift.data_ptr()), hdt, hbs, _ptr(out), B, L, Cc, float(eps), _stream()))
+    return out
+
+
+def adaln_bwd(x: torch.Tensor, scale: torch.Tensor, g: torch.Tensor, eps: float, shift_dtype: torch.dtype, scale_rows: int, shift_rows: int,
+              need=(True, True, True)):
+    """sdvar_op_adaln_bwd: (dx (B, L, C) fp32, dscale (scale_rows, C) in scale's dtype, dshift (shift_rows, C) in shift_dtype) for the upstream gradient g (B, L, C) fp32
+    dense; an entry of `need` that is False is not computed (None).  *_rows = B or 1 (1: summed over the images).  No host synchronisation."""
+    who = "adaln_bwd"
+    B, L, Cc = _train_rows(who, "x", x, (torch.float32,))
+    _train_rows(who, "g", g, (torch.float32,), x)
+    sdt, sbs, _ = _train_vec(who, "scale", scale, B, Cc, x.device)
+    if shift_dtype not in TRAIN_DTYPES or scale_rows not in (1, B) or shift_rows not in (1, B):
+        raise SdvarError(f"{who}: shift_dtype {shift_dtype}, scale_rows {scale_rows}, shift_rows {shift_rows}: a float32 / float16 / bfloat16 dtype and 1 or B = {B} rows")
+    nx, ns, nh = (bool(n) for n in need)
+    if not (nx or ns or nh):
+        return None, None, None
+    dev = x.device
+    dx = torch.empty(B, L, Cc, dtype=torch.float32, device=dev) if nx else None
+    dscale = torch.empty(scale_rows, Cc, dtype=scale.dtype, device=dev) if ns else None
+    dshift = torch.empty(shift_rows, Cc, dtype=shift_dtype, device=dev) if nh else None
+    ws = torch.empty(adaln_bwd_ws_bytes(B, L, Cc) // 4, dtype=torch.float32, device=dev) if ns or nh else None
+    lib = load_library()
+    with _on_device(dev):
+        _check(lib.sdvar_op_adaln_bwd(_ptr(x), C.c_void_p(scale.data_ptr()), sdt, sbs, _ptr(g), _ptr(dx), _ptr(dscale), scale_rows, _ptr(dshift), TRAIN_DTYPES[shift_dtype],
+                                      shift_rows, _ptr(ws), B, L, Cc, float(eps), _stream()))
+    return dx, dscale, dshift
+
+
+def gate_add_fwd(x: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sdvar_op_gate_add_fwd: x + (y * gamma) * row_scale[b] for x (B, L, C) fp32 and y (B, L, C) fp32 / fp16 / bf16, both dense; gamma as adaln_fwd's scale; row_scale (B,)
+    fp32 or None.  Returns (B, L, C) fp32; y is not modified.  No host synchronisation."""
+    who = "gate_add_fwd"
+    B, L, Cc = _train_rows(who, "x", x, (torch.float32,))
+    _train_rows(who, "y", y, tuple(TRAIN_DTYPES), x)
+    _train_one_half(who, y=y, gamma=gamma)
+    gdt, gbs, _ = _train_vec(who, "gamma", gamma, B, Cc, x.device)
+    rs = _train_row_scale(who, row_scale, B, x.device)
+    out = torch.empty(B, L, Cc, dtype=torch.float32, device=x.device)
+    lib = load_library()
+    with _on_device(x.device):
+        _check(lib.sdvar_op_gate_add_fwd(_ptr(x), _ptr(y), TRAIN_DTYPES[y.dtype], C.c_void_p(gamma.data_ptr()), gdt, gbs, _ptr(rs), _ptr(out), B, L, Cc, _stream()))
+    return out
+
+
+def gate_add_bwd(g: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, row_scale: Optional[torch.Tensor], gamma_rows: int, need=(True, True)):
+    """sdvar_op_gate_add_bwd: (dy (B, L, C) in y's dtype, dgamma (gamma_rows, C) in gamma's dtype) for the upstream gradient g (B, L, C) fp32 dense - which is also the
+    gradient of x, as it is.  An entry of `need` that is False is not computed (None).  No host synchronisation."""
+    who = "gate_add_bwd"
+    B, L, Cc = _train_rows(who, "g", g, (torch.float32,))
+    _train_rows(who, "y", y, tuple(TRAIN_DTYPES), g)
+    gdt, gbs, _ = _train_vec(who, "gamma", gamma, B, Cc, g.device)
+    rs = _train_row_scale(who, row_scale, B, g.device)
+    if gamma_rows not in (1, B):
+        raise SdvarError(f"{who}: gamma_rows {gamma_rows} must be 1 or B = {B}")
+    ny, ng = (bool(n) for n in need)
+    if not (ny or ng):
+        return None, None
+    dev = g.device
+    dy = torch.empty(B, L, Cc, dtype=y.dtype, device=dev) if ny else None
+    dgamma = torch.empty(gamma_rows, Cc, dtype=gamma.dtype, device=dev) if ng else None
+    ws = torch.empty(gate_add_bwd_ws_bytes(B, L, Cc) // 4, dtype=torch.float32, device=dev) if ng else None
+    lib = load_library()
+    with _on_device(dev):
+        _check(lib.sdvar_op_gate_add_bwd(_ptr(g), _ptr(y), TRAIN_DTYPES[y.dtype], C.c_void_p(gamma.data_ptr()), gdt, gbs, _ptr(rs), _ptr(dy), _ptr(dgamma), gamma_rows,
+                                         _ptr(ws), B, L, Cc, _stream()))
+    return dy, dgamma
 
 
 def img_err_stats(a: torch.Tensor, b: torch.Tensor, sums: torch.Tensor, accumulate: bool = False):

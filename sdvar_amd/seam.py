@@ -21,6 +21,9 @@ maintainer of the reference who wants the kernels without adopting the sampling 
 
     seam.install_trainer(trainer)           # the VARTrainer's train_loss / val_loss (trainer.py:37-38): label-smoothed cross-entropy, HIP forward + backward
 
+    seam.install_train(basic_var, model, ffn=True, adaln=True)        # ... and the blocks' adaLN modulations and gated residual lines (adaln_modulate / gated_residual)
+    seam.install_train_amp(basic_var, model, ffn="half", adaln=True)  # the same under autocast; seam.uninstall_adaln(model) takes the bound forwards off again
+
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
 slow_attn_amp_grad / memory_efficient_attention_amp_grad / flash_attn_func_grad (the half and mixed operands of autocast; backward = sdvar_op_sdpa_h_bwd) and
 fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward) and fused_mlp_func_amp_grad (autocast's half dtype;
@@ -31,6 +34,10 @@ half or fp32, and masks.  Anything else raises SdvarError - there is no fall-bac
 Torch is used for device memory and the current stream only; bool masks go to the kernel as bytes.
 cross_entropy / CrossEntropyLoss / install_trainer are the trainer's loss slots (trainer.py:37-38): label-smoothed cross-entropy on float32 logits, differentiable
 (forward = sdvar_xent_train_fwd, backward = sdvar_xent_train_bwd; one float per row saved, no double backward).
+adaln_modulate / gated_residual are the glue of a block (basic_var.py:152-159, 172-174; the reference's unfilled `fused_add_norm_fn`, :149): the modulated LayerNorm
+and the gated residual line with DropPath's per-image factor, float32 x with float32 or half modulation vectors and branch outputs, differentiable
+(csrc/adaln_train.hip: sdvar_op_adaln_fwd / _bwd, sdvar_op_gate_add_fwd / _bwd; x and scale, resp. y, gamma and row_scale saved; no double backward).  A half
+scale is widened to float32 before the + 1, where torch's scale.add(1) rounds the sum to half.
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
 reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
@@ -43,6 +50,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import types
 from collections import OrderedDict
 from typing import Optional
 
@@ -54,7 +62,8 @@ from .engine import SdvarError
 __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_func", "slow_attn_amp", "memory_efficient_attention_amp", "fused_mlp_func", "install",
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
            "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
-           "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad"]
+           "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad", "adaln_modulate", "gated_residual",
+           "uninstall_adaln"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -1148,18 +1157,24 @@ def install_amp(module, model=None, ffn_half: bool = False) -> None:
         _set_ffn_slots(module, model, fused_mlp_func_amp)
 
 
-def install_train(module, model=None, ffn: bool = False) -> None:
+def install_train(module, model=None, ffn: bool = False, adaln: bool = False) -> None:
     """For TRAINING the reference in fp32 with the seam's operators: `module.slow_attn = slow_attn_grad`.  ffn=False (default): `module.fused_mlp_func = None` plus
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
     state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
     == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign seam.memory_efficient_attention_grad yourself before building the
     model if you want the BLHc route.  A model trained under torch.autocast needs install_train_amp instead: the slots set here are float32 only, and flash_attn_func
-    and the _amp slots still raise on operands that require grad."""
+    and the _amp slots still raise on operands that require grad.  adaln=True (needs the model) also binds an instance-level `forward` on every submodule that has
+    `ln_wo_grad`: blocks (those with attn, ffn and ada_lin or ada_gss) run basic_var.py:152-159 with adaln_modulate for the two modulations and gated_residual for the
+    two residual lines - DropPath's per-image factor, drawn as helpers.py:43-45 draws it, goes in as row_scale - and head norms run :172-174 on adaln_modulate;
+    attn and ffn are still called as modules, so the slots above keep working.  uninstall_adaln(model) removes the bound forwards.  adaln=False (default) binds
+    nothing."""
+    if adaln:
+        _install_adaln("install_train", model)
     module.slow_attn = slow_attn_grad
     _set_ffn_slots(module, model, fused_mlp_func_grad if ffn else None)
 
 
-def install_train_amp(module, model=None, ffn=False) -> None:
+def install_train_amp(module, model=None, ffn=False, adaln: bool = False) -> None:
     """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
     `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
     the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
@@ -1168,7 +1183,10 @@ def install_train_amp(module, model=None, ffn=False) -> None:
     of a LayerNorm and the adaLN modulation, which autocast keeps in float32, so ffn=True works there; a model that hands its FFN a half x must use ffn=False or
     ffn="half".  ffn="half" sets them to fused_mlp_func_amp_grad: the FFN's forward and backward on the half matrix cores in autocast's dtype (float32 or half x,
     float32 master weights; out_features % 32 == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign
-    seam.memory_efficient_attention_amp_grad yourself before building the model if you want the BLHc route."""
+    seam.memory_efficient_attention_amp_grad yourself before building the model if you want the BLHc route.  adaln=True: as install_train's; under autocast the
+    modulation vectors and the branch outputs arrive in half and are read as they are."""
+    if adaln:
+        _install_adaln("install_train_amp", model)
     if isinstance(ffn, str):
         if ffn != "half":
             raise SdvarError(f"install_train_amp: ffn={ffn!r}; expected False, True or 'half'")
@@ -1182,3 +1200,174 @@ def install_train_amp(module, model=None, ffn=False) -> None:
             if hasattr(m, "using_flash"):
                 m.using_flash = True
     _set_ffn_slots(module, model, slot)
+
+
+# ------------------------------------------------------------------------------------------------------- adaLN modulation and gated residual (csrc/adaln_train.hip)
+def _train_x(x):
+    """x as the kernels read it: itself when dense and 16-byte aligned, else one dense copy (differentiable).  Anything else is left for the engine's checks to name."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 3 and x.dtype in E.TRAIN_DTYPES and (not x.is_contiguous() or x.data_ptr() % 16):
+        return x.clone(memory_format=torch.contiguous_format)
+    return x
+
+
+def _train_vec(t):
+    """A modulation vector as the kernels read it: itself under the 16-byte rule, else one dense copy (differentiable)."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dim() in (2, 3) and t.dtype in E.TRAIN_DTYPES and not E.train_vec_in_place(t):
+        return t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def _train_grad(who: str, g: torch.Tensor) -> torch.Tensor:
+    if g.dtype != torch.float32:
+        raise SdvarError(f"{who}: the gradient of the output is {g.dtype} but the output is float32")
+    return _dense16(g)          # a stride-0 expansion (out.sum().backward()) becomes one dense tensor; a dense gradient is read in place
+
+
+def _no_double_backward(who: str) -> None:
+    if torch.is_grad_enabled():
+        raise SdvarError(f"{who}: double backward (backward(create_graph=True), or torch.autograd.grad of a gradient) is not supported; "
+                         "call backward() without create_graph")
+
+
+class _AdalnGrad(torch.autograd.Function):
+    """adaln_modulate with a HIP backward (sdvar_op_adaln_fwd / sdvar_op_adaln_bwd).  Saved: x and scale; mean and rstd are recomputed in the backward with the
+    forward's code."""
+
+    @staticmethod
+    def forward(ctx, x, scale, shift, eps):
+        h = E.adaln_fwd(x, scale, shift, eps)
+        ctx.save_for_backward(x, scale)
+        ctx.ada = (eps, shift.dtype, tuple(shift.shape))
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        _no_double_backward("adaln_modulate")
+        nx, ns, nh = ctx.needs_input_grad[:3]
+        if not (nx or ns or nh):
+            return None, None, None, None
+        x, scale = ctx.saved_tensors
+        eps, hdtype, hshape = ctx.ada
+        dx, ds, dh = E.adaln_bwd(x, scale, _train_grad("adaln_modulate", g), eps, hdtype, scale.shape[0], hshape[0], (nx, ns, nh))
+        return dx, None if ds is None else ds.view(scale.shape), None if dh is None else dh.view(hshape), None
+
+
+def adaln_modulate(x, scale, shift, eps: float = 1e-6):
+    """The modulated LayerNorm of a block and of the head norm (basic_var.py:157-158, :174: `ln_wo_grad(x).mul(scale.add(1)).add_(shift)`) as one kernel per direction:
+    h = ((x - mean) * rstd) * (scale + 1) + shift, mean = the row mean, rstd = 1 / sqrt(var + eps) with the biased two-pass variance, every operation in float32.
+    x (B, L, C) float32 on the GPU, C a multiple of 4 in [4, 3072]; a dense, 16-byte aligned x is read in place, anything else is copied once.  scale and shift are
+    (B, 1, C), (1, 1, C) or (B, C), each float32, float16 or bfloat16 on its own (one half dtype per call): rows with unit last stride and 16-byte alignment - the
+    unbind(2) views of the reference's (B, 1, 6, C) / (B, 1, 2, C) buffers - are read in place, anything else is copied once.  A half scale is widened to float32
+    BEFORE the + 1, where torch's `scale.add(1)` rounds 1 + scale to half: this side is the more accurate one and differs from autocast's eager result by up to half
+    a half ulp of 1 + scale.  Returns (B, L, C) float32.  Differentiable: dx, and dscale / dshift summed over L (and over B for a (1, 1, C) operand) in float32 in a
+    fixed order and rounded once to the operand's own dtype; nothing is clamped (an fp16 overflow is inf and reaches the GradScaler); no atomics, repeats are
+    bit-identical; only the gradients autograd asks for are computed.  Saved for the backward: x and scale.  Under torch.no_grad(), or when nothing requires grad,
+    the same forward kernel runs: the same bits.  Neither direction synchronises with the host.  No double backward."""
+    who = "adaln_modulate"
+    x, scale, shift = _train_x(x), _train_vec(scale), _train_vec(shift)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, scale, shift)):
+        E._train_rows(who, "x", x, (torch.float32,))          # argument errors before autograd wraps them
+        return _AdalnGrad.apply(x, scale, shift, float(eps))
+    d = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    return E.adaln_fwd(d(x), d(scale), d(shift), float(eps))
+
+
+class _GateAddGrad(torch.autograd.Function):
+    """gated_residual with a HIP backward (sdvar_op_gate_add_fwd / sdvar_op_gate_add_bwd).  Saved: y, gamma and row_scale - nothing when only x needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, gamma, row_scale):
+        out = E.gate_add_fwd(x, y, gamma, row_scale)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            ctx.save_for_backward(y, gamma, *(() if row_scale is None else (row_scale,)))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _no_double_backward("gated_residual")
+        nx, ny, ng = ctx.needs_input_grad[:3]
+        dy = dgamma = None
+        if ny or ng:
+            y, gamma, *rest = ctx.saved_tensors
+            dy, dgamma = E.gate_add_bwd(_train_grad("gated_residual", g), y, gamma, rest[0] if rest else None, gamma.shape[0], (ny, ng))
+            if dgamma is not None:
+                dgamma = dgamma.view(gamma.shape)
+        elif g.dtype != torch.float32:
+            raise SdvarError(f"gated_residual: the gradient of the output is {g.dtype} but the output is float32")
+        return (g if nx else None), dy, dgamma, None
+
+
+def gated_residual(x, y, gamma, row_scale=None):
+    """The residual line of a block (basic_var.py:157-158: `x + drop_path(branch.mul_(gamma))`) as one kernel: out = x + (y * gamma) * row_scale[b], without row_scale
+    x + y * gamma.  x (B, L, C) float32; y (B, L, C) float32, float16 or bfloat16 (under autocast: the output of proj / fc2), not modified; gamma under
+    adaln_modulate's rules for scale; row_scale (B,) float32 without gradient: DropPath's per-image factor, 0 or 1 / keep.  Half operands are widened and the products
+    formed in float32, where the reference multiplies in half.  Returns (B, L, C) float32.  Differentiable: the gradient of x is the upstream gradient itself (no
+    kernel, no copy), dy = g * gamma * row_scale[b] in y's dtype (exactly 0 on a dropped image), dgamma[b, c] = row_scale[b] * sum_l g y in gamma's dtype, summed in
+    float32 in a fixed order and rounded once.  Saved for the backward: y, gamma, row_scale.  The other rules are adaln_modulate's."""
+    who = "gated_residual"
+    x, y, gamma = _train_x(x), _train_x(y), _train_vec(gamma)
+    if isinstance(row_scale, torch.Tensor):
+        if row_scale.requires_grad and torch.is_grad_enabled():
+            raise SdvarError(f"{who}: row_scale requires grad; it carries no gradient (pass row_scale.detach())")
+        row_scale = row_scale.detach()
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, y, gamma)):
+        E._train_rows(who, "x", x, (torch.float32,))
+        return _GateAddGrad.apply(x, y, gamma, row_scale)
+    d = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    return E.gate_add_fwd(d(x), d(y), d(gamma), row_scale)
+
+
+def _drop_path_scale(dp, y):
+    """DropPath's per-image factor for the branch output y, drawn as the reference draws it (helpers.py:43-45) so that the generator moves as it does there; None when
+    the module drops nothing (nn.Identity, drop_prob == 0, or eval mode)."""
+    p = getattr(dp, "drop_prob", 0.0)
+    if not p or not dp.training:
+        return None
+    keep = 1 - p
+    r = y.new_empty((y.shape[0],) + (1,) * (y.dim() - 1)).bernoulli_(keep)
+    if keep > 0.0 and getattr(dp, "scale_by_keep", True):
+        r.div_(keep)
+    return r.view(y.shape[0]).float()
+
+
+def _adaln_block_forward(self, x, cond_BD, attn_bias):
+    """AdaLNSelfAttn.forward (basic_var.py:152-159) on adaln_modulate / gated_residual; attn and ffn are called as modules."""
+    if hasattr(self, "ada_gss"):
+        gamma1, gamma2, scale1, scale2, shift1, shift2 = (self.ada_gss + cond_BD).unbind(2)
+    else:
+        gamma1, gamma2, scale1, scale2, shift1, shift2 = self.ada_lin(cond_BD).view(-1, 1, 6, x.shape[-1]).unbind(2)
+    eps = getattr(self.ln_wo_grad, "eps", 1e-6)
+    y = self.attn(adaln_modulate(x, scale1, shift1, eps), attn_bias=attn_bias)
+    x = gated_residual(x, y, gamma1, _drop_path_scale(self.drop_path, y))
+    y = self.ffn(adaln_modulate(x, scale2, shift2, eps))
+    return gated_residual(x, y, gamma2, _drop_path_scale(self.drop_path, y))
+
+
+def _adaln_head_forward(self, x_BLC, cond_BD):
+    """AdaLNBeforeHead.forward (basic_var.py:172-174) on adaln_modulate."""
+    scale, shift = self.ada_lin(cond_BD).view(-1, 1, 2, x_BLC.shape[-1]).unbind(2)
+    return adaln_modulate(x_BLC, scale, shift, getattr(self.ln_wo_grad, "eps", 1e-6))
+
+
+def _install_adaln(who: str, model) -> None:
+    if model is None:
+        raise SdvarError(f"{who}: adaln=True binds a forward on the model's own blocks and head norm; pass the model (model=None has nothing to bind)")
+    for m in model.modules():
+        if not hasattr(m, "ln_wo_grad"):
+            continue
+        if hasattr(m, "attn"):
+            if not (hasattr(m, "ffn") and (hasattr(m, "ada_lin") or hasattr(m, "ada_gss"))):
+                raise SdvarError(f"{who}: {type(m).__name__} has ln_wo_grad and attn but no ffn / ada_lin / ada_gss; adaln=True knows AdaLNSelfAttn-like blocks only")
+            m.forward = types.MethodType(_adaln_block_forward, m)
+        else:
+            if not hasattr(m, "ada_lin"):
+                raise SdvarError(f"{who}: {type(m).__name__} has ln_wo_grad but neither attn nor ada_lin; adaln=True knows AdaLNBeforeHead-like head norms only")
+            m.forward = types.MethodType(_adaln_head_forward, m)
+
+
+def uninstall_adaln(model) -> None:
+    """Delete the instance-level `forward` that install_train(..., adaln=True) / install_train_amp(..., adaln=True) bound: the class's own forward is back."""
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if getattr(f, "__func__", None) in (_adaln_block_forward, _adaln_head_forward):
+            del m.forward
