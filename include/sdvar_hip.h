@@ -572,6 +572,37 @@ int64_t sdvar_op_gate_add_bwd_ws_bytes(int32_t B, int32_t L, int32_t C);
 int sdvar_op_gate_add_bwd(const float* g, const void* y, int32_t y_dtype, const void* gamma, int32_t gamma_dtype, int64_t gamma_batch_stride, const float* row_scale, void* dy,
                           void* dgamma, int32_t dgamma_rows, float* ws /*workspace*/, int32_t B, int32_t L, int32_t C, void* stream);
 
+/* ---- attn_l2_norm's QK normalisation between the QKV GEMM and the attention call under autograd (SelfAttention.forward, basic_var.py:93-105) ---------------------------
+ * csrc/qknorm_train.hip.  Added without an ABI bump (purely additive).  Common to the three entry points:
+ *   - qkv and dqkv are (B, L, 3, H, 64), dense, 16-byte aligned, dtype code 0 fp32, 1 fp16, 2 bf16 (widened to fp32 before any arithmetic); the head dimension is 64,
+ *     1 <= H <= 48, B, L >= 1, B * L <= 2^29.  One wave64 per row (b, l); a lane holds 4 consecutive channels, a head is 16 consecutive lanes, a step covers 4 heads
+ *     (H need not be a multiple of 4).
+ *   - q_bias, v_bias (C = 64 H, fp32, 16-byte aligned, each may be NULL) are added in fp32; scale_log (H) fp32 is the raw per-head parameter:
+ *     s_h = expf(min(scale_log[h], max_log)).
+ *   - the sum of squares of a head: the lane's four products added left to right, then four cross-lane levels (xor 8, 4, 2, 1) inside the 16 lanes.  The backward
+ *     recomputes the forward's norms bit for bit.
+ *   - argument errors (shape, NULL, dtype code, alignment, strides) are reported before any launch; no allocation, no host synchronisation, no atomics: repeats are
+ *     bit-identical.  Nothing is clamped.
+ * sdvar_op_qknorm_fwd: q = (xq / max(|xq|, 1e-12)) * s_h with xq = qkv[.., 0, ..] + q_bias, k = xk / max(|xk|, 1e-12); q and k are dense (B, L, H, 64) fp32.  With a v_bias
+ * (and only then; v is NULL exactly when v_bias is) v = qkv[.., 2, ..] + v_bias, dense (B, L, H, 64) in dtype, rounded once.  A head with a norm below 1e-12 gives
+ * x / 1e-12: a zero head gives exact zeros. */
+int sdvar_op_qknorm_fwd(const void* qkv, int32_t dtype, const float* q_bias, const float* v_bias, const float* scale_log, double max_log, float* q, float* k, void* v,
+                        int32_t B, int32_t L, int32_t H, void* stream);
+/* Bytes of the workspace of sdvar_op_qknorm_bwd: B * ceil(L / 32) * 3 * 64 H floats (32 = rows of one image per workgroup, a compile-time constant); -1 on a bad shape.
+ * Host only. */
+int64_t sdvar_op_qknorm_bwd_ws_bytes(int32_t B, int32_t L, int32_t H);
+/* The backward of sdvar_op_qknorm_fwd for the upstream gradients dq, dk (fp32) and dv (in dtype), each read through grad_strides = {dq: b, h, l; dk: b, h, l; dv: b, h, l}
+ * in ELEMENTS (non-negative multiples of 4; unit channel stride; base aligned to 4 elements); each of the three may be NULL: zero, not read.  v_bias does not enter.
+ * With n = max(|x|, eps), xh = x / n:   |x| >= eps: dx = (s / n) (g - xh (xh . g)),  else dx = (s g) / eps   (k: s = 1).
+ *   dqkv = [dx_q, dx_k, dv] in dtype, all three slots written by the one kernel (an fp16 overflow is +-inf);
+ *   dscale_log[h] = [scale_log[h] <= max_log] sum_{b, l, c in h} dq q;   dq_bias[c] = sum_{b, l} dx_q;   dv_bias[c] = sum_{b, l} dv     - fp32, (H), (C), (C).
+ * Each of the four outputs may be NULL: it is then not computed and the inputs only it needs are not read (at least one must be given).  The sums are fp32 in a fixed order
+ * that depends on (B, L, H) alone - sdvar_op_adaln_bwd's: per workgroup of 32 rows of one image rows w, w + 4, ... per wave, the waves in order; then the partial rows
+ * s, s + 4, ... of all images per slice in index order, the 4 slices in order; a head's 64 column sums by six wave levels.  ws: the workspace above, needed for the sums. */
+int sdvar_op_qknorm_bwd(const void* qkv, int32_t dtype, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
+                        const int64_t* grad_strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws /*workspace*/, int32_t B, int32_t L, int32_t H,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

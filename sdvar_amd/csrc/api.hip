@@ -52,6 +52,11 @@ int gate_add_fwd(const float* x, const void* y, int ydt, const void* gamma, int 
 int gate_add_bwd(const float* g, const void* y, int ydt, const void* gamma, int gdt, long long gbs, const float* row_scale, void* dy, void* dgamma, int dgamma_rows,
                  float* ws, int B, int L, int C, hipStream_t stream);
 long long gate_add_bwd_ws_bytes(int B, int L, int C);
+int qknorm_fwd(const void* qkv, int dt, const float* q_bias, const float* v_bias, const float* scale_log, double max_log, float* q, float* k, void* v, int B, int L, int H,
+               hipStream_t stream);
+int qknorm_bwd(const void* qkv, int dt, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
+               const long long* strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws, int B, int L, int H, hipStream_t stream);
+long long qknorm_bwd_ws_bytes(int B, int L, int H);
 int attention_f32(const float* q, const void* kc, const void* vc, int kv_f16, float* out, uint16_t* outp, size_t ops, int pfmt, int R, int H, int l, int Lmax, int Ktot, int n_chunk, const int* qbeg, const int* vis, hipStream_t stream);
 int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -568,6 +573,17 @@ int64_t sdvar_op_gate_add_bwd_ws_bytes(int32_t B, int32_t L, int32_t C) { return
 int sdvar_op_gate_add_bwd(const float* g, const void* y, int32_t y_dtype, const void* gamma, int32_t gamma_dtype, int64_t gamma_batch_stride, const float* row_scale, void* dy,
                           void* dgamma, int32_t dgamma_rows, float* ws, int32_t B, int32_t L, int32_t C, void* stream) {
     return gate_add_bwd(g, y, y_dtype, gamma, gamma_dtype, gamma_batch_stride, row_scale, dy, dgamma, dgamma_rows, ws, B, L, C, (hipStream_t)stream);
+}
+
+// attn_l2_norm's QK normalisation between the QKV GEMM and the attention call under autograd (basic_var.py:93-105; sdvar_amd/seam.py qk_l2norm): csrc/qknorm_train.hip
+int sdvar_op_qknorm_fwd(const void* qkv, int32_t dtype, const float* q_bias, const float* v_bias, const float* scale_log, double max_log, float* q, float* k, void* v,
+                        int32_t B, int32_t L, int32_t H, void* stream) {
+    return qknorm_fwd(qkv, dtype, q_bias, v_bias, scale_log, max_log, q, k, v, B, L, H, (hipStream_t)stream);
+}
+int64_t sdvar_op_qknorm_bwd_ws_bytes(int32_t B, int32_t L, int32_t H) { return qknorm_bwd_ws_bytes(B, L, H); }
+int sdvar_op_qknorm_bwd(const void* qkv, int32_t dtype, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
+                        const int64_t* grad_strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws, int32_t B, int32_t L, int32_t H, void* stream) {
+    return qknorm_bwd(qkv, dtype, q_bias, scale_log, max_log, dq, dk, dv, (const long long*)grad_strides, dqkv, dscale_log, dq_bias, dv_bias, ws, B, L, H, (hipStream_t)stream);
 }
 
 static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream);

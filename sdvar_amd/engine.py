@@ -147,6 +147,9 @@ _SIGNATURES = {
     "sdvar_op_gate_add_fwd": (_I, [_P, _P, _I, _P, _I, C.c_int64, _P, _P, _I, _I, _I, _P]),
     "sdvar_op_gate_add_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
     "sdvar_op_gate_add_bwd": (_I, [_P, _P, _I, _P, _I, C.c_int64, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "sdvar_op_qknorm_fwd": (_I, [_P, _I, _P, _P, _P, _D, _P, _P, _P, _I, _I, _I, _P]),
+    "sdvar_op_qknorm_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
+    "sdvar_op_qknorm_bwd": (_I, [_P, _I, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
     "sdvar_debug_set_gemm_stamps": (_I, [_P]),
     "sdvar_debug_set_qkv_fuse": (_I, [_I]),
@@ -930,6 +933,123 @@ def gate_add_bwd(g: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, row_scal
         _check(lib.sdvar_op_gate_add_bwd(_ptr(g), _ptr(y), TRAIN_DTYPES[y.dtype], C.c_void_p(gamma.data_ptr()), gdt, gbs, _ptr(rs), _ptr(dy), _ptr(dgamma), gamma_rows,
                                          _ptr(ws), B, L, Cc, _stream()))
     return dy, dgamma
+
+
+QKNORM_MAX_H = 48
+
+
+def _qknorm_qkv(who: str, qkv):
+    """The (B, L, 3, H, 64) operand of the qknorm calls, read in place: a GPU tensor, float32 / float16 / bfloat16, dense and 16-byte aligned.  Returns (B, L, H)."""
+    if not isinstance(qkv, torch.Tensor):
+        raise SdvarError(f"{who}: qkv is not a tensor")
+    if qkv.dtype not in TRAIN_DTYPES:
+        raise SdvarError(f"{who}: qkv is {qkv.dtype}; it must be float32, float16 or bfloat16 (pass qkv.float())")
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise SdvarError(f"{who}: qkv has shape {tuple(qkv.shape)}; expected (B, L, 3, H, 64)")
+    B, L, _, H, hd = qkv.shape
+    if hd != 64:
+        raise SdvarError(f"{who}: head dim {hd} of qkv; only 64 is supported")
+    if H < 1 or H > QKNORM_MAX_H:
+        raise SdvarError(f"{who}: H = {H} heads of qkv is outside the supported range [1, {QKNORM_MAX_H}]")
+    if B < 1 or L < 1 or B * L > 2 ** 29:
+        raise SdvarError(f"{who}: qkv has shape {tuple(qkv.shape)}; B and L must be at least 1 and B * L at most 2^29 (split the batch)")
+    if not qkv.is_cuda:
+        raise SdvarError(f"{who}: qkv is a CPU tensor; the kernels run on the GPU and there is no CPU path (move it with .cuda())")
+    if not qkv.is_contiguous() or qkv.data_ptr() % 16:
+        raise SdvarError(f"{who}: qkv with strides {tuple(qkv.stride())} at address % 16 == {qkv.data_ptr() % 16} is not dense and 16-byte aligned "
+                         f"(pass qkv.clone(memory_format=torch.contiguous_format))")
+    return B, L, H
+
+
+def _qknorm_vec(who: str, name: str, t, n: int, dev, optional: bool = True):
+    """scale_log (H) / q_bias / v_bias (C): a dense float32 vector on qkv's GPU, 16-byte aligned; None passes when optional."""
+    if t is None and optional:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise SdvarError(f"{who}: {name} is not a tensor")
+    if not t.is_cuda or t.device != dev:
+        raise SdvarError(f"{who}: {name} is on {t.device}; every operand must be on qkv's GPU ({dev}); there is no CPU path")
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.data_ptr() % 16:
+        raise SdvarError(f"{who}: {name} is {t.dtype} of shape {tuple(t.shape)} at address % 16 == {t.data_ptr() % 16}; expected a dense, 16-byte aligned float32 ({n},) "
+                         f"tensor (pass {name}.float().reshape({n}).clone())")
+    return t
+
+
+def qknorm_grad_in_place(t: torch.Tensor) -> bool:
+    """The stride rule of an upstream gradient of the qknorm backward, (B, L, H, 64) in any dim order: unit last stride, every other stride a non-negative multiple of 4
+    elements, the base aligned to 4 elements.  The permute(0, 2, 1, 3) views the seam's attention backward returns meet it."""
+    return t.stride(-1) == 1 and t.data_ptr() % (4 * t.element_size()) == 0 and all(s >= 0 and s % 4 == 0 for s in t.stride()[:-1])
+
+
+def _qknorm_grad(who: str, name: str, g, dtype, B: int, L: int, H: int, dev):
+    """An upstream gradient given as a (B, L, H, 64) tensor (any strides under the rule above) or None -> its (b, h, l) strides."""
+    if g is None:
+        return (0, 0, 0)
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.device != dev:
+        raise SdvarError(f"{who}: {name} must be a tensor on qkv's GPU ({dev}); there is no CPU path")
+    if g.dtype != dtype:
+        raise SdvarError(f"{who}: {name} is {g.dtype}; expected {dtype}")
+    if tuple(g.shape) != (B, L, H, 64):
+        raise SdvarError(f"{who}: {name} has shape {tuple(g.shape)}; expected ({B}, {L}, {H}, 64)")
+    if not qknorm_grad_in_place(g):
+        raise SdvarError(f"{who}: {name} with strides {tuple(g.stride())} at address % 16 == {g.data_ptr() % 16} breaks the stride rule: unit last stride, the others "
+                         f"non-negative multiples of 4 elements, base aligned to 4 elements (pass {name}.clone(memory_format=torch.contiguous_format))")
+    return (g.stride(0), g.stride(2), g.stride(1))
+
+
+def qknorm_bwd_ws_bytes(B: int, L: int, H: int) -> int:
+    """Bytes of sdvar_op_qknorm_bwd's workspace: B * ceil(L / TRAIN_CHUNK) * 3 * 64 H floats."""
+    n = int(load_library().sdvar_op_qknorm_bwd_ws_bytes(B, L, H))
+    if n < 0:
+        raise SdvarError(f"qknorm_bwd_ws_bytes: {_lib.sdvar_last_error().decode()}")
+    return n
+
+
+def qknorm_fwd(qkv: torch.Tensor, scale_log: torch.Tensor, max_log: float, q_bias: Optional[torch.Tensor] = None, v_bias: Optional[torch.Tensor] = None):
+    """sdvar_op_qknorm_fwd: qkv (B, L, 3, H, 64) fp32 / fp16 / bf16 dense -> (q, k, v): q = normalize(qkv[:, :, 0] + q_bias) * exp(min(scale_log, max_log)) and
+    k = normalize(qkv[:, :, 1]), both (B, L, H, 64) fp32; v = qkv[:, :, 2] + v_bias, (B, L, H, 64) in qkv's dtype - None without a v_bias (nothing is written then).
+    scale_log (H), q_bias / v_bias (64 H) fp32.  No host synchronisation."""
+    who = "qknorm_fwd"
+    B, L, H = _qknorm_qkv(who, qkv)
+    dev = qkv.device
+    _qknorm_vec(who, "scale_log", scale_log, H, dev, optional=False)
+    _qknorm_vec(who, "q_bias", q_bias, 64 * H, dev)
+    _qknorm_vec(who, "v_bias", v_bias, 64 * H, dev)
+    q = torch.empty(B, L, H, 64, dtype=torch.float32, device=dev)
+    k = torch.empty(B, L, H, 64, dtype=torch.float32, device=dev)
+    v = torch.empty(B, L, H, 64, dtype=qkv.dtype, device=dev) if v_bias is not None else None
+    lib = load_library()
+    with _on_device(dev):
+        _check(lib.sdvar_op_qknorm_fwd(_ptr(qkv), TRAIN_DTYPES[qkv.dtype], _ptr(q_bias), _ptr(v_bias), _ptr(scale_log), float(max_log), _ptr(q), _ptr(k), _ptr(v), B, L, H,
+                                       _stream()))
+    return q, k, v
+
+
+def qknorm_bwd(qkv: torch.Tensor, scale_log: torch.Tensor, max_log: float, q_bias: Optional[torch.Tensor], dq, dk, dv, need=(True, True, True, True)):
+    """sdvar_op_qknorm_bwd: (dqkv (B, L, 3, H, 64) in qkv's dtype, dscale_log (H), dq_bias (64 H), dv_bias (64 H), the three sums fp32) for the upstream gradients dq, dk
+    (fp32) and dv (qkv's dtype), each a (B, L, H, 64) tensor read through its strides (qknorm_grad_in_place) or None (zero, not read).  An entry of `need` that is False is
+    not computed (None).  No host synchronisation."""
+    who = "qknorm_bwd"
+    B, L, H = _qknorm_qkv(who, qkv)
+    dev = qkv.device
+    _qknorm_vec(who, "scale_log", scale_log, H, dev, optional=False)
+    _qknorm_vec(who, "q_bias", q_bias, 64 * H, dev)
+    strides = (C.c_int64 * 9)(*_qknorm_grad(who, "dq", dq, torch.float32, B, L, H, dev), *_qknorm_grad(who, "dk", dk, torch.float32, B, L, H, dev),
+                              *_qknorm_grad(who, "dv", dv, qkv.dtype, B, L, H, dev))
+    nx, ns, nq, nv = (bool(n) for n in need)
+    if not (nx or ns or nq or nv):
+        return None, None, None, None
+    dqkv = torch.empty(B, L, 3, H, 64, dtype=qkv.dtype, device=dev) if nx else None
+    dscale = torch.empty(H, dtype=torch.float32, device=dev) if ns else None
+    dqb = torch.empty(64 * H, dtype=torch.float32, device=dev) if nq else None
+    dvb = torch.empty(64 * H, dtype=torch.float32, device=dev) if nv else None
+    ws = torch.empty(qknorm_bwd_ws_bytes(B, L, H) // 4, dtype=torch.float32, device=dev) if ns or nq or nv else None
+    raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())          # strided: read through grad_strides
+    lib = load_library()
+    with _on_device(dev):
+        _check(lib.sdvar_op_qknorm_bwd(_ptr(qkv), TRAIN_DTYPES[qkv.dtype], _ptr(q_bias), _ptr(scale_log), float(max_log), raw(dq), raw(dk), raw(dv), strides, _ptr(dqkv),
+                                       _ptr(dscale), _ptr(dqb), _ptr(dvb), _ptr(ws), B, L, H, _stream()))
+    return dqkv, dscale, dqb, dvb
 
 
 def img_err_stats(a: torch.Tensor, b: torch.Tensor, sums: torch.Tensor, accumulate: bool = False):

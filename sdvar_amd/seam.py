@@ -24,6 +24,10 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install_train(basic_var, model, ffn=True, adaln=True)        # ... and the blocks' adaLN modulations and gated residual lines (adaln_modulate / gated_residual)
     seam.install_train_amp(basic_var, model, ffn="half", adaln=True)  # the same under autocast; seam.uninstall_adaln(model) takes the bound forwards off again
 
+    seam.install_train(basic_var, model, ffn=True, adaln=True, qknorm=True)   # ... and attn_l2_norm's QK normalisation between the QKV GEMM and the attention (qk_l2norm)
+    seam.install_train_amp(basic_var, model, ffn="half", adaln=True, qknorm=True)    # the same under autocast; seam.install_qknorm(model) alone for inference,
+                                                                                     # seam.uninstall_qknorm(model) takes the bound forwards off again
+
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
 slow_attn_amp_grad / memory_efficient_attention_amp_grad / flash_attn_func_grad (the half and mixed operands of autocast; backward = sdvar_op_sdpa_h_bwd) and
 fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward) and fused_mlp_func_amp_grad (autocast's half dtype;
@@ -38,6 +42,9 @@ adaln_modulate / gated_residual are the glue of a block (basic_var.py:152-159, 1
 and the gated residual line with DropPath's per-image factor, float32 x with float32 or half modulation vectors and branch outputs, differentiable
 (csrc/adaln_train.hip: sdvar_op_adaln_fwd / _bwd, sdvar_op_gate_add_fwd / _bwd; x and scale, resp. y, gamma and row_scale saved; no double backward).  A half
 scale is widened to float32 before the + 1, where torch's scale.add(1) rounds the sum to half.
+qk_l2norm is what SelfAttention.forward does between the QKV GEMM and the attention call when attn_l2_norm is on (basic_var.py:93-105): bias add, per-head L2
+normalisation of q and k and the learnt per-head scale of q, one kernel per direction (csrc/qknorm_train.hip: sdvar_op_qknorm_fwd / _bwd; qkv, the biases and the scale
+parameter saved; no double backward).  The float32 master bias is added in float32 to the GEMM's output, where autocast rounds acc + half(bias) to half inside the GEMM.
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
 reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
@@ -63,7 +70,7 @@ __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_f
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
            "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
            "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad", "adaln_modulate", "gated_residual",
-           "uninstall_adaln"]
+           "uninstall_adaln", "qk_l2norm", "install_qknorm", "uninstall_qknorm"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -1157,7 +1164,7 @@ def install_amp(module, model=None, ffn_half: bool = False) -> None:
         _set_ffn_slots(module, model, fused_mlp_func_amp)
 
 
-def install_train(module, model=None, ffn: bool = False, adaln: bool = False) -> None:
+def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False) -> None:
     """For TRAINING the reference in fp32 with the seam's operators: `module.slow_attn = slow_attn_grad`.  ffn=False (default): `module.fused_mlp_func = None` plus
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
     state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
@@ -1167,14 +1174,18 @@ def install_train(module, model=None, ffn: bool = False, adaln: bool = False) ->
     `ln_wo_grad`: blocks (those with attn, ffn and ada_lin or ada_gss) run basic_var.py:152-159 with adaln_modulate for the two modulations and gated_residual for the
     two residual lines - DropPath's per-image factor, drawn as helpers.py:43-45 draws it, goes in as row_scale - and head norms run :172-174 on adaln_modulate;
     attn and ffn are still called as modules, so the slots above keep working.  uninstall_adaln(model) removes the bound forwards.  adaln=False (default) binds
-    nothing."""
+    nothing.  qknorm=True (needs the model) binds an instance-level `forward` on every submodule that has `mat_qkv` and attn_l2_norm=True: basic_var.py:90-119 with
+    qk_l2norm between the QKV GEMM and the attention call; the attention slots are still read from the reference module at call time.  uninstall_qknorm(model) removes
+    them.  qknorm=False (default) binds nothing."""
     if adaln:
         _install_adaln("install_train", model)
+    if qknorm:
+        _install_qknorm("install_train", model)
     module.slow_attn = slow_attn_grad
     _set_ffn_slots(module, model, fused_mlp_func_grad if ffn else None)
 
 
-def install_train_amp(module, model=None, ffn=False, adaln: bool = False) -> None:
+def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False) -> None:
     """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
     `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
     the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
@@ -1184,9 +1195,12 @@ def install_train_amp(module, model=None, ffn=False, adaln: bool = False) -> Non
     ffn="half".  ffn="half" sets them to fused_mlp_func_amp_grad: the FFN's forward and backward on the half matrix cores in autocast's dtype (float32 or half x,
     float32 master weights; out_features % 32 == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign
     seam.memory_efficient_attention_amp_grad yourself before building the model if you want the BLHc route.  adaln=True: as install_train's; under autocast the
-    modulation vectors and the branch outputs arrive in half and are read as they are."""
+    modulation vectors and the branch outputs arrive in half and are read as they are.  qknorm=True: as install_train's; under autocast qkv arrives in half, q and k
+    leave in float32 and v in half (the mixed operands slow_attn_amp_grad takes)."""
     if adaln:
         _install_adaln("install_train_amp", model)
+    if qknorm:
+        _install_qknorm("install_train_amp", model)
     if isinstance(ffn, str):
         if ffn != "half":
             raise SdvarError(f"install_train_amp: ffn={ffn!r}; expected False, True or 'half'")
@@ -1370,4 +1384,145 @@ def uninstall_adaln(model) -> None:
     for m in model.modules():
         f = m.__dict__.get("forward")
         if getattr(f, "__func__", None) in (_adaln_block_forward, _adaln_head_forward):
+            del m.forward
+
+
+# ------------------------------------------------------------------------------------------------------- attn_l2_norm's QK normalisation (csrc/qknorm_train.hip)
+_QK_LAYOUTS = ("BHLc", "BLHc")
+
+
+def _qk_views(layout: str, *ts):
+    """The (B, L, H, 64) buffers as the layout's views: BLHc as they are, BHLc permuted (what the seam's attention reads in place)."""
+    return tuple(t if layout == "BLHc" else t.permute(0, 2, 1, 3) for t in ts)
+
+
+def _qk_grad(who: str, name: str, g, dtype, layout: str):
+    """An upstream gradient in the layout's dim order -> a (B, L, H, 64) view, read in place under engine.qknorm_grad_in_place, else copied once."""
+    if g is None:
+        return None
+    if g.dtype != dtype:
+        raise SdvarError(f"{who}: the gradient of {name} is {g.dtype} but {name} is {dtype}")
+    if layout == "BHLc":
+        g = g.permute(0, 2, 1, 3)
+    return g if E.qknorm_grad_in_place(g) else g.clone(memory_format=torch.contiguous_format)
+
+
+class _QkNormGrad(torch.autograd.Function):
+    """qk_l2norm with a HIP backward (sdvar_op_qknorm_fwd / sdvar_op_qknorm_bwd).  Saved: qkv, scale_log and the biases; the norms are recomputed in the backward with
+    the forward's code.  Without a v_bias the returned v is a view of the input qkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, scale_log, q_bias, v_bias, max_log, layout):
+        q, k, v = E.qknorm_fwd(qkv, scale_log, max_log, q_bias, v_bias)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(qkv, scale_log, *(t for t in (q_bias,) if t is not None))
+        ctx.qkn = (max_log, layout)
+        if v is None:
+            v = qkv[:, :, 2]
+        return _qk_views(layout, q, k, v)
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        who = "qk_l2norm"
+        _no_double_backward(who)
+        nx, ns, nq, nv = ctx.needs_input_grad[:4]
+        if not (nx or ns or nq or nv) or (dq is None and dk is None and dv is None):
+            return (None,) * 6
+        qkv, scale_log, *rest = ctx.saved_tensors
+        max_log, layout = ctx.qkn
+        dq, dk, dv = _qk_grad(who, "q", dq, torch.float32, layout), _qk_grad(who, "k", dk, torch.float32, layout), _qk_grad(who, "v", dv, qkv.dtype, layout)
+        dqkv, ds, dqb, dvb = E.qknorm_bwd(qkv, scale_log, max_log, rest[0] if rest else None, dq, dk, dv, (nx, ns, nq, nv))
+        return dqkv, ds, dqb, dvb, None, None
+
+
+def qk_l2norm(qkv, scale_log, max_log: float, q_bias=None, v_bias=None, layout: str = "BHLc"):
+    """What SelfAttention.forward does between the QKV GEMM and the attention call when attn_l2_norm is on (basic_var.py:93-105), as one kernel per direction:
+        xq = qkv[:, :, 0] + q_bias;  q = xq / max(|xq|, 1e-12) * exp(min(scale_log[h], max_log));  k = xk / max(|xk|, 1e-12), xk = qkv[:, :, 1];  v = qkv[:, :, 2] + v_bias
+    with the norms over each head's 64 channels.  qkv (B, L, 3, H, 64) float32, float16 or bfloat16 on the GPU (the bias-free QKV GEMM's output, viewed), 1 <= H <= 48;
+    a dense, 16-byte aligned qkv is read in place, anything else is copied once.  scale_log (H) float32: the raw parameter (`scale_mul_1H11.view(H)`); max_log: its
+    clamp (`max_scale_mul`).  q_bias / v_bias (64 H) float32 or None.  Every operation is float32 on the widened values.  Returns (q, k, v): q and k float32, v in
+    qkv's dtype, as views of dense (B, L, H, 64) buffers - layout "BHLc": (B, H, L, 64), what slow_attn reads in place; "BLHc": (B, L, H, 64), what flash_attn_func and
+    memory_efficient_attention read.  Without a v_bias, v is the view of qkv the reference would have produced: nothing is written or copied.  A head with a norm
+    below 1e-12 gives x / 1e-12 (a zero head: exact zeros).
+    THE numerical difference from the reference: under autocast the reference's F.linear rounds acc + half(bias) to half once, inside the GEMM.  Here the float32
+    master bias is added in float32 to the half GEMM output; for q that sum is never rounded back to half, for v it is rounded once.
+    Differentiable: dqkv in qkv's dtype with all three slots written by one kernel (an fp16 overflow is +-inf and reaches the GradScaler; nothing is clamped),
+    dscale_log (zero for a head above max_log, passed at equality, as clamp_max does), dq_bias and dv_bias in float32, summed in a fixed order without atomics: repeats
+    are bit-identical; only the gradients autograd asks for are computed.  Upstream gradients of q and k must be float32 and that of v in qkv's dtype; they are read
+    through their strides (the permuted views the seam's attention backward returns) when the last stride is 1 and the others are multiples of 4, else copied once.
+    Saved for the backward: qkv, scale_log, q_bias.  Under torch.no_grad(), or when nothing requires grad, the same forward kernel runs: the same bits.  Neither
+    direction synchronises with the host.  No double backward."""
+    who = "qk_l2norm"
+    if layout not in _QK_LAYOUTS:
+        raise SdvarError(f"{who}: layout {layout!r}; expected 'BHLc' or 'BLHc'")
+    if isinstance(qkv, torch.Tensor) and qkv.is_cuda and qkv.dim() == 5 and qkv.dtype in E.TRAIN_DTYPES and (not qkv.is_contiguous() or qkv.data_ptr() % 16):
+        qkv = qkv.clone(memory_format=torch.contiguous_format)
+    vecs = [t if not isinstance(t, torch.Tensor) or (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.clone(memory_format=torch.contiguous_format)
+            for t in (scale_log, q_bias, v_bias)]
+    scale_log, q_bias, v_bias = vecs
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (qkv, scale_log, q_bias, v_bias)):
+        E._qknorm_qkv(who, qkv)          # argument errors before autograd wraps them
+        return _QkNormGrad.apply(qkv, scale_log, q_bias, v_bias, float(max_log), layout)
+    d = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    q, k, v = E.qknorm_fwd(d(qkv), d(scale_log), float(max_log), d(q_bias), d(v_bias))
+    return _qk_views(layout, q, k, d(qkv)[:, :, 2] if v is None else v)
+
+
+def _qknorm_attn_forward(self, x, attn_bias):
+    """SelfAttention.forward (basic_var.py:90-119) with qk_l2norm between the QKV GEMM and the attention call.  mat_qkv is called as a module without a bias (the
+    biases go into the kernel); the attention slots and the route choice are read from the class forward's own globals at call time, as the reference reads them."""
+    B, L, Cc = x.shape
+    H = self.num_heads
+    ns = type(self).forward.__globals__
+    qkv = self.mat_qkv(x)
+    main_type = qkv.dtype
+    using_flash = self.using_flash and attn_bias is None and main_type != torch.float32
+    blhc = using_flash or self.using_xform
+    q, k, v = qk_l2norm(qkv.view(B, L, 3, H, Cc // H), self.scale_mul_1H11.view(H), self.max_scale_mul, self.q_bias, self.v_bias, "BLHc" if blhc else "BHLc")
+    dim_cat = 1 if blhc else 2
+    if self.caching:
+        if self.cached_k is None:
+            self.cached_k, self.cached_v = k, v
+        else:
+            k = self.cached_k = torch.cat((self.cached_k, k), dim=dim_cat)
+            v = self.cached_v = torch.cat((self.cached_v, v), dim=dim_cat)
+    dropout_p = self.attn_drop if self.training else 0.0
+    if using_flash:
+        oup = ns["flash_attn_func"](q.to(dtype=main_type), k.to(dtype=main_type), v.to(dtype=main_type), dropout_p=dropout_p, softmax_scale=self.scale).view(B, L, Cc)
+    elif self.using_xform:
+        bias = None if attn_bias is None else attn_bias.to(dtype=main_type).expand(B, H, -1, -1)
+        oup = ns["memory_efficient_attention"](q.to(dtype=main_type), k.to(dtype=main_type), v.to(dtype=main_type), attn_bias=bias, p=dropout_p,
+                                               scale=self.scale).view(B, L, Cc)
+    else:
+        oup = ns["slow_attn"](query=q, key=k, value=v, scale=self.scale, attn_mask=attn_bias, dropout_p=dropout_p).transpose(1, 2).reshape(B, L, Cc)
+    return self.proj_drop(self.proj(oup))
+
+
+_QKNORM_NEEDS = ("q_bias", "v_bias", "scale_mul_1H11", "proj")
+
+
+def _install_qknorm(who: str, model) -> None:
+    if model is None:
+        raise SdvarError(f"{who}: qknorm=True binds a forward on the model's own attention modules; pass the model (model=None has nothing to bind)")
+    for m in model.modules():
+        if not hasattr(m, "mat_qkv") or not getattr(m, "attn_l2_norm", False):
+            continue
+        missing = [n for n in _QKNORM_NEEDS if not hasattr(m, n)]
+        if missing:
+            raise SdvarError(f"{who}: {type(m).__name__} has mat_qkv and attn_l2_norm=True but no {' / '.join(missing)}; qknorm knows SelfAttention-like modules only")
+        m.forward = types.MethodType(_qknorm_attn_forward, m)
+
+
+def install_qknorm(model) -> None:
+    """Bind the qk_l2norm forward on every attention module of `model` that has attn_l2_norm=True (modules without it are left alone), for inference or on top of any
+    of the install_* calls; the attention slots keep working as they are installed.  A module that has mat_qkv but no q_bias / v_bias / scale_mul_1H11 / proj raises."""
+    _install_qknorm("install_qknorm", model)
+
+
+def uninstall_qknorm(model) -> None:
+    """Delete the instance-level `forward` that install_qknorm / install_train(..., qknorm=True) / install_train_amp(..., qknorm=True) bound: the class's own forward is
+    back."""
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if getattr(f, "__func__", None) is _qknorm_attn_forward:
             del m.forward
