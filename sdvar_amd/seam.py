@@ -48,7 +48,7 @@ parameter saved; no double backward).  The float32 master bias is added in float
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
 reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
-read in place; a tensor that does not is copied once with .contiguous().
+read in place; a tensor that does not is copied once into a fresh dense tensor.
 A query row whose keys are ALL masked has no defined value (NaN); other rows are unaffected.
 The same rule holds for flash_attn_func's half operands with 2-byte elements: data_ptr % 16 == 0, every stride a multiple of 8 elements, last stride 1 (the
 unbind(dim=2) views of one (B, L, 3, H, 64) buffer and torch.cat caches meet it).
@@ -105,19 +105,22 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _check_operand(name: str, t: torch.Tensor, who: str) -> None:
+def _gpu_tensor(who: str, name: str, t) -> None:
     if not isinstance(t, torch.Tensor):
         raise SdvarError(f"{who}: {name} is not a tensor")
     if not t.is_cuda:
         raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-    if t.dtype != torch.float32:
-        raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
-    if t.requires_grad and torch.is_grad_enabled():
-        raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
 
 
-def _rows_aligned(t: torch.Tensor) -> bool:
-    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 4 == 0 and s >= 0 for s in t.stride()[:-1])
+def _token_rows(t: torch.Tensor) -> torch.Tensor:
+    """A 4-D operand as the attention kernels read its token rows: t itself when every row is 16-byte aligned (last stride 1, data_ptr % 16 == 0, every other
+    stride a multiple of 16 bytes - 4 float32 elements, 8 half ones), else ONE fresh dense copy.  clone, not .contiguous(): a dense tensor at a misaligned address
+    (a slice of a flat buffer) is its own .contiguous() and would come back as itself."""
+    s0, s1, s2, last = t.stride()
+    m = 4 if t.dtype == torch.float32 else 8
+    if last == 1 and t.data_ptr() % 16 == 0 and s0 % m == 0 and s1 % m == 0 and s2 % m == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
 
 
 def _skip_map(mask: torch.Tensor, kind: int, bstr, Bb: int, Hb: int, Lq: int, Lk: int) -> torch.Tensor:
@@ -134,11 +137,14 @@ def _skip_map(mask: torch.Tensor, kind: int, bstr, Bb: int, Hb: int, Lq: int, Lk
     return smap
 
 
+_NO_MASK = (None, 0, None, None)
+
+
 def _mask_args(who: str, mask, B: int, H: int, Lq: int, Lk: int, half):
     """(mask as the kernel reads it, bias kind, bias strides, skip map) of an attention mask; all None / 0 without one.  half = the operands' half dtype when the kernel
     also takes an additive mask of that dtype (kind 3; the skip map's kind is 3 for fp16, 4 for bf16), else None."""
     if mask is None:
-        return None, 0, None, None
+        return _NO_MASK
     if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
         raise SdvarError(f"{who}: the mask is a CPU tensor (or no tensor)")
     if mask.dtype == torch.bool:
@@ -171,31 +177,110 @@ def _mask_args(who: str, mask, B: int, H: int, Lq: int, Lk: int, half):
     return mask, kind, bstr, smap
 
 
-def _sdpa(who: str, q, k, v, idx, scale: float, mask: Optional[torch.Tensor]) -> torch.Tensor:
-    """idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
-    for name, t in (("query", q), ("key", k), ("value", v)):
-        _check_operand(name, t, who)
+_QKV, _QKV_FLASH = ("query", "key", "value"), ("q", "k", "v")             # what the slots' signatures call their operands
+
+
+def _attn_check(who: str, names, q, k, v, idx, policy: str, twin: Optional[str] = None, mask=None):
+    """The operand check of every attention slot.  names: the slot's words for its operands; idx = positions of (batch, head, token) in their dims.  policy: "f32"
+    (float32 only), "half" (three operands of one half dtype) or "mixed" (value fixes the half dtype, query and key are each that dtype or float32; three float32
+    operands are the fp32 slots' case).  twin: None for a slot that has a backward, else the end of the refusal of an operand that requires grad - the slot's
+    differentiable twin.  mask: the mask of a slot that has a backward, refused when it requires grad.  Returns (B, H, Lq, Lk, half): _mask_args' arguments, half =
+    None for three float32 operands.  A call with several faults reports the one its slot has always reported first, hence the two places of the head dim and of the
+    mask's check."""
+    for name, t in zip(names, (q, k, v)):
+        _gpu_tensor(who, name, t)
+        if policy == "f32":
+            if t.dtype != torch.float32:
+                hint = (" - the autocast slots (slow_attn_amp, flash_attn_func) have no backward; use slow_attn_amp_grad / flash_attn_func_grad"
+                        if twin is None and t.dtype in _HALF_DTYPES else "")
+                raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported{hint}")
+        elif policy == "half":
+            if t.dtype == torch.float32:
+                raise SdvarError(f"{who}: {name} is torch.float32; this slot takes float16 / bfloat16 operands - use slow_attn or memory_efficient_attention for float32")
+            if t.dtype not in _HALF_DTYPES:
+                raise SdvarError(f"{who}: {name} is {t.dtype}; only float16 and bfloat16 operands are supported")
+        elif t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+        if twin is not None and t.requires_grad and torch.is_grad_enabled():
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(){twin})")
         if t.dim() != 4:
             raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
-        if t.shape[-1] != 64:
+        if policy != "half" and t.shape[-1] != 64:
             raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+    mask_grad = isinstance(mask, torch.Tensor) and mask.requires_grad and torch.is_grad_enabled()
+    if mask_grad and policy == "mixed":
+        raise SdvarError(f"{who}: the mask requires grad; there is no gradient for the mask")
+    half = None
+    if policy == "half":
+        if q.dtype != k.dtype or q.dtype != v.dtype:
+            raise SdvarError(f"{who}: mixed dtypes: q {q.dtype}, k {k.dtype}, v {v.dtype} (all three must be float16 or all three bfloat16)")
+        for t in (q, k, v):
+            if t.shape[-1] != 64:
+                raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
+        half = v.dtype
+    elif policy == "mixed" and v.dtype == torch.float32:
+        if q.dtype != torch.float32 or k.dtype != torch.float32:
+            raise SdvarError(f"{who}: value is torch.float32 next to query {q.dtype} / key {k.dtype}: value fixes the dtype of the product and of the result, and a "
+                             "float32 value only goes with float32 query and key")
+    elif policy == "mixed":
+        half = v.dtype
+        for name, t in zip(names, (q, k)):
+            if t.dtype != half and t.dtype != torch.float32:
+                raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype}, value is {half} (query and key must each be {half} or float32)")
     ib, ih, it = idx
     B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
-    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or Lq < 1 or Lk < 1:
-        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
+    # the float32 entries refuse an empty batch themselves; the half slots have always done it here
+    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or Lq < 1 or Lk < 1 or (half is not None and (B < 1 or H < 1)):
+        raise SdvarError(f"{who}: shapes do not match: {names[0]} {tuple(q.shape)}, {names[1]} {tuple(k.shape)}, {names[2]} {tuple(v.shape)}")
     if q.device != k.device or q.device != v.device:
         raise SdvarError(f"{who}: operands live on different devices")
-    q, k, v = (t if _rows_aligned(t) else t.contiguous() for t in (q, k, v))
-    out = torch.empty((B, Lq, H, 64), dtype=torch.float32, device=q.device)
-    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
-    mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, None)
-    E._check(E.load_library().sdvar_op_sdpa(_p(q), _p(k), _p(v), _p(out), strides, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale), E._stream()))
-    return out
+    if mask_grad:
+        raise SdvarError(f"{who}: the mask requires grad; there is no gradient for the mask")
+    return B, H, Lq, Lk, half
+
+
+def _wants_grad(q, k, v) -> bool:
+    return torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+
+
+def _sdpa_launch(q, k, v, idx, scale: float, margs, dims, want_lse: bool):
+    """The forward launch of every attention slot, on checked operands.  margs: _mask_args' result; dims: _attn_check's.  Allocates the (B, Lq, H, 64) output (and the
+    (B, H, Lq) log-sum-exp rows) and picks the entry: float32 operands -> sdvar_op_sdpa / _lse; half operands without a mask, without a float32 query or key and
+    without lse -> sdvar_op_sdpa_h (what flash_attn_func launches: the same bits); any other -> sdvar_op_sdpa_hm / _hm_lse.  Returns (q, k, v) as they were read
+    (in place, or each one's copy), out and lse."""
+    B, H, Lq, Lk, half = dims
+    mask, kind, bstr, smap = margs
+    q, k, v = _token_rows(q), _token_rows(k), _token_rows(v)
+    out = torch.empty((B, Lq, H, 64), dtype=half or torch.float32, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device) if want_lse else None
+    (ib, ih, it), sq, sk, sv, so = idx, q.stride(), k.stride(), v.stride(), out.stride()
+    strides = (C.c_int64 * 12)(sq[ib], sq[ih], sq[it], sk[ib], sk[ih], sk[it], sv[ib], sv[ih], sv[it], so[0], so[2], so[1])
+    lib = E.load_library()
+    outs = (_p(out), _p(lse)) if want_lse else (_p(out),)
+    tail = (B, H, Lq, Lk, 64, float(scale), E._stream())
+    if half is None:
+        entry = lib.sdvar_op_sdpa_lse if want_lse else lib.sdvar_op_sdpa
+        rc = entry(_p(q), _p(k), _p(v), *outs, strides, _p(mask), kind, bstr, _p(smap), *tail)
+    else:
+        qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
+        if kind == 0 and not qf and not kf and not want_lse:
+            rc = lib.sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[half], *tail)
+        else:
+            entry = lib.sdvar_op_sdpa_hm_lse if want_lse else lib.sdvar_op_sdpa_hm
+            rc = entry(_p(q), _p(k), _p(v), *outs, strides, _HALF_DTYPES[half], qf, kf, _p(mask), kind, bstr, _p(smap), *tail)
+    E._check(rc)
+    return q, k, v, out, lse
+
+
+def _sdpa(who: str, q, k, v, idx, scale: float, mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """The float32 inference slots.  idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
+    dims = _attn_check(who, _QKV, q, k, v, idx, "f32", twin="")
+    return _sdpa_launch(q, k, v, idx, scale, _mask_args(who, mask, *dims), dims, False)[3]
 
 
 def slow_attn(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
     """The `slow_attn` slot (basic_var.py:25-30, called at :117): softmax(scale q k^T + attn_mask) v.  query (B, H, Lq, 64), key / value (B, H, Lk, 64) fp32 on the
-    GPU, any strides meeting the alignment rule (read in place), else one .contiguous() copy.  attn_mask: float32 additive or bool keep-mask, broadcastable to
+    GPU, any strides meeting the alignment rule (read in place), else one fresh dense copy.  attn_mask: float32 additive or bool keep-mask, broadcastable to
     (B, H, Lq, Lk) with the key dimension materialised; views (mask[:, :, :ed, :ed]) are read in place.  Returns a (B, H, Lq, 64) VIEW of a (B, Lq, H, 64)
     buffer, so the caller's .transpose(1, 2).reshape(B, L, C) is free."""
     if dropout_p and dropout_p > 0:
@@ -211,73 +296,55 @@ def memory_efficient_attention(q, k, v, attn_bias=None, p: float = 0.0, scale: O
     return _sdpa("memory_efficient_attention", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
-class _SdpaGrad(torch.autograd.Function):
-    """softmax(scale q k^T + mask) v with a HIP backward: forward = sdvar_op_sdpa_lse, backward = one sdvar_op_sdpa_bwd call (csrc/attention_sdpa_bwd.hip)."""
+class _SdpaFn(torch.autograd.Function):
+    """softmax(scale q k^T + mask) v with a HIP backward, on checked operands (dims = _attn_check's result).  Three float32 operands: forward = sdvar_op_sdpa_lse,
+    backward = one sdvar_op_sdpa_bwd call (csrc/attention_sdpa_bwd.hip).  Half / mixed operands: forward = sdvar_op_sdpa_hm_lse, backward = one sdvar_op_sdpa_h_bwd
+    call (csrc/attention_sdpa_h_bwd.hip)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, idx, scale, who):
-        ib, ih, it = idx
-        B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
-        mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, None)
-        q, k, v = (t if _rows_aligned(t) else t.contiguous() for t in (q, k, v))
-        out = torch.empty((B, Lq, H, 64), dtype=torch.float32, device=q.device)
-        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
-        strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
-        E._check(E.load_library().sdvar_op_sdpa_lse(_p(q), _p(k), _p(v), _p(out), _p(lse), strides, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale),
-                                                    E._stream()))
+    def forward(ctx, q, k, v, mask, idx, scale, who, dims):
+        margs = _mask_args(who, mask, *dims)
+        q, k, v, out, lse = _sdpa_launch(q, k, v, idx, scale, margs, dims, True)
+        mask, kind, bstr, smap = margs
         ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask, smap)))
-        ctx.sdpa = (idx, float(scale), kind, bstr, (B, H, Lq, Lk))
+        ctx.sdpa = (idx, float(scale), kind, bstr, dims[:4], dims[4], who)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
+        idx, scale, kind, bstr, (B, H, Lq, Lk), half, who = ctx.sdpa
+        if half is not None and dout.dtype != half:
+            raise SdvarError(f"{who}: the gradient of the output is {dout.dtype} but the output is {half}; the backward reads dout in the output's dtype")
         q, k, v, out, lse, *rest = ctx.saved_tensors
         mask, smap = rest if rest else (None, None)
-        idx, scale, kind, bstr, (B, H, Lq, Lk) = ctx.sdpa
-        # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address would come back as itself
-        if not _rows_aligned(dout):
-            dout = dout.clone(memory_format=torch.contiguous_format)
-        dq, dk, dv = (torch.empty((B, L, H, 64), dtype=torch.float32, device=q.device) if need else None
-                      for need, L in zip(ctx.needs_input_grad[:3], (Lq, Lk, Lk)))
+        dout = _token_rows(dout)
+        dq, dk, dv = (torch.empty((B, L, H, 64), dtype=t.dtype, device=q.device) if need else None
+                      for need, L, t in zip(ctx.needs_input_grad[:3], (Lq, Lk, Lk), (q, k, v)))
         if dq is None and dk is None and dv is None:
-            return (None,) * 7
+            return (None,) * 8
         delta = torch.empty(B * H * Lq, dtype=torch.float32, device=q.device)
-        blhc = lambda t: (0, 0, 0) if t is None else (t.stride(0), t.stride(2), t.stride(1))
-        strides = (C.c_int64 * 24)(*(t.stride(i) for t in (q, k, v) for i in idx), *blhc(out), *blhc(dout), *blhc(dq), *blhc(dk), *blhc(dv))
-        E._check(E.load_library().sdvar_op_sdpa_bwd(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), strides, _p(mask), kind, bstr,
-                                                    _p(smap), B, H, Lq, Lk, 64, scale, E._stream()))
+        def bht(t, order=(0, 2, 1)):        # a tensor's (batch, head, token) strides; the (B, L, H, 64) buffers' order by default
+            s = (0, 0, 0, 0) if t is None else t.stride()
+            return s[order[0]], s[order[1]], s[order[2]]
+        strides = (C.c_int64 * 24)(*bht(q, idx), *bht(k, idx), *bht(v, idx), *bht(out), *bht(dout), *bht(dq), *bht(dk), *bht(dv))
+        ptrs = (_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), strides)
+        tail = (_p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, scale, E._stream())
+        if half is None:
+            E._check(E.load_library().sdvar_op_sdpa_bwd(*ptrs, *tail))
+        else:
+            E._check(E.load_library().sdvar_op_sdpa_h_bwd(*ptrs, _HALF_DTYPES[half], int(q.dtype == torch.float32), int(k.dtype == torch.float32), *tail))
         if idx == (0, 1, 2):                # (B, H, L, 64) operands: views of the (B, L, H, 64) buffers
             dq, dk, dv = (None if t is None else t.permute(0, 2, 1, 3) for t in (dq, dk, dv))
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 def _sdpa_grad(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
-    """The differentiable attention slots.  idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
-    for name, t in (("query", q), ("key", k), ("value", v)):
-        if not isinstance(t, torch.Tensor):
-            raise SdvarError(f"{who}: {name} is not a tensor")
-        if not t.is_cuda:
-            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-        if t.dtype in _HALF_DTYPES:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported - the autocast slots (slow_attn_amp, flash_attn_func) have no backward; use slow_attn_amp_grad / flash_attn_func_grad")
-        if t.dtype != torch.float32:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
-        if t.dim() != 4:
-            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
-        if t.shape[-1] != 64:
-            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
-    ib, ih, it = idx
-    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
-    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or Lq < 1 or Lk < 1:
-        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
-    if q.device != k.device or q.device != v.device:
-        raise SdvarError(f"{who}: operands live on different devices")
-    if isinstance(mask, torch.Tensor) and mask.requires_grad and torch.is_grad_enabled():
-        raise SdvarError(f"{who}: the mask requires grad; there is no gradient for the mask")
-    if not torch.is_grad_enabled() or not (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _sdpa(who, q, k, v, idx, scale, mask)            # what the inference twin launches: the same bits, no LSE
-    return _SdpaGrad.apply(q, k, v, mask, idx, scale, who)
+    """The differentiable float32 attention slots.  idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
+    dims = _attn_check(who, _QKV, q, k, v, idx, "f32", mask=mask)
+    if not _wants_grad(q, k, v):            # what the inference twin launches: the same bits, no LSE
+        return _sdpa_launch(q, k, v, idx, scale, _mask_args(who, mask, *dims), dims, False)[3]
+    return _SdpaFn.apply(q, k, v, mask, idx, scale, who, dims)
 
 
 def slow_attn_grad(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
@@ -300,28 +367,20 @@ def memory_efficient_attention_grad(q, k, v, attn_bias=None, p: float = 0.0, sca
     return _sdpa_grad("memory_efficient_attention_grad", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
-def _rows_aligned_h(t: torch.Tensor) -> bool:
-    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 and s >= 0 for s in t.stride()[:-1])
-
-
 def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: Optional[float] = None, causal: bool = False, window_size=(-1, -1), softcap: float = 0.0,
                     alibi_slopes=None, deterministic: bool = False, return_attn_probs: bool = False):
     """The `flash_attn_func` slot (flash-attn's signature; basic_var.py:23, called at :113 when no mask is passed and qkv is not fp32): softmax(softmax_scale q k^T) v.
     q (B, Lq, H, 64), k / v (B, Lk, H, 64), all three float16 or all three bfloat16 on the GPU; operands meeting the alignment rule are read in place, any other is
     copied once into a dense, freshly allocated tensor.  softmax_scale=None means 1/sqrt(64).  Returns a contiguous (B, Lq, H, 64) tensor of the operand dtype.  fp32 accumulation, the
     softmax weights rounded to the operand dtype (nearest even) for the P V product; deterministic always (`deterministic` is accepted and ignored)."""
-    q, k, v = _flash_check("flash_attn_func", q, k, v, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, False)
-    B, Lq, H, _ = q.shape
-    Lk = k.shape[1]
-    out = torch.empty((B, Lq, H, 64), dtype=q.dtype, device=q.device)
-    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, out) for i in (0, 2, 1)))
-    scale = 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale)
-    E._check(E.load_library().sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[q.dtype], B, H, Lq, Lk, 64, scale, E._stream()))
-    return out
+    who = "flash_attn_func"
+    _flash_options(who, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, False)
+    dims = _attn_check(who, _QKV_FLASH, q, k, v, (0, 2, 1), "half", twin=", or use flash_attn_func_grad")
+    return _sdpa_launch(q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if softmax_scale is None else softmax_scale, _NO_MASK, dims, False)[3]
 
 
-def _flash_check(who: str, q, k, v, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, grad: bool):
-    """The argument checks of the flash_attn_func slots; grad = the caller has a backward.  Returns the operands, each read in place or copied once."""
+def _flash_options(who: str, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, grad: bool) -> None:
+    """The rejections of flash-attn's own keywords; grad = the caller has a backward."""
     if dropout_p and dropout_p > 0:
         raise SdvarError(f"{who}: dropout_p > 0 is not supported " + ("(the reference trains with attn_drop = 0)" if grad else "(inference only)"))
     if causal:
@@ -334,79 +393,13 @@ def _flash_check(who: str, q, k, v, dropout_p, causal, window_size, softcap, ali
         raise SdvarError(f"{who}: alibi_slopes is not supported")
     if return_attn_probs:
         raise SdvarError(f"{who}: return_attn_probs=True is not supported (no score matrix is ever written)")
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if not isinstance(t, torch.Tensor):
-            raise SdvarError(f"{who}: {name} is not a tensor")
-        if not t.is_cuda:
-            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-        if t.dtype == torch.float32:
-            raise SdvarError(f"{who}: {name} is torch.float32; this slot takes float16 / bfloat16 operands - use slow_attn or memory_efficient_attention for float32")
-        if t.dtype not in _HALF_DTYPES:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float16 and bfloat16 operands are supported")
-        if not grad and t.requires_grad and torch.is_grad_enabled():
-            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use flash_attn_func_grad)")
-        if t.dim() != 4:
-            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
-    if q.dtype != k.dtype or q.dtype != v.dtype:
-        raise SdvarError(f"{who}: mixed dtypes: q {q.dtype}, k {k.dtype}, v {v.dtype} (all three must be float16 or all three bfloat16)")
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.shape[-1] != 64:
-            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
-    B, Lq, H, _ = q.shape
-    Lk = k.shape[1]
-    if k.shape != v.shape or k.shape[0] != B or k.shape[2] != H or B < 1 or H < 1 or Lq < 1 or Lk < 1:
-        raise SdvarError(f"{who}: shapes do not match: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
-    if q.device != k.device or q.device != v.device:
-        raise SdvarError(f"{who}: operands live on different devices")
-    if grad:                # the autograd function copies what it must itself (its inputs stay the caller's tensors)
-        return q, k, v
-    # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
-    return tuple(t if _rows_aligned_h(t) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
 
 
 def _sdpa_amp(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
-    """The attention slots under torch.autocast.  idx = positions of (batch, head, token) in the operands' dims.  Returns the (B, Lq, H, 64) output buffer."""
-    for name, t in (("query", q), ("key", k), ("value", v)):
-        if not isinstance(t, torch.Tensor):
-            raise SdvarError(f"{who}: {name} is not a tensor")
-        if not t.is_cuda:
-            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
-        if t.requires_grad and torch.is_grad_enabled():
-            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use slow_attn_amp_grad / memory_efficient_attention_amp_grad)")
-        if t.dim() != 4:
-            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
-        if t.shape[-1] != 64:
-            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
-    if v.dtype == torch.float32:
-        if q.dtype != torch.float32 or k.dtype != torch.float32:
-            raise SdvarError(f"{who}: value is torch.float32 next to query {q.dtype} / key {k.dtype}: value fixes the dtype of the product and of the result, and a "
-                             "float32 value only goes with float32 query and key")
-        return _sdpa(who, q, k, v, idx, scale, mask)
-    half = v.dtype
-    for name, t in (("query", q), ("key", k)):
-        if t.dtype != half and t.dtype != torch.float32:
-            raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype}, value is {half} (query and key must each be {half} or float32)")
-    ib, ih, it = idx
-    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
-    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or B < 1 or H < 1 or Lq < 1 or Lk < 1:
-        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
-    if q.device != k.device or q.device != v.device:
-        raise SdvarError(f"{who}: operands live on different devices")
-    mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, half)
-    # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
-    q, k, v = (t if (_rows_aligned(t) if t.dtype == torch.float32 else _rows_aligned_h(t)) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
-    out = torch.empty((B, Lq, H, 64), dtype=half, device=q.device)
-    strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
-    qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
-    lib = E.load_library()
-    if kind == 0 and not qf and not kf:                 # what flash_attn_func launches: the same bits
-        E._check(lib.sdvar_op_sdpa_h(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[half], B, H, Lq, Lk, 64, float(scale), E._stream()))
-    else:
-        E._check(lib.sdvar_op_sdpa_hm(_p(q), _p(k), _p(v), _p(out), strides, _HALF_DTYPES[half], qf, kf, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, float(scale),
-                                      E._stream()))
-    return out
+    """The attention slots under torch.autocast; three float32 operands are the float32 slots' call.  idx = positions of (batch, head, token) in the operands' dims.
+    Returns the (B, Lq, H, 64) output buffer."""
+    dims = _attn_check(who, _QKV, q, k, v, idx, "mixed", twin=", or use slow_attn_amp_grad / memory_efficient_attention_amp_grad")
+    return _sdpa_launch(q, k, v, idx, scale, _mask_args(who, mask, *dims), dims, False)[3]
 
 
 def slow_attn_amp(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
@@ -431,88 +424,15 @@ def memory_efficient_attention_amp(q, k, v, attn_bias=None, p: float = 0.0, scal
     return _sdpa_amp("memory_efficient_attention_amp", q, k, v, (0, 2, 1), 1.0 / math.sqrt(64.0) if scale is None else scale, attn_bias)
 
 
-class _SdpaAmpGrad(torch.autograd.Function):
-    """softmax(scale q k^T + mask) v on half / mixed operands with a HIP backward: forward = sdvar_op_sdpa_hm_lse, backward = one sdvar_op_sdpa_h_bwd call
-    (csrc/attention_sdpa_h_bwd.hip)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, mask, idx, scale, who):
-        ib, ih, it = idx
-        B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
-        half = v.dtype
-        mask, kind, bstr, smap = _mask_args(who, mask, B, H, Lq, Lk, half)
-        # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address (a slice of a flat buffer) would come back as itself
-        q, k, v = (t if (_rows_aligned(t) if t.dtype == torch.float32 else _rows_aligned_h(t)) else t.clone(memory_format=torch.contiguous_format) for t in (q, k, v))
-        out = torch.empty((B, Lq, H, 64), dtype=half, device=q.device)
-        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
-        strides = (C.c_int64 * 12)(*(t.stride(i) for t in (q, k, v) for i in idx), out.stride(0), out.stride(2), out.stride(1))
-        qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
-        E._check(E.load_library().sdvar_op_sdpa_hm_lse(_p(q), _p(k), _p(v), _p(out), _p(lse), strides, _HALF_DTYPES[half], qf, kf, _p(mask), kind, bstr, _p(smap), B, H,
-                                                       Lq, Lk, 64, float(scale), E._stream()))
-        ctx.save_for_backward(q, k, v, out, lse, *(() if mask is None else (mask, smap)))
-        ctx.sdpa = (idx, float(scale), kind, bstr, (B, H, Lq, Lk), half, who)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dout):
-        idx, scale, kind, bstr, (B, H, Lq, Lk), half, who = ctx.sdpa
-        if dout.dtype != half:
-            raise SdvarError(f"{who}: the gradient of the output is {dout.dtype} but the output is {half}; the backward reads dout in the output's dtype")
-        q, k, v, out, lse, *rest = ctx.saved_tensors
-        mask, smap = rest if rest else (None, None)
-        # a fresh dense copy, not .contiguous(): a dense tensor at a misaligned address would come back as itself
-        if not _rows_aligned_h(dout):
-            dout = dout.clone(memory_format=torch.contiguous_format)
-        dq, dk, dv = (torch.empty((B, L, H, 64), dtype=t.dtype, device=q.device) if need else None
-                      for need, L, t in zip(ctx.needs_input_grad[:3], (Lq, Lk, Lk), (q, k, v)))
-        if dq is None and dk is None and dv is None:
-            return (None,) * 7
-        delta = torch.empty(B * H * Lq, dtype=torch.float32, device=q.device)
-        blhc = lambda t: (0, 0, 0) if t is None else (t.stride(0), t.stride(2), t.stride(1))
-        strides = (C.c_int64 * 24)(*(t.stride(i) for t in (q, k, v) for i in idx), *blhc(out), *blhc(dout), *blhc(dq), *blhc(dk), *blhc(dv))
-        qf, kf = int(q.dtype == torch.float32), int(k.dtype == torch.float32)
-        E._check(E.load_library().sdvar_op_sdpa_h_bwd(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), strides, _HALF_DTYPES[half],
-                                                      qf, kf, _p(mask), kind, bstr, _p(smap), B, H, Lq, Lk, 64, scale, E._stream()))
-        if idx == (0, 1, 2):                # (B, H, L, 64) operands: views of the (B, L, H, 64) buffers
-            dq, dk, dv = (None if t is None else t.permute(0, 2, 1, 3) for t in (dq, dk, dv))
-        return dq, dk, dv, None, None, None, None
-
-
 def _sdpa_amp_grad(who: str, q, k, v, idx, scale: float, mask) -> torch.Tensor:
     """The differentiable attention slots under torch.autocast: _sdpa_amp's operand rules, minus its refusal of operands that require grad.  Returns the
     (B, Lq, H, 64) output buffer."""
-    for name, t in (("query", q), ("key", k), ("value", v)):
-        if not isinstance(t, torch.Tensor):
-            raise SdvarError(f"{who}: {name} is not a tensor")
-        if not t.is_cuda:
-            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
-        if t.dim() != 4:
-            raise SdvarError(f"{who}: {name} has {t.dim()} dims, expected 4")
-        if t.shape[-1] != 64:
-            raise SdvarError(f"{who}: head dim {t.shape[-1]}; only 64 is supported")
-    if isinstance(mask, torch.Tensor) and mask.requires_grad and torch.is_grad_enabled():
-        raise SdvarError(f"{who}: the mask requires grad; there is no gradient for the mask")
-    if v.dtype == torch.float32:
-        if q.dtype != torch.float32 or k.dtype != torch.float32:
-            raise SdvarError(f"{who}: value is torch.float32 next to query {q.dtype} / key {k.dtype}: value fixes the dtype of the product and of the result, and a "
-                             "float32 value only goes with float32 query and key")
+    dims = _attn_check(who, _QKV, q, k, v, idx, "mixed", mask=mask)
+    if dims[4] is None:
         return _sdpa_grad(who, q, k, v, idx, scale, mask)           # three fp32 operands: the fp32 slots' path, unchanged
-    half = v.dtype
-    for name, t in (("query", q), ("key", k)):
-        if t.dtype != half and t.dtype != torch.float32:
-            raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype}, value is {half} (query and key must each be {half} or float32)")
-    if not torch.is_grad_enabled() or not (q.requires_grad or k.requires_grad or v.requires_grad):
+    if not _wants_grad(q, k, v):
         return _sdpa_amp(who, q, k, v, idx, scale, mask)            # what the inference twin launches: the same bits, no LSE
-    ib, ih, it = idx
-    B, H, Lq, Lk = q.shape[ib], q.shape[ih], q.shape[it], k.shape[it]
-    if k.shape != v.shape or k.shape[ib] != B or k.shape[ih] != H or B < 1 or H < 1 or Lq < 1 or Lk < 1:
-        raise SdvarError(f"{who}: shapes do not match: query {tuple(q.shape)}, key {tuple(k.shape)}, value {tuple(v.shape)}")
-    if q.device != k.device or q.device != v.device:
-        raise SdvarError(f"{who}: operands live on different devices")
-    return _SdpaAmpGrad.apply(q, k, v, mask, idx, scale, who)
+    return _SdpaFn.apply(q, k, v, mask, idx, scale, who, dims)
 
 
 def slow_attn_amp_grad(query, key, value, scale: float, attn_mask=None, dropout_p: float = 0.0):
@@ -544,10 +464,16 @@ def flash_attn_func_grad(q, k, v, dropout_p: float = 0.0, softmax_scale: Optiona
     With grad mode off, or no operand requiring grad, it IS flash_attn_func (same launch, same bits).  Otherwise memory_efficient_attention_amp_grad's function
     without a bias: the output has flash_attn_func's bits, gradients are dense (B, L, H, 64) tensors of the operand dtype."""
     who = "flash_attn_func_grad"
-    q, k, v = _flash_check(who, q, k, v, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, True)
-    if not torch.is_grad_enabled() or not (q.requires_grad or k.requires_grad or v.requires_grad):
+    _flash_options(who, dropout_p, causal, window_size, softcap, alibi_slopes, return_attn_probs, True)
+    dims = _attn_check(who, _QKV_FLASH, q, k, v, (0, 2, 1), "half")
+    if not _wants_grad(q, k, v):
         return flash_attn_func(q, k, v, softmax_scale=softmax_scale)
-    return _SdpaAmpGrad.apply(q, k, v, None, (0, 2, 1), 1.0 / math.sqrt(64.0) if softmax_scale is None else float(softmax_scale), who)
+    return _SdpaFn.apply(q, k, v, None, (0, 2, 1), 1.0 / math.sqrt(64.0) if softmax_scale is None else softmax_scale, who, dims)
+
+
+def _dense16(t: torch.Tensor) -> torch.Tensor:
+    """t itself when it is dense and 16-byte aligned, else one fresh dense copy (.contiguous() would hand back a dense tensor at a misaligned address)."""
+    return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
 def _cached_planes(kind: str, w: torch.Tensor, mode: str, make):
@@ -566,23 +492,27 @@ def _cached_planes(kind: str, w: torch.Tensor, mode: str, make):
     return planes, sc
 
 
-def _weight_planes(w: torch.Tensor, mode: str):
-    def make():
-        lib = E.load_library()
-        N, K = w.shape
-        wc = w.detach().contiguous()
-        if mode == "f16x2":
-            planes, sc = torch.empty(2, N * K, dtype=torch.int16, device=w.device), torch.zeros(4, dtype=torch.float32, device=w.device)
-            E._check(lib.sdvar_op_split_planes_f16(_p(wc), _p(planes), N, K, N * K, _p(sc), E._stream()))
-        else:
-            planes, sc = torch.empty(3, N * K, dtype=torch.int16, device=w.device), None
-            E._check(lib.sdvar_op_split_planes(_p(wc), _p(planes), N, K, N * K, E._stream()))
-        return planes, sc
-    return _cached_planes("n", w, mode, make)
-
-
 _OPERAND_FORMAT = {"f32": 0, "f16x2": 2, "bf16x3": 3}       # csrc/mlp_bwd.hip
 _OPERAND_PLANES = {"f32": 1, "f16x2": 2, "bf16x3": 3}
+
+
+def _split_planes(t: torch.Tensor, mode: str, rows: int, cols: int, scale: Optional[torch.Tensor] = None, st=None) -> torch.Tensor:
+    """The K-blocked operand planes of a dense fp32 (rows, cols) tensor in mode f16x2 (scale: the device scale the split writes, or None for the unscaled split)
+    or bf16x3.  st: the current stream, when the caller has looked it up already."""
+    planes = torch.empty(_OPERAND_PLANES[mode], rows * cols, dtype=torch.int16, device=t.device)
+    st = E._stream() if st is None else st
+    if mode == "f16x2":
+        E._check(E.load_library().sdvar_op_split_planes_f16(_p(t), _p(planes), rows, cols, rows * cols, _p(scale), st))
+    else:
+        E._check(E.load_library().sdvar_op_split_planes(_p(t), _p(planes), rows, cols, rows * cols, st))
+    return planes
+
+
+def _weight_planes(w: torch.Tensor, mode: str):
+    def make():
+        sc = torch.zeros(4, dtype=torch.float32, device=w.device) if mode == "f16x2" else None
+        return _split_planes(w.detach().contiguous(), mode, *w.shape, sc), sc
+    return _cached_planes("n", w, mode, make)
 
 
 def _pad32(n: int) -> int:
@@ -603,46 +533,79 @@ def _weight_planes_t(w: torch.Tensor, mode: str):
     """(operand of w^T, scale): the dgrad GEMMs' weight operand, cached like the forward's.  In mode f16x2 it carries the forward planes' scale."""
     def make():
         sc = _weight_planes(w, mode)[1] if mode == "f16x2" else None
-        wc = w.detach().contiguous()
-        if wc.data_ptr() % 16:
-            wc = wc.clone()
-        return _transposed_operand(wc, mode, sc), sc
+        return _transposed_operand(_dense16(w.detach()), mode, sc), sc
     return _cached_planes("t", w, mode, make)
 
 
-def _mlp_check(who: str, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, grad: bool):
+def _mlp_check(who: str, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, amp: bool, grad: bool, bias_shapes: bool = True):
+    """The argument checks of the FFN slots.  amp: the dtype policy - False: float32 operands only; True: every operand float32 or the call's half dtype (x.dtype when
+    x is half, else the GPU's autocast dtype).  grad = the caller has a backward.  bias_shapes=False: fused_mlp_func alone has never looked at its biases' shapes.
+    Returns (half or None, Cin, hid, Cout).  Nothing here touches the library."""
     if activation != "gelu_approx":
         raise SdvarError(f"{who}: activation {activation!r}; only 'gelu_approx' (tanh GELU) is built")
     if return_residual:
         raise SdvarError(f"{who}: return_residual=True is not supported")
     if process_group is not None:
         raise SdvarError(f"{who}: a process group (tensor-parallel MLP) is not supported")
-    for name, t in (("x", x), ("weight1", weight1), ("weight2", weight2)) + tuple((n, b) for n, b in (("bias1", bias1), ("bias2", bias2)) if b is not None):
-        if grad:
-            if not isinstance(t, torch.Tensor):
-                raise SdvarError(f"{who}: {name} is not a tensor")
-            if not t.is_cuda:
-                raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-            if t.dtype != torch.float32:
-                raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
-        else:
-            _check_operand(name, t, who)
+    named = [("x", x), ("weight1", weight1), ("weight2", weight2)]
+    if bias1 is not None:
+        named.append(("bias1", bias1))
+    if bias2 is not None:
+        named.append(("bias2", bias2))
+    refuse = not grad and torch.is_grad_enabled()
+    for name, t in named:
+        _gpu_tensor(who, name, t)
+        if amp:
+            if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+                raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+        elif t.dtype != torch.float32:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
+        elif refuse and t.requires_grad:
+            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad())")
+    half = None
+    if amp:
+        half = x.dtype if x.dtype in _HALF_DTYPES else _autocast_gpu_dtype()
+        if half not in _HALF_DTYPES:
+            twin = "fused_mlp_func_grad" if grad else "fused_mlp_func"
+            raise SdvarError(f"{who}: x is {x.dtype} and torch.autocast is not enabled for the GPU with float16 / bfloat16: there is no half dtype to compute in - "
+                             f"call it under torch.autocast or with a half x, or use fused_mlp_func / {twin} for float32 arithmetic")
+        for name, t in named:
+            if t.dtype != torch.float32 and t.dtype != half:
+                raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype} but the half dtype of the call is {half} (every operand must be {half} or float32)")
+            if refuse and t.requires_grad:
+                raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use fused_mlp_func_amp_grad)")
     if weight1.dim() != 2 or weight2.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight1.shape[1] or weight2.shape[1] != weight1.shape[0]:
         raise SdvarError(f"{who}: shapes do not chain: x {tuple(x.shape)}, weight1 {tuple(weight1.shape)}, weight2 {tuple(weight2.shape)}")
     Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
     if Cin % 32 or hid % 32:
         raise SdvarError(f"{who}: in_features {Cin} and hidden_features {hid} must be multiples of 32")
-    for name, b, n in (("bias1", bias1, hid), ("bias2", bias2, Cout)):
-        if grad and b is not None and tuple(b.shape) != (n,):
+    if amp and Cout % 8:
+        raise SdvarError(f"{who}: out_features {Cout} must be a multiple of 8")
+    for name, b, n in (("bias1", bias1, hid), ("bias2", bias2, Cout)) if bias_shapes else ():
+        if b is not None and tuple(b.shape) != (n,):
             raise SdvarError(f"{who}: {name} has shape {tuple(b.shape)}, expected ({n},)")
-    return Cin, hid, Cout
+    if amp and any(t.device != x.device for _, t in named):
+        raise SdvarError(f"{who}: operands live on different devices")
+    return half, Cin, hid, Cout
+
+
+def _gemm_nt(mode: str, A, B, wscale, out, M: int, N: int, K: int, bias=None, epilogue: int = 0, planes=None, st=None) -> None:
+    """epilogue(A (M x K) . B (N x K)^T + bias) on operands of `mode` (fp32 dense, or K-blocked planes); wscale: the f16x2 GEMM's device scale pointer or None;
+    epilogue 1 = tanh GELU.  The result goes to out (M, N) fp32 and / or, in the plane modes, to `planes`: the operand planes the next GEMM reads.  st: the current
+    stream, when the caller has looked it up already."""
+    lib, st, ldp = E.load_library(), E._stream() if st is None else st, 0 if planes is None else M * N
+    if mode == "f32":
+        E._check(lib.sdvar_op_gemm(_p(A), K, _p(B), _p(bias), _p(out), N, M, N, K, epilogue, None, 0, None, 1, 0, st))
+    elif mode == "f16x2":
+        E._check(lib.sdvar_op_gemm_f16x2(_p(A), M * K, _p(B), N * K, wscale, _p(bias), _p(out), N, _p(planes), ldp, M, N, K, epilogue, None, 0, None, 1, 0, st))
+    else:
+        E._check(lib.sdvar_op_gemm_bf16x3(_p(A), M * K, _p(B), N * K, _p(bias), _p(out), N, _p(planes), ldp, M, N, K, epilogue, None, 0, None, 1, 0, st))
 
 
 def _mlp_forward(x, weight1, weight2, bias1, bias2, mode: str, keep_pre: bool):
     """(out, xr, pre).  keep_pre False: the inference launches (fc1 with the GELU epilogue).  True: fc1 with the bias epilogue leaves pre (M, hid) in memory and
     sdvar_op_gelu_operand writes what the GELU epilogue would have - the same bits, so `out` is the same in both."""
     Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
-    lib, st = E.load_library(), E._stream()
     xr = x.detach().reshape(-1, Cin).contiguous()
     M = xr.shape[0]
     out = torch.empty(tuple(x.shape[:-1]) + (Cout,), dtype=torch.float32, device=x.device)
@@ -651,37 +614,21 @@ def _mlp_forward(x, weight1, weight2, bias1, bias2, mode: str, keep_pre: bool):
     b1 = torch.zeros(hid, dtype=torch.float32, device=x.device) if bias1 is None else bias1.detach().contiguous()
     b2 = torch.zeros(Cout, dtype=torch.float32, device=x.device) if bias2 is None else bias2.detach().contiguous()
     pre = torch.empty(M, hid, dtype=torch.float32, device=x.device) if keep_pre else None
-    fmt = _OPERAND_FORMAT[mode]
-    if mode == "f32":
-        w1, w2 = weight1.detach().contiguous(), weight2.detach().contiguous()
+    st, f32 = E._stream(), mode == "f32"
+    # xo, h: the operands of fc1 and fc2 - dense fp32 in mode f32, else planes, which fc1 writes through its plane output
+    if f32:
+        (w1, s1), (w2, s2), xo = (weight1.detach().contiguous(), None), (weight2.detach().contiguous(), None), xr
         h = torch.empty(M, hid, dtype=torch.float32, device=x.device)
-        if keep_pre:
-            E._check(lib.sdvar_op_gemm(_p(xr), Cin, _p(w1), _p(b1), _p(pre), hid, M, hid, Cin, 0, None, 0, None, 1, 0, st))
-            E._check(lib.sdvar_op_gelu_operand(_p(pre), M, hid, fmt, 0, _p(h), 0, st))
-        else:
-            E._check(lib.sdvar_op_gemm(_p(xr), Cin, _p(w1), _p(b1), _p(h), hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
-        E._check(lib.sdvar_op_gemm(_p(h), hid, _p(w2), _p(b2), _p(out), Cout, M, Cout, hid, 0, None, 0, None, 1, 0, st))
-        return out, xr, pre
-    (w1p, s1), (w2p, s2) = _weight_planes(weight1, mode), _weight_planes(weight2, mode)
-    npl = 2 if mode == "f16x2" else 3
-    xp = torch.empty(npl, M * Cin, dtype=torch.int16, device=x.device)
-    hp = torch.empty(npl, M * hid, dtype=torch.int16, device=x.device)
-    if mode == "f16x2":
-        E._check(lib.sdvar_op_split_planes_f16(_p(xr), _p(xp), M, Cin, M * Cin, None, st))
-        if keep_pre:
-            E._check(lib.sdvar_op_gemm_f16x2(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(s1), _p(b1), _p(pre), hid, None, 0, M, hid, Cin, 0, None, 0, None, 1, 0, st))
-            E._check(lib.sdvar_op_gelu_operand(_p(pre), M, hid, fmt, 1, _p(hp), M * hid, st))
-        else:
-            E._check(lib.sdvar_op_gemm_f16x2(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(s1), _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
-        E._check(lib.sdvar_op_gemm_f16x2(_p(hp), M * hid, _p(w2p), Cout * hid, _p(s2), _p(b2), _p(out), Cout, None, 0, M, Cout, hid, 0, None, 0, None, 1, 0, st))
     else:
-        E._check(lib.sdvar_op_split_planes(_p(xr), _p(xp), M, Cin, M * Cin, st))
-        if keep_pre:
-            E._check(lib.sdvar_op_gemm_bf16x3(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(b1), _p(pre), hid, None, 0, M, hid, Cin, 0, None, 0, None, 1, 0, st))
-            E._check(lib.sdvar_op_gelu_operand(_p(pre), M, hid, fmt, 0, _p(hp), M * hid, st))
-        else:
-            E._check(lib.sdvar_op_gemm_bf16x3(_p(xp), M * Cin, _p(w1p), hid * Cin, _p(b1), None, hid, _p(hp), M * hid, M, hid, Cin, 1, None, 0, None, 1, 0, st))
-        E._check(lib.sdvar_op_gemm_bf16x3(_p(hp), M * hid, _p(w2p), Cout * hid, _p(b2), _p(out), Cout, None, 0, M, Cout, hid, 0, None, 0, None, 1, 0, st))
+        (w1, s1), (w2, s2) = _weight_planes(weight1, mode), _weight_planes(weight2, mode)
+        xo = _split_planes(xr, mode, M, Cin, st=st)
+        h = torch.empty(_OPERAND_PLANES[mode], M * hid, dtype=torch.int16, device=x.device)
+    if keep_pre:
+        _gemm_nt(mode, xo, w1, _p(s1), pre, M, hid, Cin, b1, st=st)
+        E._check(E.load_library().sdvar_op_gelu_operand(_p(pre), M, hid, _OPERAND_FORMAT[mode], int(mode == "f16x2"), _p(h), 0 if f32 else M * hid, st))
+    else:
+        _gemm_nt(mode, xo, w1, _p(s1), h if f32 else None, M, hid, Cin, b1, 1, None if f32 else h, st)
+    _gemm_nt(mode, h, w2, _p(s2), out, M, Cout, hid, b2, st=st)
     return out, xr, pre
 
 
@@ -690,19 +637,8 @@ def fused_mlp_func(x, weight1, weight2, bias1=None, bias2=None, activation: str 
     """The `fused_mlp_func` slot (flash_attn.ops.fused_dense signature; basic_var.py:46-50): fc2(gelu_tanh(fc1(x))), x (..., C) fp32 on the GPU, weight1 (hidden, C),
     weight2 (out, hidden).  Two launches of the operator GEMMs of the configured mode (seam.configure): fc1 with the GELU epilogue writing the operand planes of fc2
     directly.  C and hidden must be multiples of 32.  save_pre_act / checkpoint_lvl / heuristic only matter to a backward and are ignored."""
-    _mlp_check("fused_mlp_func", x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, False)
+    _mlp_check("fused_mlp_func", x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, False, False, bias_shapes=False)
     return _mlp_forward(x, weight1, weight2, bias1, bias2, _gemm_mode, False)[0]
-
-
-def _gemm_nt(mode: str, A, B, wscale, out, M: int, N: int, K: int) -> None:
-    """out (M, N) fp32 = A (M x K) . B (N x K)^T on operands of `mode` (fp32 dense, or K-blocked planes); wscale: the f16x2 GEMM's device scale pointer or None."""
-    lib, st = E.load_library(), E._stream()
-    if mode == "f32":
-        E._check(lib.sdvar_op_gemm(_p(A), K, _p(B), None, _p(out), N, M, N, K, 0, None, 0, None, 1, 0, st))
-    elif mode == "f16x2":
-        E._check(lib.sdvar_op_gemm_f16x2(_p(A), M * K, _p(B), N * K, wscale, None, _p(out), N, None, 0, M, N, K, 0, None, 0, None, 1, 0, st))
-    else:
-        E._check(lib.sdvar_op_gemm_bf16x3(_p(A), M * K, _p(B), N * K, None, _p(out), N, None, 0, M, N, K, 0, None, 0, None, 1, 0, st))
 
 
 class _MlpGrad(torch.autograd.Function):
@@ -730,11 +666,8 @@ class _MlpGrad(torch.autograd.Function):
         lib, st, fmt, npl, Mp = E.load_library(), E._stream(), _OPERAND_FORMAT[mode], _OPERAND_PLANES[mode], _pad32(M)
         kind, h16, el = int(mode == "f16x2"), mode == "f16x2", torch.float32 if mode == "f32" else torch.int16
         operand = lambda n: torch.empty(npl, n, dtype=el, device=dev)
-        dy = dy.reshape(M, Cout)
-        if not dy.is_contiguous() or dy.data_ptr() % 16:      # stride-0 expansions, transposed consumers, a dense tensor at a misaligned address: one fresh dense copy
-            dy = dy.clone(memory_format=torch.contiguous_format)
-        if xr.data_ptr() % 16:
-            xr = xr.clone()
+        dy = _dense16(dy.reshape(M, Cout))          # stride-0 expansions, transposed consumers, a dense tensor at a misaligned address: one fresh dense copy
+        xr = _dense16(xr)
         need_dh = nx or nw1 or nb1
         dx = dw1 = dw2 = db1 = db2 = None
         if nb2:
@@ -747,17 +680,11 @@ class _MlpGrad(torch.autograd.Function):
         dpre = dpre_t = h_t = part = None
         if need_dh:
             w2t, s2 = _weight_planes_t(weight2, mode)
-            if mode == "f32":
-                dyo = dy
-            elif h16:
-                dyo = operand(M * Cout)
-                E._check(lib.sdvar_op_split_planes_f16(_p(dy), _p(dyo), M, Cout, M * Cout, _p(sdy), st))
+            dyo = dy if mode == "f32" else _split_planes(dy, mode, M, Cout, sdy, st)
+            if h16:
                 E._check(lib.sdvar_op_scale_pair(None, 0, _p(sdy), 0, _p(s2), st))
-            else:
-                dyo = operand(M * Cout)
-                E._check(lib.sdvar_op_split_planes(_p(dy), _p(dyo), M, Cout, M * Cout, st))
             dh = f32(M, hid)
-            _gemm_nt(mode, dyo, w2t, off(sdy, 2), dh, M, hid, Cout)
+            _gemm_nt(mode, dyo, w2t, off(sdy, 2), dh, M, hid, Cout, st=st)
             if h16:          # |gelu'| <= 1.13: half of dh's scale keeps dpre inside the range without a second pass
                 E._check(lib.sdvar_op_scale_pair(_p(dh), M * hid, _p(sdp), 1, _p(_weight_planes(weight1, mode)[1]) if nx else None, st))
             if nx:
@@ -777,14 +704,14 @@ class _MlpGrad(torch.autograd.Function):
         if nx:
             w1t, _ = _weight_planes_t(weight1, mode)
             dx = f32(M, Cin)
-            _gemm_nt(mode, dpre, w1t, off(sdp, 2), dx, M, Cin, hid)
+            _gemm_nt(mode, dpre, w1t, off(sdp, 2), dx, M, Cin, hid, st=st)
             dx = dx.view(xshape)
         if nw2:
             dw2 = f32(Cout, hid)
-            _gemm_nt(mode, _transposed_operand(dy, mode, sdy), h_t, off(sdy, 0), dw2, Cout, hid, Mp)
+            _gemm_nt(mode, _transposed_operand(dy, mode, sdy), h_t, off(sdy, 0), dw2, Cout, hid, Mp, st=st)
         if nw1:
             dw1 = f32(hid, Cin)
-            _gemm_nt(mode, dpre_t, _transposed_operand(xr, mode), off(sdp, 0), dw1, hid, Cin, Mp)
+            _gemm_nt(mode, dpre_t, _transposed_operand(xr, mode), off(sdp, 0), dw1, hid, Cin, Mp, st=st)
         if nb1:
             db1 = f32(hid)
             E._check(lib.sdvar_op_colsum(_p(part), hid, Mp // 32, hid, _p(db1), st))
@@ -803,7 +730,7 @@ def fused_mlp_func_grad(x, weight1, weight2, bias1=None, bias2=None, activation:
     has in the full run.  Mode f16x2 splits the gradient operands with a per-tensor power-of-two scale.  No double backward, float32 only; save_pre_act /
     checkpoint_lvl / heuristic are accepted and ignored."""
     who = "fused_mlp_func_grad"
-    Cin, hid, Cout = _mlp_check(who, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, True)
+    _, Cin, hid, Cout = _mlp_check(who, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, False, True)
     tensors = [t for t in (x, weight1, weight2, bias1, bias2) if t is not None]
     if not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors):
         return _mlp_forward(x, weight1, weight2, bias1, bias2, _gemm_mode, False)[0]            # what the inference twin launches: the same bits
@@ -820,52 +747,6 @@ def _autocast_gpu_dtype():
     if hasattr(torch, "get_autocast_dtype"):
         return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
     return torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None
-
-
-def _mlp_amp_check(who: str, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, grad: bool):
-    """The argument checks of the half-precision FFN slots; grad = the caller has a backward.  Returns (half dtype, Cin, hid, Cout).  Nothing here touches the library."""
-    if activation != "gelu_approx":
-        raise SdvarError(f"{who}: activation {activation!r}; only 'gelu_approx' (tanh GELU) is built")
-    if return_residual:
-        raise SdvarError(f"{who}: return_residual=True is not supported")
-    if process_group is not None:
-        raise SdvarError(f"{who}: a process group (tensor-parallel MLP) is not supported")
-    named = (("x", x), ("weight1", weight1), ("weight2", weight2)) + tuple((n, b) for n, b in (("bias1", bias1), ("bias2", bias2)) if b is not None)
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise SdvarError(f"{who}: {name} is not a tensor")
-        if not t.is_cuda:
-            raise SdvarError(f"{who}: {name} is a CPU tensor (the kernels run on the GPU; there is no CPU path)")
-        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
-            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
-    half = x.dtype if x.dtype in _HALF_DTYPES else _autocast_gpu_dtype()
-    if half not in _HALF_DTYPES:
-        twin = "fused_mlp_func_grad" if grad else "fused_mlp_func"
-        raise SdvarError(f"{who}: x is {x.dtype} and torch.autocast is not enabled for the GPU with float16 / bfloat16: there is no half dtype to compute in - "
-                         f"call it under torch.autocast or with a half x, or use fused_mlp_func / {twin} for float32 arithmetic")
-    for name, t in named:
-        if t.dtype != torch.float32 and t.dtype != half:
-            raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype} but the half dtype of the call is {half} (every operand must be {half} or float32)")
-        if not grad and t.requires_grad and torch.is_grad_enabled():
-            raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use fused_mlp_func_amp_grad)")
-    if weight1.dim() != 2 or weight2.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight1.shape[1] or weight2.shape[1] != weight1.shape[0]:
-        raise SdvarError(f"{who}: shapes do not chain: x {tuple(x.shape)}, weight1 {tuple(weight1.shape)}, weight2 {tuple(weight2.shape)}")
-    Cin, hid, Cout = weight1.shape[1], weight1.shape[0], weight2.shape[0]
-    if Cin % 32 or hid % 32:
-        raise SdvarError(f"{who}: in_features {Cin} and hidden_features {hid} must be multiples of 32")
-    if Cout % 8:
-        raise SdvarError(f"{who}: out_features {Cout} must be a multiple of 8")
-    for name, b, n in (("bias1", bias1, hid), ("bias2", bias2, Cout)):
-        if b is not None and tuple(b.shape) != (n,):
-            raise SdvarError(f"{who}: {name} has shape {tuple(b.shape)}, expected ({n},)")
-    if any(t.device != x.device for _, t in named):
-        raise SdvarError(f"{who}: operands live on different devices")
-    return half, Cin, hid, Cout
-
-
-def _dense16(t: torch.Tensor) -> torch.Tensor:
-    """t itself when it is dense and 16-byte aligned, else one fresh dense copy (.contiguous() would hand back a dense tensor at a misaligned address)."""
-    return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
 def _in_code(t: torch.Tensor) -> int:
@@ -927,7 +808,7 @@ def fused_mlp_func_amp(x, weight1, weight2, bias1=None, bias2=None, activation: 
     y = half(fp32acc(h W2_h^T) + b2); nothing is clamped, an fp16 overflow is +-inf.  Two launches of sdvar_op_gemm_h (one fp16 / bf16 MFMA per product where mode f16x2
     issues three); weight operands are cached per (weight, dtype) and replaced when the weight is updated in place.  C and hidden must be multiples of 32, out of 8.
     Returns (..., out) in the half dtype.  Deterministic.  save_pre_act / checkpoint_lvl / heuristic are accepted and ignored."""
-    half, _, _, _ = _mlp_amp_check("fused_mlp_func_amp", x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, False)
+    half, _, _, _ = _mlp_check("fused_mlp_func_amp", x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, True, False)
     return _mlp_amp_forward(x, weight1, weight2, bias1, bias2, half, False)[0]
 
 
@@ -1010,7 +891,7 @@ def fused_mlp_func_amp_grad(x, weight1, weight2, bias1=None, bias2=None, activat
     is not dense or not 16-byte aligned is copied once.  Deterministic; only the gradients autograd asks for are computed, and each has the bits it has in the full
     run.  Nothing is clamped: an fp16 overflow is +-inf and reaches the GradScaler.  No double backward."""
     who = "fused_mlp_func_amp_grad"
-    half, Cin, hid, Cout = _mlp_amp_check(who, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, True)
+    half, Cin, hid, Cout = _mlp_check(who, x, weight1, weight2, bias1, bias2, activation, return_residual, process_group, True, True)
     tensors = [t for t in (x, weight1, weight2, bias1, bias2) if t is not None]
     if not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors):
         return _mlp_amp_forward(x, weight1, weight2, bias1, bias2, half, False)[0]            # what the inference twin launches: the same bits
@@ -1132,6 +1013,14 @@ def _set_ffn_slots(module, model, slot) -> None:
                 m.fused_mlp_func = slot
 
 
+def _set_using_flash(model) -> None:
+    """`using_flash = True` on every submodule of a model that has the attribute (the reference decides it at construction, basic_var.py:81)."""
+    if model is not None:
+        for m in model.modules():
+            if hasattr(m, "using_flash"):
+                m.using_flash = True
+
+
 def install(module, model=None) -> None:
     """Set the `slow_attn` and `fused_mlp_func` globals of a basic_var-like module; with a model, also every `ffn.fused_mlp_func` its FFN modules captured at
     construction (basic_var.py:36).  `memory_efficient_attention` is left alone: setting it would not switch an existing model to it (using_xform is decided at
@@ -1145,10 +1034,7 @@ def enable_flash(module, model=None) -> None:
     (the reference decides that flag at construction, basic_var.py:81, from whether flash-attn could be imported).  Separate from install(): the slot only serves
     half-precision operands, i.e. a model run under torch.autocast."""
     module.flash_attn_func = flash_attn_func
-    if model is not None:
-        for m in model.modules():
-            if hasattr(m, "using_flash"):
-                m.using_flash = True
+    _set_using_flash(model)
 
 
 def install_amp(module, model=None, ffn_half: bool = False) -> None:
@@ -1209,10 +1095,7 @@ def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm
         slot = fused_mlp_func_grad if ffn else None
     module.slow_attn = slow_attn_amp_grad
     module.flash_attn_func = flash_attn_func_grad
-    if model is not None:
-        for m in model.modules():
-            if hasattr(m, "using_flash"):
-                m.using_flash = True
+    _set_using_flash(model)
     _set_ffn_slots(module, model, slot)
 
 

@@ -219,3 +219,33 @@ def test_slot_call_as_the_reference_makes_it(dev, mask680):
     ref = _ref(qc, kc, vc, s, m[:, :, :L, :L]).transpose(1, 2).reshape(B, L, C_)
     err = (oup.cpu().double() - ref).abs().max().item()
     assert err <= 2e-5 * max(1.0, ref.abs().max().item()), err
+
+
+# ------------------------------------------------------------------------------------------------------------------ the copy-once rule
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_dense_fp32_operand_at_a_misaligned_address_is_copied_once(dev, which):
+    """A dense fp32 q / k / v one element into a flat buffer (address % 16 == 4) meets the stride rule and misses the address rule: it is copied once, and the
+    output and all three gradients have the bits of the run on aligned copies.  70 keys: one full 64-key tile and a partial one."""
+    g = torch.Generator().manual_seed(40)
+    keep = torch.rand(1, 1, 70, 70, generator=g) < 0.5
+    keep[..., 0] = True
+    md = keep.to(dev)
+    aligned = [rnd(41 + i, (1, 2, 70, 64)).to(dev) for i in range(3)]
+    dout = rnd(44, (1, 2, 70, 64)).to(dev)
+    n = aligned[which].numel()
+    flat = torch.zeros(n + 4, device=dev)
+    odd = flat[1:1 + n].view(1, 2, 70, 64)
+    odd.copy_(aligned[which])
+    assert odd.is_contiguous() and odd.data_ptr() % 16 == 4 and all(t.data_ptr() % 16 == 0 for t in aligned)
+    operands = [odd if i == which else t for i, t in enumerate(aligned)]
+    with torch.no_grad():
+        assert torch.equal(seam.slow_attn(*operands, 0.125, attn_mask=md), seam.slow_attn(*aligned, 0.125, attn_mask=md))
+    runs = []
+    for ops in (operands, aligned):
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_() for t in ops]
+            assert leaves[which].data_ptr() == ops[which].data_ptr()
+            out = seam.slow_attn_grad(*leaves, 0.125, attn_mask=md)
+            runs.append((out.detach(),) + torch.autograd.grad(out, leaves, dout))
+    for a, b in zip(*runs):
+        assert torch.isfinite(a).all() and torch.equal(a, b)

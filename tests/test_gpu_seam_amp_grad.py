@@ -366,7 +366,7 @@ def test_wrong_dout_dtype_raises(dev, dtype):
     ts = [rnd(370 + i, (1, 16, 2, 64)).to(dtype).to(dev).requires_grad_() for i in range(3)]
     out = seam.memory_efficient_attention_amp_grad(*ts)                      # BLHc: the function's own output, so out.grad_fn is its context
     with pytest.raises(E.SdvarError, match="memory_efficient_attention_amp_grad.*gradient of the output"):
-        seam._SdpaAmpGrad.backward(out.grad_fn, torch.zeros(1, 16, 2, 64, device=dev))
+        seam._SdpaFn.backward(out.grad_fn, torch.zeros(1, 16, 2, 64, device=dev))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the C entries

@@ -195,9 +195,9 @@ def test_flash_grad_operands():
 
 @pytest.mark.parametrize("half", HALVES)
 def test_wrong_dout_dtype_raises(half):
-    ctx = types.SimpleNamespace(sdpa=((0, 1, 2), 1.0, 0, None, (1, 2, 8, 8), half, "slow_attn_amp_grad"), needs_input_grad=(True,) * 3 + (False,) * 4)
+    ctx = types.SimpleNamespace(sdpa=((0, 1, 2), 1.0, 0, None, (1, 2, 8, 8), half, "slow_attn_amp_grad"), needs_input_grad=(True,) * 3 + (False,) * 5)
     with pytest.raises(E.SdvarError, match=f"^slow_attn_amp_grad: the gradient of the output is torch.float32 but the output is {half}"):
-        seam._SdpaAmpGrad.backward(ctx, torch.zeros(1, 8, 2, 64))
+        seam._SdpaFn.backward(ctx, torch.zeros(1, 8, 2, 64))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the existing slots keep refusing grad
