@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd, and after them sdvar_xent_train_fwd and sdvar_xent_train_bwd, and the six sdvar_op_adaln_* / sdvar_op_gate_add_* entry points; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
+#define SDVAR_ABI_VERSION 5      /* 5: sdvar_debug_plan_gemm (the GEMM planner, callable without a GPU), and, added later WITHOUT a bump (purely additive), sdvar_op_sdpa_lse, sdvar_op_sdpa_bwd, sdvar_op_sdpa_hm_lse and sdvar_op_sdpa_h_bwd, and after them sdvar_xent_train_fwd and sdvar_xent_train_bwd, and the six sdvar_op_adaln_* / sdvar_op_gate_add_* entry points, the three sdvar_op_qknorm_* ones, and sdvar_optim_grad_stats and sdvar_optim_adamw_step; 4 (round 4): sdvar_cfg_combine, sdvar_op_gemm_rowblk, sdvar_debug_set_rowblk; 3 (round 3): the f16-plane KV-cache formats 3 / 4 store V row-major like K; new debug entry points (guard, gemm cfg getter) */
 #define SDVAR_MAX_STAGES 16
 
 typedef struct sdvar_model sdvar_model_t;   /* one VAR transformer: weights (borrowed), KV cache, workspaces */
@@ -602,6 +602,44 @@ int64_t sdvar_op_qknorm_bwd_ws_bytes(int32_t B, int32_t L, int32_t H);
 int sdvar_op_qknorm_bwd(const void* qkv, int32_t dtype, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
                         const int64_t* grad_strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws /*workspace*/, int32_t B, int32_t L, int32_t H,
                         void* stream);
+
+/* ---- the optimizer step of the reference's trainer (AmpOptimizer.backward_clip_step, utils/amp_sc.py:39-75: unscale_, clip_grad_norm_, AdamW.step) -------------------
+ * csrc/optim.hip; sdvar_amd/seam.py AdamW.  Added without an ABI bump (purely additive).  Two calls over a HOST list of n tensor descriptors: float32 param, grad,
+ * exp_avg, exp_avg_sq (device, 4-byte aligned, numel elements each, dense), the tensor's float32 `step` counter (device) and its lr and weight_decay.  The descriptors
+ * are copied into the kernel arguments of each launch (SDVAR_OPTIM_TENSORS_PER_LAUNCH per launch, as many launches as needed): the list may be freed or rewritten as soon
+ * as a call returns, and calls enqueued back to back never share descriptor memory.  A workgroup handles one chunk of SDVAR_OPTIM_CHUNK elements of one tensor.
+ * ws (device, 8-byte aligned): 16 + 8 n + 8 sum_t ceil(numel_t / SDVAR_OPTIM_CHUNK) bytes = {record: 4 floats; 2 floats per tensor; one double per workgroup}; hand the
+ * SAME ws and list to both calls.  record = {norm, coef, skip, gscale}.  Argument errors (NULL list, n < 1, a NULL or misaligned pointer in a descriptor, numel < 0,
+ * beta outside [0, 1), a negative or NaN eps / lr / weight_decay, a NaN max_norm, a ws that is too small) are reported before any GPU call.  No allocation, no host
+ * synchronisation, no atomics: repeats are bit-identical.  The gradients are only read. */
+#define SDVAR_OPTIM_CHUNK 32768
+#define SDVAR_OPTIM_TENSORS_PER_LAUNCH 48
+typedef struct sdvar_optim_tensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* step;
+    int64_t numel;
+    double lr;
+    double weight_decay;
+} sdvar_optim_tensor_t;
+/* Pass 1 (reads the gradients once): S = sum of g^2 over all tensors, each square and every sum in float64 (a float32 square is exact there and the sum can neither
+ * overflow nor underflow: S is non-finite exactly when an element is) - per lane, six wave levels, the four waves of a workgroup in order, then ONE workgroup adds the
+ * per-workgroup partials in a fixed order (thread t: partials t, t + 256, ...; then a fixed tree).  With inv_scale = float(1 / double(*grad_scale)) (grad_scale NULL: 1):
+ *     norm = float(sqrt(S) * inv_scale);   coef = max_norm <= 0 ? 1 : min(1, float(max_norm) / (norm + 1e-6f))       (clip_grad_norm_'s definition, float32)
+ *     skip = 1 when norm is not finite or *found_inf > 0 (found_inf may be NULL), else 0;   gscale = inv_scale * coef
+ * The same finalising launches advance every tensor's step by 1 - skip (a skipped step keeps its bits; numel == 0: untouched) and leave per tensor, computed in float64
+ * from the advanced step: float(lr / (1 - beta1^step)) and float(sqrt(1 - beta2^step)). */
+int sdvar_optim_grad_stats(const sdvar_optim_tensor_t* tensors /*host*/, int32_t n, const float* grad_scale, const float* found_inf, double max_norm, double beta1,
+                           double beta2, void* ws, uint64_t ws_bytes, void* stream);
+/* Pass 2, after pass 1 on the same stream with the same list and ws: torch's decoupled AdamW (no amsgrad, no maximize) with one read of g, p, m, v and one write of p, m, v,
+ * 16-byte accesses where all four pointers of a tensor are 16-byte aligned (scalar otherwise, and for the numel % 4 tail).  Each line is one float32 operation, in this
+ * order (-ffp-contract=off), with ss and rb the two per-tensor floats of pass 1:
+ *     g' = g * gscale;   p1 = p * float(1 - lr * weight_decay);   m' = float(beta1) * m + float(1 - beta1) * g';   v' = float(beta2) * v + (float(1 - beta2) * g') * g'
+ *     p' = p1 - ss * (m' / (sqrt(v') / rb + float(eps)))                  (division and square root correctly rounded)
+ * record.skip != 0: nothing is written, p, m and v keep their bits. */
+int sdvar_optim_adamw_step(const sdvar_optim_tensor_t* tensors /*host*/, int32_t n, double beta1, double beta2, double eps, void* ws, uint64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

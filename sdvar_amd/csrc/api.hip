@@ -57,6 +57,9 @@ int qknorm_fwd(const void* qkv, int dt, const float* q_bias, const float* v_bias
 int qknorm_bwd(const void* qkv, int dt, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
                const long long* strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws, int B, int L, int H, hipStream_t stream);
 long long qknorm_bwd_ws_bytes(int B, int L, int H);
+int optim_grad_stats(const sdvar_optim_tensor_t* ts, int n, const float* grad_scale, const float* found_inf, double max_norm, double beta1, double beta2, void* ws,
+                     unsigned long long ws_bytes, hipStream_t stream);
+int optim_adamw_step(const sdvar_optim_tensor_t* ts, int n, double beta1, double beta2, double eps, void* ws, unsigned long long ws_bytes, hipStream_t stream);
 int attention_f32(const float* q, const void* kc, const void* vc, int kv_f16, float* out, uint16_t* outp, size_t ops, int pfmt, int R, int H, int l, int Lmax, int Ktot, int n_chunk, const int* qbeg, const int* vis, hipStream_t stream);
 int gemm_bf16x3_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                    int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
@@ -584,6 +587,15 @@ int64_t sdvar_op_qknorm_bwd_ws_bytes(int32_t B, int32_t L, int32_t H) { return q
 int sdvar_op_qknorm_bwd(const void* qkv, int32_t dtype, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
                         const int64_t* grad_strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws, int32_t B, int32_t L, int32_t H, void* stream) {
     return qknorm_bwd(qkv, dtype, q_bias, scale_log, max_log, dq, dk, dv, (const long long*)grad_strides, dqkv, dscale_log, dq_bias, dv_bias, ws, B, L, H, (hipStream_t)stream);
+}
+
+// the trainer's optimizer step (utils/amp_sc.py:39-75; sdvar_amd/seam.py AdamW): csrc/optim.hip
+int sdvar_optim_grad_stats(const sdvar_optim_tensor_t* tensors, int32_t n, const float* grad_scale, const float* found_inf, double max_norm, double beta1, double beta2,
+                           void* ws, uint64_t ws_bytes, void* stream) {
+    return optim_grad_stats(tensors, n, grad_scale, found_inf, max_norm, beta1, beta2, ws, ws_bytes, (hipStream_t)stream);
+}
+int sdvar_optim_adamw_step(const sdvar_optim_tensor_t* tensors, int32_t n, double beta1, double beta2, double eps, void* ws, uint64_t ws_bytes, void* stream) {
+    return optim_adamw_step(tensors, n, beta1, beta2, eps, ws, ws_bytes, (hipStream_t)stream);
 }
 
 static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream);

@@ -150,6 +150,8 @@ _SIGNATURES = {
     "sdvar_op_qknorm_fwd": (_I, [_P, _I, _P, _P, _P, _D, _P, _P, _P, _I, _I, _I, _P]),
     "sdvar_op_qknorm_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
     "sdvar_op_qknorm_bwd": (_I, [_P, _I, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sdvar_optim_grad_stats": (_I, [_P, _I, _P, _P, _D, _D, _D, _P, _U64, _P]),
+    "sdvar_optim_adamw_step": (_I, [_P, _I, _D, _D, _D, _P, _U64, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
     "sdvar_debug_set_gemm_stamps": (_I, [_P]),
     "sdvar_debug_set_qkv_fuse": (_I, [_I]),
@@ -763,6 +765,41 @@ def xent_train_bwd(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Tenso
         _check(lib.sdvar_xent_train_bwd(C.c_void_p(logits.data_ptr()), ld, _ptr(targets), _ptr(lse), _ptr(grad), XENT_REDUCTIONS.index(reduction),
                                         _ptr(sums) if reduction == "mean" else None, rows, V, eps, int(ignore_index), _ptr(dlogits), int(nt), _stream()))
     return dlogits
+
+
+OPTIM_CHUNK = 32768                    # SDVAR_OPTIM_CHUNK: elements of one tensor per workgroup of csrc/optim.hip
+OPTIM_TENSORS_PER_LAUNCH = 48          # SDVAR_OPTIM_TENSORS_PER_LAUNCH: descriptors carried in the arguments of one launch
+
+
+class _OptimTensor(C.Structure):
+    """sdvar_optim_tensor_t"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("numel", C.c_int64),
+                ("lr", C.c_double), ("weight_decay", C.c_double)]
+
+
+def optim_table(rows):
+    """rows: (param, grad, exp_avg, exp_avg_sq, step addresses, numel, lr, weight_decay) per tensor -> the host array both optim calls take.  Built afresh for every
+    step (gradient addresses change); the library copies what it needs into each launch, so the array may be dropped as soon as the calls return."""
+    return (_OptimTensor * len(rows))(*rows)
+
+
+def optim_ws_bytes(numels) -> int:
+    """Bytes of the workspace of the two optim calls for tensors of these sizes: a 4-float record, 2 floats per tensor, one double per chunk."""
+    return 16 + 8 * len(numels) + 8 * sum((int(n) + OPTIM_CHUNK - 1) // OPTIM_CHUNK for n in numels)
+
+
+def optim_grad_stats(table, grad_scale: Optional[torch.Tensor], found_inf: Optional[torch.Tensor], max_norm: float, beta1: float, beta2: float, ws: torch.Tensor) -> None:
+    """sdvar_optim_grad_stats on the current device and stream: fills ws (a uint8 / float32 device tensor of optim_ws_bytes) with the record {norm, coef, skip, gscale},
+    advances the step counters by 1 - skip and leaves the per-tensor bias corrections.  grad_scale / found_inf: one-element float32 device tensors or None."""
+    lib = load_library()
+    _check(lib.sdvar_optim_grad_stats(table, len(table), _ptr(grad_scale), _ptr(found_inf), float(max_norm), float(beta1), float(beta2), _ptr(ws),
+                                      ws.numel() * ws.element_size(), _stream()))
+
+
+def optim_adamw_step(table, beta1: float, beta2: float, eps: float, ws: torch.Tensor) -> None:
+    """sdvar_optim_adamw_step on the current device and stream, after optim_grad_stats with the same table and ws: one read of g, p, m, v and one write of p, m, v."""
+    lib = load_library()
+    _check(lib.sdvar_optim_adamw_step(table, len(table), float(beta1), float(beta2), float(eps), _ptr(ws), ws.numel() * ws.element_size(), _stream()))
 
 
 TRAIN_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}          # dtype codes of csrc/adaln_train.hip

@@ -28,6 +28,8 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install_train_amp(basic_var, model, ffn="half", adaln=True, qknorm=True)    # the same under autocast; seam.install_qknorm(model) alone for inference,
                                                                                      # seam.uninstall_qknorm(model) takes the bound forwards off again
 
+    seam.install_optimizer(var_opt)         # the AmpOptimizer's AdamW (utils/amp_sc.py): unscale + clip_grad_norm_ + AdamW.step as two passes on HIP (seam.AdamW)
+
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
 slow_attn_amp_grad / memory_efficient_attention_amp_grad / flash_attn_func_grad (the half and mixed operands of autocast; backward = sdvar_op_sdpa_h_bwd) and
 fused_mlp_func_grad (fp32 operands; backward = four GEMMs on operands from csrc/mlp_bwd.hip, no double backward) and fused_mlp_func_amp_grad (autocast's half dtype;
@@ -45,6 +47,9 @@ scale is widened to float32 before the + 1, where torch's scale.add(1) rounds th
 qk_l2norm is what SelfAttention.forward does between the QKV GEMM and the attention call when attn_l2_norm is on (basic_var.py:93-105): bias add, per-head L2
 normalisation of q and k and the learnt per-head scale of q, one kernel per direction (csrc/qknorm_train.hip: sdvar_op_qknorm_fwd / _bwd; qkv, the biases and the scale
 parameter saved; no double backward).  The float32 master bias is added in float32 to the GEMM's output, where autocast rounds acc + half(bias) to half inside the GEMM.
+AdamW / install_optimizer are the optimizer step outside the blocks (utils/amp_sc.py:39-75, train.py:118): torch's decoupled AdamW on float32 parameters with the
+GradScaler's unscale, clip_grad_norm_'s global norm and the non-finite skip folded into two passes over the tensors (csrc/optim.hip: sdvar_optim_grad_stats,
+sdvar_optim_adamw_step); the norm stays on the device as `global_grad_norm`, the reference's late-clipping slot.  The gradients are read, never modified.
 
 Operand rule of the attention slots: every token row 16-byte aligned (data_ptr % 16 == 0, every stride a multiple of 4 elements, last stride 1).  The
 reference's permuted views of one (B, L, 3, H, 64) buffer, its (B, H, L, 64) caches and xformers' (B, L, H, 64) tensors all meet it and are
@@ -70,7 +75,7 @@ __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_f
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
            "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
            "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad", "adaln_modulate", "gated_residual",
-           "uninstall_adaln", "qk_l2norm", "install_qknorm", "uninstall_qknorm"]
+           "uninstall_adaln", "qk_l2norm", "install_qknorm", "uninstall_qknorm", "AdamW", "install_optimizer"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -1002,6 +1007,180 @@ def install_trainer(trainer) -> None:
                          "with seam.CrossEntropyLoss")
     trainer.train_loss = CrossEntropyLoss(label_smoothing=trainer.label_smooth, reduction="none")
     trainer.val_loss = CrossEntropyLoss(label_smoothing=0.0, reduction="mean")
+
+
+# ------------------------------------------------------------------------------------------------------- the optimizer step (csrc/optim.hip)
+_OPT_IGNORED = {"fused": None, "foreach": None, "capturable": False, "differentiable": False}          # torch's keywords that select an implementation: accepted, kept in the groups, unused
+
+
+class AdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW's update (decoupled weight decay, no amsgrad, no maximize) with GradScaler's unscale and clip_grad_norm_ folded in, as two passes over the
+    gradients and the state (csrc/optim.hip: sdvar_optim_grad_stats, sdvar_optim_adamw_step) - what the reference's AmpOptimizer.backward_clip_step (utils/amp_sc.py:39-75)
+    issues as unscale_, clip_grad_norm_ and AdamW.step.  It can stand in as the `opt_clz` of train.py:118: torch's `fused`, `foreach`, `capturable` and `differentiable`
+    keywords are accepted and ignored; amsgrad=True or maximize=True raise SdvarError.
+    step(): pass 1 reads every gradient once and leaves on the device norm = |g|_2 * inv_scale (float64 sums in a fixed order), coef = 1 when grad_clip <= 0, else
+    min(1, grad_clip / (norm + 1e-6)) (clip_grad_norm_'s definition), and skip = 1 when a gradient element or the norm is not finite or `found_inf` > 0; pass 2 applies
+        g' = g * (inv_scale * coef);  p <- p (1 - lr wd);  m <- b1 m + (1 - b1) g';  v <- b2 v + (1 - b2) g'^2;  p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+    with one read of g, p, m, v and one write of p, m, v.  On a skipped step nothing is written: p, m, v and every `step` keep their bits.  THE GRADIENTS ARE NEVER
+    MODIFIED: after torch's clip_grad_norm_ `.grad` holds the clipped values, here it holds what backward() left (the reference drops the gradients on the next line).
+    `grad_scale` and `found_inf`, the attributes GradScaler.step sets on an optimizer with _step_supports_amp_scaling, are honoured as torch's fused AdamW honours them:
+    inv_scale = 1 / grad_scale, or 1 when it is None (the caller already ran unscale_: the reference's flow).  After every step() `global_grad_norm` is a 0-dim float32
+    device tensor, the norm of the UNSCALED gradients before clipping (non-finite if they were) - the attribute that switches the reference's AmpOptimizer to late
+    clipping (amp_sc.py:34-35, 70-71) - and `stats_record` the float32 device tensor {norm, coef, skip, inv_scale * coef}; both are set without a host synchronisation.
+    The `_version` of every parameter and state tensor handed to the kernels moves at each step(), a skipped one included (the host does not know), as after torch's
+    in-place update: fused_mlp_func's cached weight planes are rebuilt and autograd refuses a stale saved tensor.
+    float32 parameters, gradients and state on ONE GPU only; parameters must be contiguous; a non-contiguous gradient is copied once; parameters without a gradient and
+    zero-element parameters are skipped.  Everything else raises SdvarError naming the parameter's index (its position over all groups): there is no fall-back to torch.
+    betas and eps must be the same in every group (lr and weight_decay are per group).  These checks happen in step(): the object is built, saved and loaded without a
+    GPU.  State keys are torch's (`step`: 0-dim float32 device tensor, `exp_avg`, `exp_avg_sq`): a state_dict() loads into torch.optim.AdamW and back; `step` counters a
+    non-fused torch checkpoint keeps on the CPU are moved to the device at the next step().  step() launches on the current stream, never synchronises with the host
+    (no .item(), no get_scale()) and takes no closure."""
+
+    _step_supports_amp_scaling = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_clip: float = 0.0, amsgrad: bool = False, maximize: bool = False,
+                 **torch_kwargs):
+        who = "seam.AdamW"
+        if amsgrad or maximize:
+            raise SdvarError(f"{who}: amsgrad={amsgrad}, maximize={maximize}: neither is supported (the kernel is plain decoupled AdamW); pass False")
+        unknown = sorted(set(torch_kwargs) - set(_OPT_IGNORED))
+        if unknown:
+            raise SdvarError(f"{who}: unknown keyword(s) {unknown}; beside torch.optim.AdamW's own arguments only grad_clip is taken")
+        if not (isinstance(betas, (tuple, list)) and len(betas) == 2 and all(0.0 <= float(b) < 1.0 for b in betas)):
+            raise SdvarError(f"{who}: betas={betas!r} must be two numbers in [0, 1)")
+        for name, val in (("lr", lr), ("eps", eps), ("weight_decay", weight_decay)):
+            if not float(val) >= 0.0:
+                raise SdvarError(f"{who}: {name}={val} must be >= 0")
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, **{**_OPT_IGNORED, **torch_kwargs})
+        super().__init__(params, defaults)
+        self.grad_clip = float(grad_clip)
+        self.global_grad_norm = None          # present from construction: AmpOptimizer looks for the attribute (amp_sc.py:34-35)
+        self.stats_record = None
+
+    def __getstate__(self):
+        return {**super().__getstate__(), "grad_clip": self.grad_clip}
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("grad_clip", 0.0)
+        self.global_grad_norm = self.stats_record = None
+
+    @staticmethod
+    def _state_of(who: str, idx: int, p, st: dict):
+        """The parameter's state in the form the kernels read: created on first use, a loaded checkpoint's tensors moved to the parameter's GPU as float32."""
+        if len(st) == 0:
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            return st
+        missing = [k for k in ("step", "exp_avg", "exp_avg_sq") if k not in st]
+        if missing:
+            raise SdvarError(f"{who}: the state of parameter {idx} has no {' / '.join(missing)} (not an Adam / AdamW state)")
+        s = st["step"]
+        if not isinstance(s, torch.Tensor):
+            st["step"] = torch.tensor(float(s), dtype=torch.float32, device=p.device)
+        elif s.device != p.device or s.dtype != torch.float32 or s.dim() != 0:
+            if s.numel() != 1:
+                raise SdvarError(f"{who}: the `step` of parameter {idx} has {s.numel()} elements, expected 1")
+            st["step"] = s.detach().to(device=p.device, dtype=torch.float32).reshape(())
+        for k in ("exp_avg", "exp_avg_sq"):
+            t = st[k]
+            if not isinstance(t, torch.Tensor) or t.numel() != p.numel():
+                raise SdvarError(f"{who}: `{k}` of parameter {idx} does not have the parameter's {p.numel()} elements")
+            if t.device != p.device or t.dtype != torch.float32 or not t.is_contiguous():
+                st[k] = t.detach().to(device=p.device, dtype=torch.float32).contiguous()
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        who = "seam.AdamW.step"
+        if closure is not None:
+            raise SdvarError(f"{who}: a closure is not supported; evaluate the loss and call backward() before step()")
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        rows, numels, keep, written = [], [], [], []
+        dev = betas = eps = None
+        idx = -1
+        for gi, group in enumerate(self.param_groups):
+            if group.get("amsgrad") or group.get("maximize"):
+                raise SdvarError(f"{who}: group {gi} has amsgrad={group.get('amsgrad')}, maximize={group.get('maximize')}: neither is supported")
+            gb, ge = (float(group["betas"][0]), float(group["betas"][1])), float(group["eps"])
+            if betas is None:
+                betas, eps = gb, ge
+            elif gb != betas or ge != eps:
+                raise SdvarError(f"{who}: group {gi} has betas={gb}, eps={ge} but group 0 has betas={betas}, eps={eps}: one pair of betas and one eps per optimizer "
+                                 f"(lr and weight_decay may differ)")
+            lr, wd = float(group["lr"]), float(group["weight_decay"])
+            for p in group["params"]:
+                idx += 1
+                g = p.grad
+                if g is None or p.numel() == 0:
+                    continue
+                if not p.is_cuda:
+                    raise SdvarError(f"{who}: parameter {idx} is on {p.device}; the kernels run on the GPU and there is no CPU path")
+                if p.dtype != torch.float32:
+                    raise SdvarError(f"{who}: parameter {idx} is {p.dtype}; only float32 parameters, gradients and state are supported")
+                if dev is None:
+                    dev = p.device
+                elif p.device != dev:
+                    raise SdvarError(f"{who}: parameter {idx} is on {p.device} but an earlier one is on {dev}: one optimizer per GPU")
+                if not p.is_contiguous():
+                    raise SdvarError(f"{who}: parameter {idx} with strides {tuple(p.stride())} is not contiguous (it is updated in place and cannot be copied)")
+                if g.is_sparse or g.layout != torch.strided:
+                    raise SdvarError(f"{who}: the gradient of parameter {idx} is sparse ({g.layout}); dense gradients only")
+                if g.dtype != torch.float32 or g.device != dev:
+                    raise SdvarError(f"{who}: the gradient of parameter {idx} is {g.dtype} on {g.device}, expected float32 on {dev}")
+                if not g.is_contiguous():
+                    g = g.contiguous()          # copied once; the copy lives until the launches are enqueued (the caching allocator reuses it in stream order)
+                    keep.append(g)
+                st = self._state_of(who, idx, p, self.state[p])
+                rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(), p.numel(), lr, wd))
+                numels.append(p.numel())
+                written.extend((p, st["exp_avg"], st["exp_avg_sq"], st["step"]))
+        if not rows:
+            self.stats_record = torch.tensor([0.0, 1.0, 0.0, 1.0], dtype=torch.float32, device=dev)
+            self.global_grad_norm = self.stats_record[0]
+            return None
+        for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.numel() == 1):
+                raise SdvarError(f"{who}: {name} must be a one-element float32 tensor on {dev} (what GradScaler.step sets), got {t!r}")
+        table = E.optim_table(rows)
+        with E._on_device(dev):
+            ws = torch.empty(E.optim_ws_bytes(numels) // 4, dtype=torch.float32, device=dev)          # fresh every step: global_grad_norm stays valid after the next one
+            E.optim_grad_stats(table, grad_scale, found_inf, self.grad_clip, betas[0], betas[1], ws)
+            E.optim_adamw_step(table, betas[0], betas[1], eps, ws)
+        torch._C._increment_version(written)          # the kernels write through raw pointers: autograd's saved-tensor check and the seam's weight-plane cache go by _version
+        self.stats_record = ws[:4]
+        self.global_grad_norm = ws[0]
+        return None
+
+
+def install_optimizer(var_opt) -> None:
+    """Replace the torch.optim.AdamW (or Adam) of an AmpOptimizer-like object (utils/amp_sc.py:15-37) by a seam.AdamW over the same parameters: every param group entry
+    is carried over (the `lr_sc` / `wd_sc` keys lr_wd_annealing reads included) and every state tensor; grad_clip = var_opt.grad_clip; and the two flags are set to what
+    the reference's constructor computes for an optimizer that has `global_grad_norm`: early_clipping = False, late_clipping = grad_clip > 0 - backward_clip_step then
+    runs no clip_grad_norm_ of its own and reads the norm after the step.  Any other optimizer class, an amsgrad / maximize group, or a torch.optim.Adam whose weight
+    decay is the coupled L2 kind (weight_decay != 0 without decoupled_weight_decay) raises SdvarError: the kernel computes the decoupled form only.  The reference's code
+    is not edited."""
+    who = "install_optimizer"
+    old = getattr(var_opt, "optimizer", None)
+    if not isinstance(old, (torch.optim.AdamW, torch.optim.Adam)):
+        raise SdvarError(f"{who}: var_opt.optimizer is a {type(old).__name__}; only torch.optim.AdamW / Adam can be replaced by seam.AdamW")
+    if not hasattr(var_opt, "grad_clip"):
+        raise SdvarError(f"{who}: the object has no `grad_clip` attribute (an AmpOptimizer sets it at amp_sc.py:33)")
+    groups = []
+    for gi, group in enumerate(old.param_groups):
+        if group.get("amsgrad") or group.get("maximize"):
+            raise SdvarError(f"{who}: group {gi} has amsgrad={group.get('amsgrad')}, maximize={group.get('maximize')}: neither is supported")
+        if not isinstance(old, torch.optim.AdamW) and not group.get("decoupled_weight_decay", False) and float(group["weight_decay"]) != 0.0:
+            raise SdvarError(f"{who}: group {gi} of a torch.optim.Adam has weight_decay={group['weight_decay']} as an L2 term in the gradient; seam.AdamW decays the "
+                             f"weights directly (use AdamW, decoupled_weight_decay=True or weight_decay=0)")
+        groups.append(dict(group))
+    new = AdamW(groups, grad_clip=float(var_opt.grad_clip))
+    for p, st in old.state.items():
+        new.state[p] = dict(st)
+    var_opt.optimizer = new
+    var_opt.early_clipping = False
+    var_opt.late_clipping = float(var_opt.grad_clip) > 0
 
 
 def _set_ffn_slots(module, model, slot) -> None:
