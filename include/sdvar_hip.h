@@ -428,7 +428,8 @@ int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const 
                          int32_t M, int32_t N, int32_t K, int32_t epilogue, const float* res, int32_t ldres, const float* gate, int32_t rows_per_gate, int32_t gate_stride,
                          const float* scale_mul, float* q_out, void* k_cache, void* v_cache, int32_t l, int32_t H, int32_t Lp, int32_t pos0, int32_t kv_fmt, void* stream);
 /* Select a kernel variant that otherwise only an environment variable (read at first use) selects - tests run the non-default variants in one process.
- * name: "gemm_h4_var" 0..3, "gemm_h2_stages" 2..6, "gemm_small_pp" 0..2, "attn_pp_sched" 0..3, "conv_pp" 0..2; value < 0 restores the environment / default.
+ * name: "gemm_h4_var" 0..3, "gemm_h2_stages" 2..6, "gemm_small_pp" 0..2, "attn_pp_sched" 0..3, "conv_pp" 0..2, "conv_tap_reuse" 0..1 (SDVAR_CONV_TAP_REUSE, read per call like
+ * SDVAR_CONV_PP: 1 = the f16x2 decoder convolution stages X once per row of taps where the shape allows it, 0 = never); value < 0 restores the environment / default.
  * A lookup in the library's one table of process-wide switches (csrc/gemm_plan.h), which sdvar_debug_set_rowblk ("rowblk" 0..2), sdvar_debug_set_qkv_fuse
  * ("qkv_fuse" 0..1) and sdvar_debug_set_gemm_cfg write too; "gemm_v2" 0..1 (bf16x3: the 128-row tile on the LDS-DMA kernel, default 1) has no other setter. */
 int sdvar_debug_set_variant(const char* name, int32_t value);
@@ -436,6 +437,9 @@ int sdvar_debug_set_variant(const char* name, int32_t value);
  * split since the last read, number of QKV launches that finished q and k in their epilogue since the last read}; reading resets the two counters.
  * Tests assert with it that the path they mean to cover is the one that ran. */
 int sdvar_debug_get_gemm_cfg(int32_t* out4);
+/* test aid: out1[0] = 1 if the LAST convolution launch (sdvar_op_conv_planes / _ex, the decoder's convolutions) of this host thread took the tap-reuse K loop
+ * (f16x2 planes, "conv_pp" 2, "conv_tap_reuse" 1, 3x3 or fused up-sampling taps, no split-K, H W % 256 == 0, W % 256 == 0 or 256 % W == 0 with W >= 64), else 0. */
+int sdvar_debug_get_conv_cfg(int32_t* out1);
 /* The GEMM planner (csrc/gemm_plan.h) on its own: what a GEMM of this shape would launch.  Pure host code - no HIP call, no GPU needed; a pure function of the
  * arguments, the switches above and the SDVAR_GEMM_* environment.  mode: 0 f32, 1 bf16x3, 2 f16x2.  flags: bit 0 = the caller defers the K-slice sum to its
  * consumer kernel, bit 1 = the call offers a QKV finish for the epilogue (sdvar_stage_forward's QKV launch), bit 2 = every output pointer and leading dimension

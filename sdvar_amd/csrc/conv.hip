@@ -15,6 +15,7 @@
 // 32 rows x 160 columns (5 MFMA column tiles: one A fragment feeds 5 x 6 MFMAs), K-step 32, 2-stage LDS-DMA ring of
 // 78 KB, XOR-swizzled 64-byte rows (conflict-free ds_read_b128), hand-placed fragment reads with counted lgkmcnt, the
 // DMA instructions of the next K-step spread between the MFMA groups (as gemm_bf16x3_v3_kernel).
+// conv_f16x2_reuse_kernel (f16x2 planes, the decoder's 64^2 .. 256^2 levels): the X rows are staged once per row of taps instead of once per tap.
 #include <stdlib.h>
 
 #include "common.h"
@@ -51,7 +52,8 @@ struct ConvArgs {
     double* gn_part; int cpg;                      // optional GroupNorm partial sums of the OUTPUT: [M/256][32 groups][sum, sumsq], cpg = N / 32
     int up_phase;                                  // >= 0: fused nearest-2x up-sampling (taps = 4): blockIdx.y = output phase (py, px) = (y >> 1, y & 1)
     size_t w_phase_stride;                         //       weight planes of phase p at W + p * w_phase_stride
-    int dbg;                                       // timing experiments (SDVAR_CONV_DBG, results wrong): bit 0 = no epilogue, bit 1 = no GroupNorm statistics, bit 2 = no output stores
+    int dbg;                                       // timing experiments (SDVAR_CONV_DBG, results wrong): bit 0 = no epilogue, bit 1 = no GroupNorm statistics, bit 2 = no output stores,
+                                                   // bit 3 = conv_f16x2_kernel<EPI, 2> skips the X DMA of every tap that is not the first of its row of taps (the stage keeps stale data)
 };
 
 // per group of the tile: the fp32 column sums around the column pivots (red, piv) -> {sum, M2} in fp64, the columns merged as in vae.hip gn_partial_kernel
@@ -385,7 +387,9 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
     const char* ux = nullptr; const char* uw = nullptr;
     const int tw = (a.taps == 9) ? 3 : 2;
     int sc = kt0 % a.cb, stap = kt0 / a.cb, sty = stap / tw, stx = stap - sty * tw, skb = kt0;
+    bool skx = false;                              // SDVAR_CONV_DBG bit 3: the step set up last issues no X DMA
     auto set_next = [&]() {
+        if (PP == 2 && SDVAR_CDBG(a, 8)) skx = stx != 0;
         const int shift = (a.taps == 9) ? (sty - 1) * w2 + (stx - 1) : (a.taps == 4) ? (sty - 1 + (phase >> 1)) * w2 + (stx - 1 + (phase & 1)) : 0;
         ux = reinterpret_cast<const char*>(a.X) + ((long long)sc * (long long)a.x_rows + shift) * 64;
         uw = reinterpret_cast<const char*>(Wp) + (size_t)skb * a.N * 64;
@@ -396,6 +400,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
     auto issue_one = [&](uint16_t* st, int q) {
         if (q < 6) {
             const int p = q / 3, kind = q % 3;
+            if (kind < 2 && skx) return;
             if (kind == 0) SDVAR_DMA16(lx0, ux + p * a.xps * 2, SDVAR_LDS_ADDR(st + p * 8192 + swave * 1024));
             else if (kind == 1) SDVAR_DMA16(lx1, ux + p * a.xps * 2, SDVAR_LDS_ADDR(st + p * 8192 + swave * 1024 + 512));
             else SDVAR_DMA16(lw0, uw + p * a.wps * 2, SDVAR_LDS_ADDR(st + 2 * 8192 + p * 5120 + swave * 512));
@@ -430,7 +435,8 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
         const int late = __builtin_amdgcn_readfirstlane(wave >> 2);
         const int l15 = lane & 15, lq = lane >> 4;
         auto wait_next = [&](int t) {
-            if (t + 2 < nk) { if (two_w) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
+            if (t + 2 < nk && skx) { if (two_w) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }     // the newest step has W only
+            else if (t + 2 < nk) { if (two_w) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         };
 #define SDVAR_C_SLOT() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -601,6 +607,198 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
     conv_epilogue<EPI>(a, acc, a.wsi ? *a.wsi : 1.0f, m0, n0, tm, ks, phase, wave, li, lh, tid, csm);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Tap-reuse K loop for the f16x2 convolution: conv_f16x2_kernel<EPI, 2> with the X operand staged once per ROW of taps.  In the padded-pixel-row layout the
+// X rows of taps (dy, -1), (dy, 0), (dy, +1) of one channel block are the same rows shifted by one, so the K order becomes (dy, channel block, dx) and one X
+// stage - the contiguous padded rows [prow(m0) - 1, prow(m0 + 255) + 1] shifted by dy (W + 2), both planes - serves TW = 3 K-steps (TW = 2 for the 2 x 2 taps of
+// a fused up-sampling phase): X intake per K-step falls from 32 KB to 34 / TW KB, X + W from 52 to 31.3 (37.0) KB.  Tile, MFMA shape, plane-product order,
+// ping-pong halves and epilogue are those of conv_f16x2_kernel<EPI, 2>; the fp32 accumulation order differs (same contract, other rounding).
+// Host conditions (conv_planes): no split-K, H W % 256 == 0 and W % 256 == 0 or (256 % W == 0, W >= 64): a tile is part of one image row or 1 - 4 whole rows of
+// one image, and the staged span is (256 / W)(W + 2) <= 264 rows (258 inside one row).
+//   X ring: 2 stages [2 planes][272 rows][32] (69.6 KB); group g = (dy, c) lives in stage g & 1 for TW K-steps.  Row r of a stage is padded row
+//           prow(m0) - 1 + min(r, span - 1) (+ dy shift): the rows behind the span repeat its last row (inside the plane allocation, never read).
+//           17 DMA instructions of 16 rows per plane: wave w issues row groups w and w + 8 of both planes, waves 2 / 3 group 16 of plane 0 / 1.
+//   W ring: 4 stages [2 planes][160 rows][32] (81.9 KB); K-step t in stage t & 3, issued two K-steps ahead as before.
+//   A lane's fragment row for tap dx is prow(m) - prow(m0) + 1 + (dx shift); the XOR swizzle is keyed on that LDS row (the DMA writes row r's chunk
+//   c ^ ((r >> 2) & 3) at position c), so 16 consecutive rows at any offset still hit 16 different bank groups.
+// Slots (K-step t = TW g + dx; X(g + 1) = the X DMA of the next group, spread over the group's first TW - 1 steps; W(t + 2) = the W DMA two steps ahead):
+//     slot:       4t               4t+1             4t+2             4t+3
+//     waves 0-3:  L0(t) + X share  M0(t)            L1(t) + W(t+2)   M1(t), wait
+//     waves 4-7:  M1(t-1)          L0(t) + X share  M0(t)            L1(t) + W(t+2), wait
+//   L0(t) reads the 4 X fragments (stage g & 1, rows shifted by dx) and W tiles 0-4, L1(t) W tiles 5-9.  X share: TW = 3: dx = 0 row group w (+ group 16),
+//   dx = 1 row group w + 8, dx = 2 nothing; TW = 2: everything at dx = 0.
+//   Stage reuse: stage (g + 1) & 1 held group g - 1, whose last X reads are the late half's L0(TW g - 1) in slot 4 (TW g - 1) + 1; the first DMA into it is
+//   issued in slot 4 TW g, two barriers later.  W stage (t + 2) & 3 held K-step t - 2, last read in slot 4 (t - 2) + 3.
+//   Waits: everything a wave issued before K-step t must have landed at the end of K-step t (X shares are issued at least two K-steps before their first read,
+//   W exactly two), so the wait at the end of K-step t is vmcnt(number of DMA instructions this wave issued IN K-step t) - a per-wave, per-dx count.
+constexpr int CXR = 272;                              // rows of an X stage
+constexpr int CXSTAGE_R = 2 * CXR * 32;               // fp16 elements of an X stage (34816 bytes)
+constexpr int CWSTAGE_R = 2 * CBN * 32;               // of a W stage (20480 bytes)
+constexpr size_t CLDS_R = (2 * (size_t)CXSTAGE_R + 4 * (size_t)CWSTAGE_R) * sizeof(uint16_t);          // 151552 bytes
+
+__device__ __forceinline__ void conv_vm_wait(int n) {          // s_waitcnt vmcnt(n) for a wave-uniform n in [0, 9]
+    switch (n) {
+        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+}
+
+template <int EPI, int TW>
+__global__ __launch_bounds__(512, 2) void conv_f16x2_reuse_kernel(ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t csm[];
+    const int tiles_n = (a.N + CBN - 1) / CBN, ntile = (a.M / CBM) * tiles_n;
+    const int lid = xcd_remap(blockIdx.x, ntile);
+    const int tm = lid / tiles_n, tn = lid - tm * tiles_n;
+    const int m0 = tm * CBM, n0 = tn * CBN;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int phase = a.up_phase >= 0 ? (int)blockIdx.y : 0;
+    const uint16_t* Wp = a.W + (size_t)phase * a.w_phase_stride;
+    const int w2 = a.iw + 2;
+    auto prow = [&](int m) {
+        const int hw = a.ih * a.iw, b = m / hw, rem = m - b * hw, y = rem / a.iw, x = rem - y * a.iw;
+        return (b * (a.ih + 2) + y + 1) * w2 + x + 1;
+    };
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    const int late = __builtin_amdgcn_readfirstlane(wave >> 2);
+    const int l15 = lane & 15, lq = lane >> 4, r16 = lane >> 2;
+    const int p0 = prow(m0), span = prow(m0 + CBM - 1) - p0 + 3;          // padded rows [p0 - 1, p0 - 1 + span) are staged; span <= 264
+    // DMA lane offsets (bytes from the channel block's plane base + the dy shift): stage row r <- padded row p0 - 1 + min(r, span - 1)
+    auto xoff = [&](int grp) {
+        const int r = 16 * grp + r16, rr = min(r, span - 1), ch = (lane & 3) ^ ((r >> 2) & 3);
+        return (uint32_t)((a.x_row0 + p0 - 1 + rr) * 32 + 8 * ch) * 2u;
+    };
+    const uint32_t lxa = xoff(swave), lxb = xoff(swave + 8), lxc = xoff(16);
+    const int wr0 = 16 * wave + r16, wr1 = 128 + wr0;
+    const int cw0 = (lane & 3) ^ ((wr0 >> 2) & 3), cw1 = (lane & 3) ^ ((wr1 >> 2) & 3);
+    const uint32_t lw0 = (uint32_t)(min(n0 + wr0, a.N - 1) * 32 + 8 * cw0) * 2u, lw1 = (uint32_t)(min(n0 + wr1, a.N - 1) * 32 + 8 * cw1) * 2u;
+    const bool two_w = swave < 2, x17 = swave == 2 || swave == 3;
+    const int nw = two_w ? 4 : 2;                                         // DMA instructions of this wave per W block
+    const int ng = TW * a.cb, nk = TW * ng;                               // X groups (dy, c); K-steps
+
+    uint16_t* const wring = csm + 2 * CXSTAGE_R;
+    // X part 0: row group w of both planes (+ group 16 of one plane on waves 2, 3); part 1: row group w + 8 of both planes
+    int xy = 0, xc = 0;                                                   // the next X group to issue
+    auto issue_x = [&](uint16_t* xs, int part) {
+        const int shift = (TW == 3) ? (xy - 1) * w2 : (xy - 1 + (phase >> 1)) * w2;
+        const char* ux = reinterpret_cast<const char*>(a.X) + ((long long)xc * (long long)a.x_rows + shift) * 64;
+        if (part == 0) {
+            SDVAR_DMA16(lxa, ux, SDVAR_LDS_ADDR(xs + swave * 512));
+            SDVAR_DMA16(lxa, ux + a.xps * 2, SDVAR_LDS_ADDR(xs + CXR * 32 + swave * 512));
+            if (x17) SDVAR_DMA16(lxc, ux + (swave - 2) * a.xps * 2, SDVAR_LDS_ADDR(xs + (swave - 2) * CXR * 32 + 16 * 512));
+        } else {
+            SDVAR_DMA16(lxb, ux, SDVAR_LDS_ADDR(xs + (swave + 8) * 512));
+            SDVAR_DMA16(lxb, ux + a.xps * 2, SDVAR_LDS_ADDR(xs + CXR * 32 + (swave + 8) * 512));
+        }
+    };
+    auto x_adv = [&]() { if (++xc == a.cb) { xc = 0; ++xy; } };
+    const int nx0 = x17 ? 3 : 2;                                          // DMA instructions of part 0 (part 1: 2)
+    int wy = 0, wc = 0, wx = 0;                                           // the next W block to issue: tap (wy, wx), channel block wc
+    auto issue_w = [&](uint16_t* ws) {
+        const char* uw = reinterpret_cast<const char*>(Wp) + (size_t)((wy * TW + wx) * a.cb + wc) * a.N * 64;
+        SDVAR_DMA16(lw0, uw, SDVAR_LDS_ADDR(ws + swave * 512));
+        SDVAR_DMA16(lw0, uw + a.wps * 2, SDVAR_LDS_ADDR(ws + 5120 + swave * 512));
+        if (two_w) {
+            SDVAR_DMA16(lw1, uw, SDVAR_LDS_ADDR(ws + 4096 + swave * 512));
+            SDVAR_DMA16(lw1, uw + a.wps * 2, SDVAR_LDS_ADDR(ws + 5120 + 4096 + swave * 512));
+        }
+        if (++wx == TW) { wx = 0; if (++wc == a.cb) { wc = 0; ++wy; } }
+    };
+
+    // prologue: X group 0, W blocks 0 and 1 (ng >= 2 and nk >= 4 always)
+    issue_x(csm, 0); issue_x(csm, 1); x_adv();
+    issue_w(wring);
+    issue_w(wring + CWSTAGE_R);
+
+    cf32x4 acc16[2][10];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 10; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.f;
+    // X fragment addresses inside a stage (bytes, plane 0; plane 1 at + 17408): [dx][row tile]
+    uint32_t fxa[TW][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int rel = prow(m0 + wave * 32 + 16 * i + l15) - p0;
+#pragma unroll
+        for (int dx = 0; dx < TW; ++dx) {
+            const int row = rel + 1 + ((TW == 3) ? dx - 1 : dx - 1 + (phase & 1));
+            fxa[dx][i] = (uint32_t)(row * 64 + 16 * (lq ^ ((row >> 2) & 3)));
+        }
+    }
+    const uint32_t fro = (uint32_t)(l15 * 64 + 16 * (lq ^ ((l15 >> 2) & 3)));
+    const uint32_t xb0 = SDVAR_LDS_ADDR(csm), wb0 = SDVAR_LDS_ADDR(wring) + fro;
+
+#define SDVAR_C_SLOT() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define SDVAR_LDS_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
+#define SDVAR_C_MFMA16(J0)                                                                                      \
+    _Pragma("unroll") for (int j = 0; j < 5; ++j)                                                               \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
+            acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][0], fx[i][1], acc16[i][(J0) + j], 0, 0, 0);   \
+            acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][1], fx[i][0], acc16[i][(J0) + j], 0, 0, 0);   \
+            acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][0], fx[i][0], acc16[i][(J0) + j], 0, 0, 0);   \
+        }
+    conv_vm_wait(nw);                                    // X group 0 and W block 0 landed; W block 1 may be in flight
+    SDVAR_C_SLOT();
+    if (late) SDVAR_C_SLOT();
+    f16x8 fx[2][2], fw[5][2];                            // [row tile][plane], [column tile of the half][plane]
+#pragma unroll 1
+    for (int g = 0; g < ng; ++g) {
+        const bool xpf = g + 1 < ng;
+        const uint32_t xsb = xb0 + (uint32_t)(g & 1) * (uint32_t)(CXSTAGE_R * 2);
+        uint16_t* const xn = csm + ((g + 1) & 1) * CXSTAGE_R;
+#pragma unroll
+        for (int dx = 0; dx < TW; ++dx) {
+            const int t = g * TW + dx;
+            const bool wpf = t + 2 < nk;
+            const uint32_t xa0 = xsb + fxa[dx][0], xa1 = xsb + fxa[dx][1];
+            const uint32_t wa = wb0 + (uint32_t)(t & 3) * (uint32_t)(CWSTAGE_R * 2);
+            int issued = 0;
+            // ---- L0(t)
+            SDVAR_LDS_RD(fx[0][0], xa0, 0); SDVAR_LDS_RD(fx[0][1], xa0, 17408); SDVAR_LDS_RD(fx[1][0], xa1, 0); SDVAR_LDS_RD(fx[1][1], xa1, 17408);
+            SDVAR_LDS_RD(fw[0][0], wa, 0);    SDVAR_LDS_RD(fw[0][1], wa, 10240); SDVAR_LDS_RD(fw[1][0], wa, 1024); SDVAR_LDS_RD(fw[1][1], wa, 11264);
+            SDVAR_LDS_RD(fw[2][0], wa, 2048); SDVAR_LDS_RD(fw[2][1], wa, 12288); SDVAR_LDS_RD(fw[3][0], wa, 3072); SDVAR_LDS_RD(fw[3][1], wa, 13312);
+            SDVAR_LDS_RD(fw[4][0], wa, 4096); SDVAR_LDS_RD(fw[4][1], wa, 14336);
+            if (xpf) {
+                if (dx == 0) { issue_x(xn, 0); issued += nx0; }
+                if (dx == TW - 2) { issue_x(xn, 1); issued += 2; }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            SDVAR_C_SLOT();
+            SDVAR_C_MFMA16(0);                           // M0(t): column tiles 0-4
+            SDVAR_C_SLOT();
+            // ---- L1(t)
+            SDVAR_LDS_RD(fw[0][0], wa, 5120); SDVAR_LDS_RD(fw[0][1], wa, 15360); SDVAR_LDS_RD(fw[1][0], wa, 6144); SDVAR_LDS_RD(fw[1][1], wa, 16384);
+            SDVAR_LDS_RD(fw[2][0], wa, 7168); SDVAR_LDS_RD(fw[2][1], wa, 17408); SDVAR_LDS_RD(fw[3][0], wa, 8192); SDVAR_LDS_RD(fw[3][1], wa, 18432);
+            SDVAR_LDS_RD(fw[4][0], wa, 9216); SDVAR_LDS_RD(fw[4][1], wa, 19456);
+            if (wpf) { issue_w(wring + ((t + 2) & 3) * CWSTAGE_R); issued += nw; }
+            if (late) conv_vm_wait(issued);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            SDVAR_C_SLOT();
+            SDVAR_C_MFMA16(5);                           // M1(t): column tiles 5-9
+            if (!late) conv_vm_wait(issued);
+            SDVAR_C_SLOT();
+        }
+        if (xpf) x_adv();
+    }
+    if (!late) SDVAR_C_SLOT();
+#undef SDVAR_C_MFMA16
+#undef SDVAR_LDS_RD
+#undef SDVAR_C_SLOT
+    if (SDVAR_CDBG(a, 1)) return;
+    conv_epilogue16<EPI>(a, acc16, a.wsi ? *a.wsi : 1.0f, m0, n0, tm, 0, phase, wave, l15, lq, tid, csm);
+}
+
 // out = sum_s slab[s] + bias (+ res)
 __global__ __launch_bounds__(256) void conv_reduce_kernel(const float* __restrict__ ws, int split, const float* __restrict__ bias, const float* res,
                                                           float* out, int M, int N) {
@@ -675,6 +873,9 @@ int upconv_weights(const float* w, float* weff, int Cout, int Cin, hipStream_t s
     return SDVAR_OK;
 }
 
+static thread_local int g_conv_last_reuse = 0;      // 1: the last conv_planes launch of this host thread took conv_f16x2_reuse_kernel (test aid)
+int debug_get_conv_tap_reuse() { return g_conv_last_reuse; }
+
 // split heuristic: fill the 256 CUs (one resident workgroup each) without leaving a mostly empty last round
 static int conv_choose_split(int M, int N, int nkt, size_t ws_floats, double kstep_cycles) {
     const long tiles = (long)((M + CBM - 1) / CBM) * ((N + CBN - 1) / CBN);
@@ -732,7 +933,22 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
     // SDVAR_CONV_PP is read per call; sdvar_debug_set_variant("conv_pp", v) overrides it (tests): 0 = the round-2 loop, 1 = ping-pong on 32x32x16, 2 (default) = ping-pong on 16x16x32
     const int pp_env = variant(VAR_CONV_PP);
     const int pp = (pp_env == 2 && N % 4 != 0) ? 1 : pp_env;                                         // the 16-byte epilogue needs whole groups of four columns
-    static LdsOptIn opt_in, opt_in_h;
+    // SDVAR_CONV_TAP_REUSE (read per call; sdvar_debug_set_variant("conv_tap_reuse", v)): 1 (default) = conv_f16x2_reuse_kernel where the shape allows it, 0 = never.
+    // A tile must be part of one image row or whole rows of one image (the staged span is contiguous and <= 264 rows), and the DMA lane offsets are 32-bit.
+    const bool reuse = F16 && pp == 2 && variant(VAR_CONV_TAP_REUSE) == 1 && (taps == 9 || taps == 4) && split == 1 && (H * Wd) % CBM == 0 &&
+                       (Wd % CBM == 0 || (CBM % Wd == 0 && Wd >= 64)) && x_rows * 64 <= 0xFFFFFFFFull;
+    g_conv_last_reuse = reuse ? 1 : 0;
+    static LdsOptIn opt_in, opt_in_h, opt_in_r;
+    if (reuse) {
+        SDVAR_LDS_OPT_IN(opt_in_r, CLDS_R, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 3>, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3>,
+                         (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 2>);
+        if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; }
+        if (taps == 4) hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS, 2>), dim3(tiles, 4), dim3(512), CLDS_R, stream, a);
+        else if (res) hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3>), dim3(tiles), dim3(512), CLDS_R, stream, a);
+        else hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS, 3>), dim3(tiles), dim3(512), CLDS_R, stream, a);
+        SDVAR_LAUNCH_CHECK();
+        return SDVAR_OK;
+    }
     if (F16) SDVAR_LDS_OPT_IN(opt_in_h, lds, (const void*)conv_f16x2_kernel<CEPI_BIAS, 0>, (const void*)conv_f16x2_kernel<CEPI_BIAS_RES, 0>, (const void*)conv_f16x2_kernel<CEPI_PARTIAL, 0>,
                               (const void*)conv_f16x2_kernel<CEPI_BIAS, 1>, (const void*)conv_f16x2_kernel<CEPI_BIAS_RES, 1>, (const void*)conv_f16x2_kernel<CEPI_PARTIAL, 1>,
                               (const void*)conv_f16x2_kernel<CEPI_BIAS, 2>, (const void*)conv_f16x2_kernel<CEPI_BIAS_RES, 2>, (const void*)conv_f16x2_kernel<CEPI_PARTIAL, 2>);

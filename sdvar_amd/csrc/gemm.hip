@@ -191,6 +191,7 @@ Variant g_variants[VAR_COUNT] = {
     {"gemm_small_pp", "SDVAR_GEMM_SMALL_PP", 2, 0, 2, 2, false, false},         // 0 = ring kernel for every small tile, 1 = ping-pong kernel for 64-row tiles, 2 = for 32-row tiles too
     {"attn_pp_sched", "SDVAR_ATTN_PP_SCHED", 1, 0, 3, 1, false, false},         // schedule of the 8-wave attention kernel
     {"conv_pp", "SDVAR_CONV_PP", 2, 0, 2, 2, true, false},                      // decoder convolution loop
+    {"conv_tap_reuse", "SDVAR_CONV_TAP_REUSE", 1, 0, 1, 1, true, false},        // decoder convolution: X staged once per row of taps where the shape allows it
     {"rowblk", "SDVAR_ROWBLK", 1, 0, 2, 1, false, false},                       // 0 off, 1 from 32 rows, 2 every call of at most 80 rows (sdvar_debug_set_rowblk)
     {"qkv_fuse", "SDVAR_NO_QKV_FUSE", 1, 0, 1, 1, false, true},                 // QKV finish in the GEMM epilogue (sdvar_debug_set_qkv_fuse)
     {"gemm_v2", nullptr, 1, 0, 1, 1, false, false},                             // bf16x3 128-row tile on the LDS-DMA kernel

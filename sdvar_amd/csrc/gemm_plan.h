@@ -18,13 +18,13 @@ namespace sdvar {
 // ---- variant table -----------------------------------------------------------------------------------------------------------------------------------------
 // One entry per switch that has a setter.  The value is env-or-default until a setter stores one; a setter value < 0 goes back to env-or-default.  An environment
 // value outside [lo, hi] maps to `fallback`.  The atomics make reads from concurrent host threads safe; the setters are still meant for single-threaded tools.
-enum VariantId { VAR_GEMM_H4, VAR_GEMM_H2_STAGES, VAR_GEMM_SMALL_PP, VAR_ATTN_PP_SCHED, VAR_CONV_PP, VAR_ROWBLK, VAR_QKV_FUSE, VAR_GEMM_V2, VAR_FORCE_BM, VAR_FORCE_SPLIT, VAR_COUNT };
+enum VariantId { VAR_GEMM_H4, VAR_GEMM_H2_STAGES, VAR_GEMM_SMALL_PP, VAR_ATTN_PP_SCHED, VAR_CONV_PP, VAR_CONV_TAP_REUSE, VAR_ROWBLK, VAR_QKV_FUSE, VAR_GEMM_V2, VAR_FORCE_BM, VAR_FORCE_SPLIT, VAR_COUNT };
 
 struct Variant {
     const char* name;           // sdvar_debug_set_variant's name; null: set only through its own ABI function
     const char* env;            // null: no environment variable
     int def, lo, hi, fallback;
-    bool env_per_call;          // read the environment at every use (tests change SDVAR_CONV_PP inside one process)
+    bool env_per_call;          // read the environment at every use (tests change SDVAR_CONV_PP / SDVAR_CONV_TAP_REUSE inside one process)
     bool env_switches_off;      // the variable's presence means 0, whatever a setter said (SDVAR_NO_QKV_FUSE)
     std::atomic<int> set{INT_MIN}, cached{INT_MIN};
 
