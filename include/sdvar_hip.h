@@ -542,6 +542,26 @@ int sdvar_op_half_operand(const void* x, int32_t x_dtype, int32_t ldx, int32_t r
  * asked for. */
 int sdvar_op_gelu_bwd_h(const float* dh, const void* pre, int32_t M, int32_t N, int32_t dtype, void* dpre, void* dpre_t, void* h_t, float* colsum_part, void* stream);
 
+/* ---- the dense linears under autograd (the reference's mat_qkv, proj, ada_lin, word_embed and head; sdvar_amd/seam.py linear_grad / linear_amp_grad) ------------------
+ * csrc/linear_train.hip.  Added without an ABI bump (purely additive).  y = x W^T + b, dx = dy W, dW = dy^T x, db = sum_m dy: the three entries below make ONE pass over dy
+ * and write everything the two gradient GEMMs and db read.  Every pointer 16-byte aligned; argument errors (NULL or misaligned pointers, cols % 32, an unknown format or
+ * dtype, every output NULL) are reported before any launch.  No atomics, no host synchronisation.
+ * sdvar_op_grad_operands: dy fp32 (rows, cols) with leading dimension ld (cols % 32 == 0, ld % 4 == 0, rows >= 1), read once.  Outputs, each may be NULL:
+ *   out         the row-major operand (rows x cols) of dy * scale[0]: format 2 = the bits of sdvar_op_split_planes_f16 with that scale, 3 = those of sdvar_op_split_planes;
+ *               format 0 has none (dy itself is the operand: out must be NULL).  Plane strides in elements, multiples of 8, at least the operand.
+ *   out_t       the operand of dy^T, (cols x Mp), Mp = rows rounded up to 32, zero tail written here: the bits of sdvar_op_transpose_operand in formats 0 / 2 / 3.
+ *   colsum_part float[Mp/32][cols]: the column sums of the UNSCALED dy over each block of 32 rows, added in row order in fp32 (finish with sdvar_op_colsum).
+ * scale (format 2 only, may be NULL): a device scale pair {2^S, 2^-S, ..} as sdvar_op_gelu_bwd takes it. */
+int sdvar_op_grad_operands(const float* dy, int32_t ld, int32_t rows, int32_t cols, int32_t format, const float* scale, void* out, uint64_t out_plane_stride, void* out_t,
+                           uint64_t out_t_plane_stride, float* colsum_part, void* stream);
+/* The same pass for the half matrix cores.  dtype: 1 = fp16, 2 = bf16; x_dtype: 0 = fp32 input, rounded to nearest even as it is read, else = dtype (ld % 8 == 0 then).
+ * out = OPERAND (rows x cols), out_t = OPERAND (cols x Mp) of the transpose: the bits sdvar_op_half_operand writes with transpose 0 / 1; colsum_part = the bits of that
+ * entry's colsum_part (sums of the ROUNDED values).  Each may be NULL, not all three. */
+int sdvar_op_grad_operands_h(const void* dy, int32_t x_dtype, int32_t ld, int32_t rows, int32_t cols, int32_t dtype, void* out, void* out_t, float* colsum_part, void* stream);
+/* in = a K-blocked operand (rows x K) of 16-bit elements (either dtype: the bits move untouched), K % 32 == 0 -> out = the operand of its transpose, (K x Mp), Mp = rows
+ * rounded up to 32, zero tail written here: bit-identical to sdvar_op_half_operand(.., transpose = 1) on the row-major matrix the operand was made from. */
+int sdvar_op_operand_transpose_h(const void* in, int32_t rows, int32_t K, void* out, void* stream);
+
 /* ---- the adaLN modulation and the gated residual of a block under autograd (AdaLNSelfAttn.forward, basic_var.py:152-159; AdaLNBeforeHead.forward, :172-174) ----------
  * csrc/adaln_train.hip.  Added without an ABI bump (purely additive).  Common to the six entry points:
  *   - x, out, g, dx are (B, L, C) fp32, dense, 16-byte aligned; C % 4 == 0, 4 <= C <= 3072, B, L >= 1, B * L <= 2^29.  One wave64 per row, float4 accesses.

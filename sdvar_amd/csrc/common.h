@@ -237,6 +237,61 @@ __device__ __forceinline__ void split8_packed(const float* v, u32x4& a, u32x4& b
 // fragments at stride 2K: twice the L1/TA requests per byte).
 __device__ __forceinline__ size_t kb_index(int row, int k, int rows) { return ((size_t)(k >> 5) * rows + row) * 32 + (k & 31); }
 
+// ---- shared by the operand producers of the seam's backward passes (mlp_bwd.hip, mlp_half.hip, linear_train.hip)
+enum { OPF_F32 = 0 };               // an operand format next to PLANES_F16X2 / PLANES_BF16X3: plain fp32 row-major
+// eight consecutive values of one operand row -> memory, at element (row, k) of a (rows x K) operand; k % 8 == 0
+__device__ __forceinline__ void store_operand8(void* out, size_t ps, int fmt, int row, int k, int rows, int ldo, const float* v, bool live) {
+    if (fmt == OPF_F32) {
+        if (live) {
+            float* p = reinterpret_cast<float*>(out) + (size_t)row * ldo + k;
+            *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+        }
+        return;
+    }
+    uint16_t* outp = reinterpret_cast<uint16_t*>(out);
+    const size_t o = kb_index(row, k, rows);
+    if (fmt == PLANES_F16X2) {
+        uint2 h0, l0, h1, l1;
+        split4h_pk(v, h0, l0); split4h_pk(v + 4, h1, l1);             // wave-uniform range test inside: called by every lane
+        if (live) {
+            *reinterpret_cast<u32x4*>(outp + o) = u32x4{h0.x, h0.y, h1.x, h1.y};
+            *reinterpret_cast<u32x4*>(outp + ps + o) = u32x4{l0.x, l0.y, l1.x, l1.y};
+        }
+    } else {
+        u32x4 a, b, c;
+        split8_packed(v, a, b, c);
+        if (live) { *reinterpret_cast<u32x4*>(outp + o) = a; *reinterpret_cast<u32x4*>(outp + ps + o) = b; *reinterpret_cast<u32x4*>(outp + 2 * ps + o) = c; }
+    }
+}
+// eight values <-> one packed 16-byte word of fp16 (bf = false) or bf16
+__device__ __forceinline__ u32x4 hp_pack8(const float* v, bool bf) {
+    return u32x4{half_pack2(v[0], v[1], bf), half_pack2(v[2], v[3], bf), half_pack2(v[4], v[5], bf), half_pack2(v[6], v[7], bf)};
+}
+__device__ __forceinline__ void hp_unpack8(const u32x4& w, bool bf, float* v) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[2 * e] = half_lo(w[e], bf); v[2 * e + 1] = half_hi(w[e], bf); }
+}
+// The transposing producers move a 32 (k) x 64 (c) tile through LDS with rows padded to 65 words (the bank argument is in mlp_bwd.hip); 256 threads.
+constexpr int OPT_K = 32, OPT_C = 64, OPT_S = 65;
+// the LDS tile -> rows c0 .. c0 + 63 of the transposed operand (R rows, K = Kp), k block kb; SCALED: the values are multiplied by sc as they leave the tile
+template <bool SCALED = false>
+__device__ __forceinline__ void store_tile_t(const float* tile, void* out, size_t ps, int fmt, int c0, int kb, int R, int Kp, float sc = 1.0f) {
+    const int cl = threadIdx.x >> 2, kq = threadIdx.x & 3;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = SCALED ? tile[(8 * kq + e) * OPT_S + cl] * sc : tile[(8 * kq + e) * OPT_S + cl];
+    store_operand8(out, ps, fmt, c0 + cl, kb * OPT_K + 8 * kq, R, Kp, v, c0 + cl < R);
+}
+// the LDS tile of rounded values -> rows c0 .. c0 + 63 of the transposed half operand (R rows), k block kb
+__device__ __forceinline__ void hp_store_tile_t(const float* tile, uint16_t* out, bool bf, int c0, int kb, int R) {
+    const int cl = threadIdx.x >> 2, kq = threadIdx.x & 3;
+    if (c0 + cl >= R) return;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = tile[(8 * kq + e) * OPT_S + cl];
+    *reinterpret_cast<u32x4*>(out + kb_index(c0 + cl, kb * OPT_K + 8 * kq, R)) = hp_pack8(v, bf);
+}
+
 // ---- Philox4x32-10 (must match sdvar_amd/noise.py bit for bit) ----------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t out[4]) {

@@ -24,44 +24,9 @@ namespace sdvar {
 
 int weight_scale_f16(const float* w, size_t n, float* sc, hipStream_t stream);          // gemm_f16x2.hip
 
-enum { OPF_F32 = 0 };               // next to PLANES_F16X2 / PLANES_BF16X3
-constexpr int TK = 32, TC = 64, TS = 65;
+constexpr int TK = OPT_K, TC = OPT_C, TS = OPT_S;          // the transposing tile of common.h (store_tile_t)
 
-// gelu_val_grad (g and g' of both GELU forms) lives in common.h: the half-precision producers (mlp_half.hip) share it.
-
-// eight consecutive values of one operand row -> memory, at element (row, k) of a (rows x K) operand; k % 8 == 0
-__device__ __forceinline__ void store_operand8(void* out, size_t ps, int fmt, int row, int k, int rows, int ldo, const float* v, bool live) {
-    if (fmt == OPF_F32) {
-        if (live) {
-            float* p = reinterpret_cast<float*>(out) + (size_t)row * ldo + k;
-            *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        }
-        return;
-    }
-    uint16_t* outp = reinterpret_cast<uint16_t*>(out);
-    const size_t o = kb_index(row, k, rows);
-    if (fmt == PLANES_F16X2) {
-        uint2 h0, l0, h1, l1;
-        split4h_pk(v, h0, l0); split4h_pk(v + 4, h1, l1);             // wave-uniform range test inside: called by every lane
-        if (live) {
-            *reinterpret_cast<u32x4*>(outp + o) = u32x4{h0.x, h0.y, h1.x, h1.y};
-            *reinterpret_cast<u32x4*>(outp + ps + o) = u32x4{l0.x, l0.y, l1.x, l1.y};
-        }
-    } else {
-        u32x4 a, b, c;
-        split8_packed(v, a, b, c);
-        if (live) { *reinterpret_cast<u32x4*>(outp + o) = a; *reinterpret_cast<u32x4*>(outp + ps + o) = b; *reinterpret_cast<u32x4*>(outp + 2 * ps + o) = c; }
-    }
-}
-
-// the 32 (k) x 64 (c) LDS tile -> rows c0 .. c0 + 63 of the transposed operand (R rows, K = Kp), k block kb
-__device__ __forceinline__ void store_tile_t(const float* tile, void* out, size_t ps, int fmt, int c0, int kb, int R, int Kp) {
-    const int cl = threadIdx.x >> 2, kq = threadIdx.x & 3;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = tile[(8 * kq + e) * TS + cl];
-    store_operand8(out, ps, fmt, c0 + cl, kb * TK + 8 * kq, R, Kp, v, c0 + cl < R);
-}
+// gelu_val_grad (g and g' of both GELU forms), OPF_F32, store_operand8 and store_tile_t live in common.h: mlp_half.hip and linear_train.hip share them.
 
 // ------------------------------------------------------------------------------------------------ transpose_operand
 __global__ __launch_bounds__(256) void transpose_operand_kernel(const float* __restrict__ x, int ldx, int rows, int cols, int fmt, void* __restrict__ out, size_t ps,

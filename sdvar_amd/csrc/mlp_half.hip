@@ -19,15 +19,9 @@
 
 namespace sdvar {
 
-constexpr int HK = 32, HC = 64, HS = 65;
+constexpr int HK = OPT_K, HC = OPT_C, HS = OPT_S;          // the transposing tile of common.h (hp_store_tile_t)
 
-__device__ __forceinline__ u32x4 hp_pack8(const float* v, bool bf) {
-    return u32x4{half_pack2(v[0], v[1], bf), half_pack2(v[2], v[3], bf), half_pack2(v[4], v[5], bf), half_pack2(v[6], v[7], bf)};
-}
-__device__ __forceinline__ void hp_unpack8(const u32x4& w, bool bf, float* v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = half_lo(w[e], bf); v[2 * e + 1] = half_hi(w[e], bf); }
-}
+// hp_pack8 / hp_unpack8 (eight values <-> one packed 16-byte word of the dtype) and hp_store_tile_t live in common.h: linear_train.hip shares them.
 // eight consecutive values of a row, rounded to the operand dtype, as floats and as the packed word; x_dtype 0 = fp32 input, else the input already has the operand dtype
 __device__ __forceinline__ u32x4 hp_load8(const void* x, int x_dtype, size_t off, bool bf, float* v) {
     u32x4 w;
@@ -41,16 +35,6 @@ __device__ __forceinline__ u32x4 hp_load8(const void* x, int x_dtype, size_t off
     }
     hp_unpack8(w, bf, v);
     return w;
-}
-
-// the 32 (k) x 64 (c) LDS tile of rounded values -> rows c0 .. c0 + 63 of the transposed operand (R rows), k block kb
-__device__ __forceinline__ void hp_store_tile_t(const float* tile, uint16_t* out, bool bf, int c0, int kb, int R) {
-    const int cl = threadIdx.x >> 2, kq = threadIdx.x & 3;
-    if (c0 + cl >= R) return;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = tile[(8 * kq + e) * HS + cl];
-    *reinterpret_cast<u32x4*>(out + kb_index(c0 + cl, kb * HK + 8 * kq, R)) = hp_pack8(v, bf);
 }
 
 // ------------------------------------------------------------------------------------------------ half_operand, as stored

@@ -141,6 +141,9 @@ _SIGNATURES = {
     "sdvar_op_gemm_h": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "sdvar_op_half_operand": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sdvar_op_gelu_bwd_h": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "sdvar_op_grad_operands": (_I, [_P, _I, _I, _I, _I, _P, _P, _U64, _P, _U64, _P, _P]),
+    "sdvar_op_grad_operands_h": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sdvar_op_operand_transpose_h": (_I, [_P, _I, _I, _P, _P]),
     "sdvar_op_adaln_fwd": (_I, [_P, _P, _I, C.c_int64, _P, _I, C.c_int64, _P, _I, _I, _I, _D, _P]),
     "sdvar_op_adaln_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
     "sdvar_op_adaln_bwd": (_I, [_P, _P, _I, C.c_int64, _P, _P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _D, _P]),

@@ -28,6 +28,10 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install_train_amp(basic_var, model, ffn="half", adaln=True, qknorm=True)    # the same under autocast; seam.install_qknorm(model) alone for inference,
                                                                                      # seam.uninstall_qknorm(model) takes the bound forwards off again
 
+    seam.install_train(basic_var, model, ffn=True, adaln=True, qknorm=True, linears=True)    # ... and every dense nn.Linear (mat_qkv, proj, ada_lin, word_embed, head):
+    seam.install_train_amp(basic_var, model, ffn="half", adaln=True, qknorm=True, linears=True)   # linear_grad / linear_amp_grad, picked per call; seam.install_linears(model)
+                                                                                     # alone for inference, seam.uninstall_linears(model) takes them off again
+
     seam.install_optimizer(var_opt)         # the AmpOptimizer's AdamW (utils/amp_sc.py): unscale + clip_grad_norm_ + AdamW.step as two passes on HIP (seam.AdamW)
 
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
@@ -47,6 +51,8 @@ scale is widened to float32 before the + 1, where torch's scale.add(1) rounds th
 qk_l2norm is what SelfAttention.forward does between the QKV GEMM and the attention call when attn_l2_norm is on (basic_var.py:93-105): bias add, per-head L2
 normalisation of q and k and the learnt per-head scale of q, one kernel per direction (csrc/qknorm_train.hip: sdvar_op_qknorm_fwd / _bwd; qkv, the biases and the scale
 parameter saved; no double backward).  The float32 master bias is added in float32 to the GEMM's output, where autocast rounds acc + half(bias) to half inside the GEMM.
+linear / linear_grad / linear_amp / linear_amp_grad are F.linear on the operator GEMMs of the configured mode, resp. on the half matrix cores (csrc/linear_train.hip:
+sdvar_op_grad_operands / _h read dy once for both gradient GEMMs and db; the amp path saves the forward's half operand of x, 2 M K bytes; no double backward).
 AdamW / install_optimizer are the optimizer step outside the blocks (utils/amp_sc.py:39-75, train.py:118): torch's decoupled AdamW on float32 parameters with the
 GradScaler's unscale, clip_grad_norm_'s global norm and the non-finite skip folded into two passes over the tensors (csrc/optim.hip: sdvar_optim_grad_stats,
 sdvar_optim_adamw_step); the norm stays on the device as `global_grad_norm`, the reference's late-clipping slot.  The gradients are read, never modified.
@@ -75,7 +81,8 @@ __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_f
            "enable_flash", "install_amp", "clear_caches", "slow_attn_grad", "memory_efficient_attention_grad", "install_train",
            "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
            "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad", "adaln_modulate", "gated_residual",
-           "uninstall_adaln", "qk_l2norm", "install_qknorm", "uninstall_qknorm", "AdamW", "install_optimizer"]
+           "uninstall_adaln", "qk_l2norm", "install_qknorm", "uninstall_qknorm", "AdamW", "install_optimizer", "linear", "linear_grad", "linear_amp", "linear_amp_grad",
+           "install_linears", "uninstall_linears"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -83,9 +90,10 @@ _gemm_mode = E.DEFAULT_GEMM_MODE
 _SKIP_MAPS: "OrderedDict[tuple, tuple]" = OrderedDict()
 _SKIP_MAPS_MAX = 8
 # (kind, mode, data_ptr, shape) -> (weight, _version, planes, scale): GEMM operand planes of a weight ("n": as stored, none in mode f32; "t": of its transpose, for the
-# backward).  A weight updated in place replaces its own entry.  A d30 model has 60 FFN weights.
+# backward).  A weight updated in place replaces its own entry.  A d30 model has 60 FFN weights; with the dense linears (linears=True) a d36 model holds
+# 36 blocks x 5 weights x 2 kinds + head and word_embed = 364 entries, and an LRU visited in model order that is one entry short misses on EVERY access.
 _WEIGHT_PLANES: "OrderedDict[tuple, tuple]" = OrderedDict()
-_WEIGHT_PLANES_MAX = 256
+_WEIGHT_PLANES_MAX = 512
 
 
 def configure(gemm_mode: Optional[str] = None) -> None:
@@ -905,6 +913,283 @@ def fused_mlp_func_amp_grad(x, weight1, weight2, bias1=None, bias2=None, activat
     return _MlpAmpGrad.apply(x, weight1, weight2, bias1, bias2, half)
 
 
+# ------------------------------------------------------------------------------------------------------- the dense linears (csrc/linear_train.hip)
+def _linear_check(who: str, x, weight, bias, amp: bool, grad: bool):
+    """The argument checks of the four linear functions.  amp / grad as for _mlp_check.  Returns (half or None, K, N).  Nothing here touches the library."""
+    named = [("x", x), ("weight", weight)] + ([] if bias is None else [("bias", bias)])
+    refuse = not grad and torch.is_grad_enabled()
+    for name, t in named:
+        _gpu_tensor(who, name, t)
+        if t.dtype == torch.float64:
+            raise SdvarError(f"{who}: {name} is torch.float64; only float32" + (", float16 and bfloat16 operands" if amp else " operands") + f" are supported - pass {name}.float()")
+        if amp:
+            if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+                raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+        elif t.dtype in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; this function takes float32 operands only - use {'linear_amp_grad' if grad else 'linear_amp'} for half operands")
+        elif t.dtype != torch.float32:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32 operands are supported")
+    half = None
+    if amp:
+        half = x.dtype if x.dtype in _HALF_DTYPES else _autocast_gpu_dtype()
+        if half not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: x is {x.dtype} and torch.autocast is not enabled for the GPU with float16 / bfloat16: there is no half dtype to compute in - "
+                             f"call it under torch.autocast or with a half x, or use {'linear_grad' if grad else 'linear'} for float32 arithmetic")
+        for name, t in named:
+            if t.dtype != torch.float32 and t.dtype != half:
+                raise SdvarError(f"{who}: mixed half dtypes: {name} is {t.dtype} but the half dtype of the call is {half} (every operand must be {half} or float32)")
+    if refuse:
+        for name, t in named:
+            if t.requires_grad:
+                raise SdvarError(f"{who}: {name} requires grad and grad mode is on; no backward exists (call under torch.no_grad(), or use {who}_grad)")
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1]:
+        raise SdvarError(f"{who}: shapes do not chain: x {tuple(x.shape)}, weight {tuple(weight.shape)} (x (..., K) with weight (N, K))")
+    N, K = weight.shape
+    if K % 32:
+        raise SdvarError(f"{who}: in_features {K} (the last dim of x) must be a multiple of 32")
+    if amp and N % 8:
+        raise SdvarError(f"{who}: out_features {N} (weight.shape[0]) must be a multiple of 8")
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise SdvarError(f"{who}: bias has shape {tuple(bias.shape)}, expected ({N},)")
+    if any(t.device != x.device for _, t in named):
+        raise SdvarError(f"{who}: operands live on different devices; move weight and bias to x's device")
+    return half, K, N
+
+
+def _linear_wants_grad(who: str, x, weight, bias, N: int) -> bool:
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        return False
+    if N % 32:
+        raise SdvarError(f"{who}: out_features {N} (weight.shape[0]) must be a multiple of 32 under grad (it is K of the dx = dy W product)")
+    return True
+
+
+def _rows16(x: torch.Tensor, K: int) -> torch.Tensor:
+    """x (..., K) as the dense, 16-byte aligned (M, K) matrix the kernels read: a view where x is one, else one copy.  A single row is given the row stride K (a one-row
+    slice of a wider buffer counts as dense whatever its row stride is, and a kernel's leading dimension is a stride)."""
+    xr = _dense16(x.detach().reshape(-1, K))
+    return xr.as_strided((1, K), (K, 1)) if xr.shape[0] == 1 else xr
+
+
+def _linear_forward(x, weight, bias, mode: str):
+    """(out, xr): x W^T + b as one operator GEMM of `mode` behind one operand pass over x (none in mode f32)."""
+    N, K = weight.shape
+    xr = _rows16(x, K)
+    M = xr.shape[0]
+    out = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=torch.float32, device=x.device)
+    if M == 0:
+        return out, xr
+    st = E._stream()
+    b = None if bias is None else _dense16(bias.detach())
+    if mode == "f32":
+        _gemm_nt(mode, xr, _dense16(weight.detach()), None, out, M, N, K, b, st=st)
+    else:
+        w, sw = _weight_planes(weight, mode)
+        _gemm_nt(mode, _split_planes(xr, mode, M, K, st=st), w, _p(sw), out, M, N, K, b, st=st)
+    return out, xr
+
+
+def linear(x, weight, bias=None):
+    """F.linear on the operator GEMMs of the configured mode (seam.configure): x (..., K) W (N, K)^T + bias (N,) -> (..., N), float32 operands on the GPU, K % 32 == 0.
+    One GEMM launch behind one operand pass over x (modes f16x2 / bf16x3; mode f16x2 saturates x at +-65504 as fused_mlp_func does); the weight's operand planes come
+    from the FFN's cache and are replaced when the weight is updated in place.  x is read in place when dense and 16-byte aligned, else copied once.  Inference only:
+    an operand that requires grad while grad mode is on raises (use linear_grad).  Anything else raises SdvarError - there is no fall-back to torch."""
+    _linear_check("linear", x, weight, bias, False, False)
+    return _linear_forward(x, weight, bias, _gemm_mode)[0]
+
+
+class _LinearGrad(torch.autograd.Function):
+    """x W^T + b with a HIP backward: two NT GEMMs of the forward's mode on operands one sdvar_op_grad_operands pass writes.  Saved: x (dense (M, K)) and the weight;
+    nothing of x when the weight is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mode):
+        out, xr = _linear_forward(x, weight, bias, mode)
+        ctx.save_for_backward(weight, *((xr,) if ctx.needs_input_grad[1] else ()))
+        ctx.lin = (mode, tuple(x.shape))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        weight, *rest = ctx.saved_tensors
+        mode, xshape = ctx.lin
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        N, K = weight.shape
+        M, dev = math.prod(xshape[:-1]), dy.device
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        if M == 0:
+            z = lambda need, *shape: torch.zeros(*shape, dtype=torch.float32, device=dev) if need else None
+            return z(nx, *xshape), z(nw, N, K), z(nb, N), None
+        if dy.dtype != torch.float32:
+            raise SdvarError(f"linear_grad: the gradient of the output is {dy.dtype} but the output is float32")
+        lib, st, fmt, npl, Mp = E.load_library(), E._stream(), _OPERAND_FORMAT[mode], _OPERAND_PLANES[mode], _pad32(M)
+        h16, el = mode == "f16x2", torch.float32 if mode == "f32" else torch.int16
+        dy = _dense16(dy.reshape(M, N))             # stride-0 expansions, transposed consumers, a dense tensor at a misaligned address: one fresh dense copy
+        off = lambda sc, floats: None if sc is None else C.c_void_p(sc.data_ptr() + 4 * floats)
+        wt = sdy = None
+        if nx:
+            wt, swt = _weight_planes_t(weight, mode)
+        if h16 and (nx or nw):       # the gradient operands carry a per-tensor power-of-two scale: the absmax pass, the one other read of dy
+            sdy = torch.zeros(4, dtype=torch.float32, device=dev)
+            E._check(lib.sdvar_op_scale_pair(_p(dy), M * N, _p(sdy), 0, _p(swt) if nx else None, st))
+        dyo = torch.empty(npl, M * N, dtype=el, device=dev) if nx and mode != "f32" else None
+        dyt = torch.empty(npl, N * Mp, dtype=el, device=dev) if nw else None
+        part = f32(Mp // 32, N) if nb else None
+        if dyo is not None or dyt is not None or part is not None:
+            E._check(lib.sdvar_op_grad_operands(_p(dy), N, M, N, fmt, _p(sdy), _p(dyo), M * N, _p(dyt), N * Mp, _p(part), st))
+        dx = dw = db = None
+        if nx:
+            dx = f32(M, K)
+            _gemm_nt(mode, dy if mode == "f32" else dyo, wt, off(sdy, 2), dx, M, K, N, st=st)
+            dx = dx.view(xshape)
+        if nw:
+            dw = f32(N, K)
+            _gemm_nt(mode, dyt, _transposed_operand(rest[0], mode), off(sdy, 0), dw, N, K, Mp, st=st)
+        if nb:
+            db = f32(N)
+            E._check(lib.sdvar_op_colsum(_p(part), N, Mp // 32, N, _p(db), st))
+        return dx, dw, db, None
+
+
+def linear_grad(x, weight, bias=None):
+    """linear under autograd (the reference's mat_qkv, proj, ada_lin, word_embed and head, and fc1 / fc2 where the FFN slot is empty): signature, operand rules and argument
+    errors as linear, plus out_features % 32 == 0 under grad.  With grad mode off, or nothing requiring grad, it IS linear (same launches, same bits).  Backward:
+    dx = dy W, dW = dy^T x as two NT GEMMs of the configured mode (the mode of the forward call), db = sum_m dy.  dy is read ONCE: one sdvar_op_grad_operands pass
+    writes the row-major operand for dx, the transposed, zero-padded operand for dW and db's 32-row partials (finished by a fixed-order column sum); in mode f16x2 the
+    per-tensor power-of-two scale's absmax pass comes before it.  Saved: x as a dense (M, K) tensor and the weight; nothing of x when the weight does not require grad.
+    Only the gradients autograd asks for are computed (a frozen weight costs no wgrad GEMM and no transposed operand, an x without grad no dgrad GEMM), each has the
+    bits it has in the full run, and repeats are bit-identical: no atomics, no host synchronisation.  A dy that is not dense or not 16-byte aligned is copied once.
+    M == 0 returns zeros without a launch.  No double backward, float32 only."""
+    who = "linear_grad"
+    _, K, N = _linear_check(who, x, weight, bias, False, True)
+    if not _linear_wants_grad(who, x, weight, bias, N):
+        return _linear_forward(x, weight, bias, _gemm_mode)[0]            # what the inference twin launches: the same bits
+    return _LinearGrad.apply(x, weight, bias, _gemm_mode)
+
+
+def _linear_amp_forward(x, weight, bias, half):
+    """(out, xop): half(fp32acc(x_h W_h^T) + b) as one sdvar_op_gemm_h launch behind one operand pass over x; xop = the half operand of x (None when M == 0)."""
+    N, K = weight.shape
+    xr = _rows16(x, K)
+    M = xr.shape[0]
+    out = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=half, device=x.device)
+    if M == 0:
+        return out, None
+    xop = _half_operand(xr, half, False)
+    _gemm_h(half, xop, _weight_operand_h(weight, half, False), _bias_f32(bias), out, M, N, K)
+    return out, xop
+
+
+def linear_amp(x, weight, bias=None):
+    """F.linear for a model run under torch.autocast, on the HALF matrix cores, under fused_mlp_func_amp's dtype rule: the half dtype is x.dtype when x is float16 /
+    bfloat16, else the GPU's autocast dtype; with neither it raises (use linear).  x (..., K), weight (N, K) and bias (N,) are each float32 or that dtype - a float32
+    operand is rounded to nearest even as it is read, the bias enters as float32.  Contract: y = half(fp32acc(x_h W_h^T) + b); nothing is clamped, an fp16 overflow is
+    +-inf.  K % 32 == 0, N % 8 == 0.  One sdvar_op_gemm_h launch behind one operand pass over x; the weight's half operand comes from the FFN's cache.  Returns (..., N)
+    in the half dtype.  Inference only: an operand that requires grad while grad mode is on raises (use linear_amp_grad)."""
+    half, _, _ = _linear_check("linear_amp", x, weight, bias, True, False)
+    return _linear_amp_forward(x, weight, bias, half)[0]
+
+
+class _LinearAmpGrad(torch.autograd.Function):
+    """The half-precision linear with a HIP backward: two sdvar_op_gemm_h launches on operands one sdvar_op_grad_operands_h pass writes.  Saved: the forward's half
+    OPERAND of x (2 M K bytes; sdvar_op_operand_transpose_h turns it into the operand of x^T) and the weight; nothing of x when the weight is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, half):
+        out, xop = _linear_amp_forward(x, weight, bias, half)
+        ctx.save_for_backward(weight, *((xop,) if ctx.needs_input_grad[1] and xop is not None else ()))
+        ctx.lin = (half, tuple(x.shape), x.dtype, None if bias is None else bias.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        weight, *rest = ctx.saved_tensors
+        half, xshape, xdt, bdt = ctx.lin
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        N, K = weight.shape
+        M, dev = math.prod(xshape[:-1]), dy.device
+        if dy.dtype != half:
+            raise SdvarError(f"linear_amp_grad: the gradient of the output is {dy.dtype} but the output is {half}; the backward reads dy in the output's dtype")
+        if M == 0:
+            z = lambda need, dtype, *shape: torch.zeros(*shape, dtype=dtype, device=dev) if need else None
+            return z(nx, xdt, *xshape), z(nw, weight.dtype, N, K), z(nb, bdt, N), None
+        lib, st, dt, Mp = E.load_library(), E._stream(), _HALF_DTYPES[half], _pad32(M)
+        operand = lambda need, n: torch.empty(n, dtype=torch.int16, device=dev) if need else None
+        dy = _dense16(dy.reshape(M, N))             # stride-0 expansions, transposed consumers, a dense tensor at a misaligned address: one fresh dense copy
+        dyo, dyt = operand(nx, M * N), operand(nw, N * Mp)
+        part = torch.empty(Mp // 32, N, dtype=torch.float32, device=dev) if nb else None
+        dx = dw = db = None
+        if nx or nw or nb:
+            E._check(lib.sdvar_op_grad_operands_h(_p(dy), dt, N, M, N, dt, _p(dyo), _p(dyt), _p(part), st))
+        if nx:
+            dx = torch.empty(M, K, dtype=xdt, device=dev)
+            _gemm_h(half, dyo, _weight_operand_h(weight, half, True), None, dx, M, K, N)
+            dx = dx.view(xshape)
+        if nw:
+            xt = torch.empty(K * Mp, dtype=torch.int16, device=dev)
+            E._check(lib.sdvar_op_operand_transpose_h(_p(rest[0]), M, K, _p(xt), st))
+            dw = torch.empty(N, K, dtype=weight.dtype, device=dev)
+            _gemm_h(half, dyt, xt, None, dw, N, K, Mp)
+        if nb:
+            db = torch.empty(N, dtype=torch.float32, device=dev)
+            E._check(lib.sdvar_op_colsum(_p(part), N, Mp // 32, N, _p(db), st))
+            db = db.to(bdt)
+        return dx, dw, db, None
+
+
+def linear_amp_grad(x, weight, bias=None):
+    """linear_amp under autograd: signature, dtype rule, operand rules and argument errors as linear_amp, plus out_features % 32 == 0 under grad.  With grad mode off, or
+    nothing requiring grad, it IS linear_amp (same launches, same bits).  Backward: dx = fp32acc(dy W_h), dW = fp32acc(dy^T x_h) as two sdvar_op_gemm_h launches,
+    db = sum_m dy of the rounded values in a fixed order.  dy is read ONCE: one sdvar_op_grad_operands_h pass writes both operands and db's partials.  Saved: the
+    forward's half operand of x - 2 M K bytes where an fp32 x would cost 4 M K; sdvar_op_operand_transpose_h makes the operand of x^T from it - and the weight; nothing
+    of x when the weight does not require grad.  Gradients come back in each operand's OWN dtype: unrounded float32 for a float32 x / weight / bias (the reference's
+    case: float32 activations into head and master weights), half otherwise.  dy must have the output's dtype; one that is not dense or not 16-byte aligned is copied
+    once.  Only the gradients autograd asks for are computed, each with the bits it has in the full run; deterministic; nothing is clamped: an fp16 overflow is +-inf
+    and reaches the GradScaler.  M == 0 returns zeros without a launch.  No double backward."""
+    who = "linear_amp_grad"
+    half, K, N = _linear_check(who, x, weight, bias, True, True)
+    if not _linear_wants_grad(who, x, weight, bias, N):
+        return _linear_amp_forward(x, weight, bias, half)[0]            # what the inference twin launches: the same bits
+    return _LinearAmpGrad.apply(x, weight, bias, half)
+
+
+def _linear_module_forward(self, input):
+    """nn.Linear.forward on the seam, chosen at call time: a half input, or autocast enabled for the GPU with float16 / bfloat16 -> linear_amp_grad; else linear_grad.
+    The reference's word_embed runs inside autocast(enabled=False) on a float32 x (models/var.py:225-231) and takes the float32 path in the middle of an autocast run;
+    its head runs under autocast on a .float()-ed input (:125) and takes the half path."""
+    if (isinstance(input, torch.Tensor) and input.dtype in _HALF_DTYPES) or _autocast_gpu_dtype() in _HALF_DTYPES:
+        return linear_amp_grad(input, self.weight, self.bias)
+    return linear_grad(input, self.weight, self.bias)
+
+
+def _install_linears(who: str, model) -> None:
+    if model is None:
+        raise SdvarError(f"{who}: linears=True binds a forward on the model's own nn.Linear modules; pass the model (model=None has nothing to bind)")
+    for m in model.modules():
+        if isinstance(m, torch.nn.Linear) and m.in_features % 32 == 0 and m.out_features % 32 == 0:
+            m.forward = types.MethodType(_linear_module_forward, m)
+
+
+def install_linears(model) -> None:
+    """Bind the seam's linear on every nn.Linear of `model` whose in_features and out_features are multiples of 32 (others are left with torch), for inference on top
+    of install() / install_amp() or on top of any other install_* call.  One bound forward, dispatching at call time: a half input, or autocast enabled for the GPU ->
+    linear_amp_grad; otherwise linear_grad (each is its inference twin under torch.no_grad()).  Only calls of the MODULE are served: the reference's SelfAttention
+    calls F.linear(input=x, weight=self.mat_qkv.weight, ...) directly (basic_var.py:93), so without qknorm=True - whose bound forward calls self.mat_qkv(x) - the QKV
+    GEMM stays with torch; likewise fc1 / fc2 are reached only where the FFN slot is None."""
+    _install_linears("install_linears", model)
+
+
+def uninstall_linears(model) -> None:
+    """Delete the instance-level `forward` that install_linears / install_train(..., linears=True) / install_train_amp(..., linears=True) bound: nn.Linear's own forward
+    is back."""
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if getattr(f, "__func__", None) is _linear_module_forward:
+            del m.forward
+
+
 class _XentGrad(torch.autograd.Function):
     """Label-smoothed cross-entropy with a HIP backward: forward = sdvar_xent_train_fwd, backward = one sdvar_xent_train_bwd call (csrc/xent_train.hip).  Saved: the
     logits, the targets and lse (one float per row); reduction 'mean' also keeps the forward's two doubles {sum, counted rows}."""
@@ -1229,7 +1514,7 @@ def install_amp(module, model=None, ffn_half: bool = False) -> None:
         _set_ffn_slots(module, model, fused_mlp_func_amp)
 
 
-def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False) -> None:
+def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False, linears: bool = False) -> None:
     """For TRAINING the reference in fp32 with the seam's operators: `module.slow_attn = slow_attn_grad`.  ffn=False (default): `module.fused_mlp_func = None` plus
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
     state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
@@ -1241,16 +1526,21 @@ def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qk
     attn and ffn are still called as modules, so the slots above keep working.  uninstall_adaln(model) removes the bound forwards.  adaln=False (default) binds
     nothing.  qknorm=True (needs the model) binds an instance-level `forward` on every submodule that has `mat_qkv` and attn_l2_norm=True: basic_var.py:90-119 with
     qk_l2norm between the QKV GEMM and the attention call; the attention slots are still read from the reference module at call time.  uninstall_qknorm(model) removes
-    them.  qknorm=False (default) binds nothing."""
+    them.  qknorm=False (default) binds nothing.  linears=True (needs the model) binds install_linears' forward on every nn.Linear whose in_features and out_features
+    are multiples of 32: mat_qkv (reached through qknorm=True's forward only - the class forward calls F.linear itself, basic_var.py:93), proj, the Linear inside
+    ada_lin, word_embed and head, and fc1 / fc2 where ffn=False leaves them to the module - linear_grad, forward and backward on HIP.  uninstall_linears(model)
+    removes them.  linears=False (default) binds nothing."""
     if adaln:
         _install_adaln("install_train", model)
     if qknorm:
         _install_qknorm("install_train", model)
+    if linears:
+        _install_linears("install_train", model)
     module.slow_attn = slow_attn_grad
     _set_ffn_slots(module, model, fused_mlp_func_grad if ffn else None)
 
 
-def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False) -> None:
+def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False, linears: bool = False) -> None:
     """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
     `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
     the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
@@ -1261,11 +1551,14 @@ def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm
     float32 master weights; out_features % 32 == 0).  `memory_efficient_attention` is left alone for the reason install() documents; assign
     seam.memory_efficient_attention_amp_grad yourself before building the model if you want the BLHc route.  adaln=True: as install_train's; under autocast the
     modulation vectors and the branch outputs arrive in half and are read as they are.  qknorm=True: as install_train's; under autocast qkv arrives in half, q and k
-    leave in float32 and v in half (the mixed operands slow_attn_amp_grad takes)."""
+    leave in float32 and v in half (the mixed operands slow_attn_amp_grad takes).  linears=True: as install_train's; the bound forward picks linear_amp_grad where
+    autocast is enabled (or the input is half) and linear_grad where it is not - word_embed inside autocast(enabled=False), var.py:225-231."""
     if adaln:
         _install_adaln("install_train_amp", model)
     if qknorm:
         _install_qknorm("install_train_amp", model)
+    if linears:
+        _install_linears("install_train_amp", model)
     if isinstance(ffn, str):
         if ffn != "half":
             raise SdvarError(f"install_train_amp: ffn={ffn!r}; expected False, True or 'half'")
