@@ -627,6 +627,43 @@ int sdvar_op_qknorm_bwd(const void* qkv, int32_t dtype, const float* q_bias, con
                         const int64_t* grad_strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws /*workspace*/, int32_t B, int32_t L, int32_t H,
                         void* stream);
 
+/* ---- the conditioning linears under autograd: ada_lin = Sequential(SiLU, Linear(D, 6C)) of a block (basic_var.py:147, 156) and Sequential(SiLU, Linear(D, 2C)) of the
+ * head norm (:170, 173); sdvar_amd/seam.py ada_lin ------------------------------------------------------------------------------------------------------------------
+ * csrc/cond_train.hip.  Added without an ABI bump (purely additive).  A skinny product: M = the batch, all the bytes are in W.  No matrix cores, no operand planes, no
+ * cache: W is streamed once per direction and the SiLU is folded into the read of c.  Common to the entry points:
+ *   - c is (M, K) with leading dimension ldc ELEMENTS (ldc >= K, a multiple of 4 for fp32 and of 8 for half), c_dtype 0 fp32, 1 fp16, 2 bf16; w is (N, K) dense, w_dtype
+ *     0 fp32 or the half code; `dtype` is the ARITHMETIC code.  0: c and w fp32, true fp32 - every product enters the sum by one fp32 fmaf, in a fixed order.  1 / 2
+ *     (autocast's contract): c and w each fp32 or that half dtype; s is rounded once to the half dtype, an fp32 w is rounded to it as it is read (nearest even, the bits
+ *     of .to(dtype)), the sums are fp32, results are rounded once to half and an overflow is +-inf.
+ *   - s = silu(c) = x / (1 + expf(-x)) on the widened fp32 value (libm's expf, a correctly rounded division), the same code - the same bits - in both directions: -0
+ *     where expf overflows (x < -88.7), x where it underflows.
+ *   - 1 <= M <= 64, K % 8 == 0 with 8 <= K <= 4096, N % 8 == 0 with N >= 8, N * K < 2^31; every pointer 16-byte aligned.  Argument errors (shape, NULL, dtype codes,
+ *     alignment) are reported before any launch.  No allocation, no host synchronisation, no atomics: repeats are bit-identical.  Nothing is clamped.
+ * sdvar_op_cond_lin_fwd: y[m, n] = sum_k s[m, k] w[n, k] + b[n]; b fp32 (N) or NULL (nothing added); y (M, N) dense, fp32 for dtype 0, else half.  The sum over k of one
+ * output: lane l of a wave adds k = 4 l + 256 j + e in the order j = 0, 1, .., e = 0 .. 3, then six butterfly levels (xor 32, 16, .., 1) add the 64 lanes; the fp32 bias is
+ * added to that fp32 sum.  The order depends on K alone: a row's output bits do not depend on M, on N or on the other rows.  Up to 16 rows of c, W
+ * is read once.  Rows 16 .. 63 are further passes of 16 rows over the 16 rows of W a workgroup owns and has just read; that those reads are served by a cache and not by
+ * memory is assumed, not measured. */
+int sdvar_op_cond_lin_fwd(const void* c, int32_t c_dtype, int64_t ldc, const void* w, int32_t w_dtype, const float* b, void* y, int32_t dtype, int32_t M, int32_t N, int32_t K,
+                          void* stream);
+/* Bytes of the workspace of sdvar_op_cond_lin_bwd: ceil(N / 64) * M * K floats (64 = rows of W per workgroup, a compile-time constant); -1 on a bad shape.  Host only. */
+int64_t sdvar_op_cond_lin_bwd_ws_bytes(int32_t M, int32_t N, int32_t K);
+/* The backward of sdvar_op_cond_lin_fwd for the upstream gradient dy (M, N) dense, fp32 for dtype 0 and the half dtype otherwise.  Each output may be NULL (not computed),
+ * not all three:
+ *   dW[n, k] = sum_m dy[m, n] s[m, k]     m ascending, fp32; s as the forward has it (rounded in the half modes); (N, K) dense in w's own dtype: unrounded fp32 for fp32
+ *                                         master weights.
+ *   db[n]    = sum_m dy[m, n]             m ascending, fp32 (N).
+ *   dc[m, k] = (sum_n dy[m, n] w[n, k]) silu'(c[m, k])      w rounded as in the forward; (M, K) dense in c's dtype, rounded once.  The sum over n is fp32 in a fixed
+ *              order that depends on N alone: inside a workgroup's slab of 64 rows of W, wave v adds its rows 4 (v + 4 i) + r in the order i = 0 .. 3, r = 0 .. 3, the four
+ *              waves are added as ((v0 + v1) + v2) + v3 and the partial row goes to the workspace [slab][m][k]; a second kernel adds the slabs (slice t of 4: slabs t, t + 4,
+ *              .. in index order; the slices as ((t0 + t1) + t2) + t3), multiplies by silu'(x) = sg (1 + x (1 - sg)), sg = 1 / (1 + expf(-x)) - finite for every finite x, tending to 0 and 1 - and rounds.  The sum is NOT rounded to half
+ *              before the derivative (torch's autocast rounds dy W to half first): this side is the more accurate one.
+ * An output asked for alone has the bits it has in the full run.  W is read only when dc is asked for - once for M <= 32, once per 32 rows beyond (dc's partial sums
+ * then come from one launch per 32 rows, dW and db from a launch of their own); dW is written once.  ws: the workspace above, needed
+ * for dc only. */
+int sdvar_op_cond_lin_bwd(const void* dy, const void* c, int32_t c_dtype, int64_t ldc, const void* w, int32_t w_dtype, void* dc, void* dW, float* db, float* ws /*workspace*/,
+                          int32_t dtype, int32_t M, int32_t N, int32_t K, void* stream);
+
 /* ---- the optimizer step of the reference's trainer (AmpOptimizer.backward_clip_step, utils/amp_sc.py:39-75: unscale_, clip_grad_norm_, AdamW.step) -------------------
  * csrc/optim.hip; sdvar_amd/seam.py AdamW.  Added without an ABI bump (purely additive).  Two calls over a HOST list of n tensor descriptors: float32 param, grad,
  * exp_avg, exp_avg_sq (device, 4-byte aligned, numel elements each, dense), the tensor's float32 `step` counter (device) and its lr and weight_decay.  The descriptors

@@ -57,6 +57,10 @@ int qknorm_fwd(const void* qkv, int dt, const float* q_bias, const float* v_bias
 int qknorm_bwd(const void* qkv, int dt, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
                const long long* strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws, int B, int L, int H, hipStream_t stream);
 long long qknorm_bwd_ws_bytes(int B, int L, int H);
+int cond_lin_fwd(const void* c, int cdt, long long ldc, const void* w, int wdt, const float* b, void* y, int adt, int M, int N, int K, hipStream_t stream);
+int cond_lin_bwd(const void* dy, const void* c, int cdt, long long ldc, const void* w, int wdt, void* dc, void* dW, float* db, float* ws, int adt, int M, int N, int K,
+                 hipStream_t stream);
+long long cond_lin_bwd_ws_bytes(int M, int N, int K);
 int optim_grad_stats(const sdvar_optim_tensor_t* ts, int n, const float* grad_scale, const float* found_inf, double max_norm, double beta1, double beta2, void* ws,
                      unsigned long long ws_bytes, hipStream_t stream);
 int optim_adamw_step(const sdvar_optim_tensor_t* ts, int n, double beta1, double beta2, double eps, void* ws, unsigned long long ws_bytes, hipStream_t stream);
@@ -588,6 +592,17 @@ int64_t sdvar_op_qknorm_bwd_ws_bytes(int32_t B, int32_t L, int32_t H) { return q
 int sdvar_op_qknorm_bwd(const void* qkv, int32_t dtype, const float* q_bias, const float* scale_log, double max_log, const float* dq, const float* dk, const void* dv,
                         const int64_t* grad_strides, void* dqkv, float* dscale_log, float* dq_bias, float* dv_bias, float* ws, int32_t B, int32_t L, int32_t H, void* stream) {
     return qknorm_bwd(qkv, dtype, q_bias, scale_log, max_log, dq, dk, dv, (const long long*)grad_strides, dqkv, dscale_log, dq_bias, dv_bias, ws, B, L, H, (hipStream_t)stream);
+}
+
+// the conditioning linears Sequential(SiLU, Linear) under autograd (basic_var.py:147, 156, 170, 173; sdvar_amd/seam.py ada_lin): csrc/cond_train.hip
+int sdvar_op_cond_lin_fwd(const void* c, int32_t c_dtype, int64_t ldc, const void* w, int32_t w_dtype, const float* b, void* y, int32_t dtype, int32_t M, int32_t N, int32_t K,
+                          void* stream) {
+    return cond_lin_fwd(c, c_dtype, ldc, w, w_dtype, b, y, dtype, M, N, K, (hipStream_t)stream);
+}
+int64_t sdvar_op_cond_lin_bwd_ws_bytes(int32_t M, int32_t N, int32_t K) { return cond_lin_bwd_ws_bytes(M, N, K); }
+int sdvar_op_cond_lin_bwd(const void* dy, const void* c, int32_t c_dtype, int64_t ldc, const void* w, int32_t w_dtype, void* dc, void* dW, float* db, float* ws, int32_t dtype,
+                          int32_t M, int32_t N, int32_t K, void* stream) {
+    return cond_lin_bwd(dy, c, c_dtype, ldc, w, w_dtype, dc, dW, db, ws, dtype, M, N, K, (hipStream_t)stream);
 }
 
 // the trainer's optimizer step (utils/amp_sc.py:39-75; sdvar_amd/seam.py AdamW): csrc/optim.hip

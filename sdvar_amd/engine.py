@@ -153,6 +153,9 @@ _SIGNATURES = {
     "sdvar_op_qknorm_fwd": (_I, [_P, _I, _P, _P, _P, _D, _P, _P, _P, _I, _I, _I, _P]),
     "sdvar_op_qknorm_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
     "sdvar_op_qknorm_bwd": (_I, [_P, _I, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sdvar_op_cond_lin_fwd": (_I, [_P, _I, C.c_int64, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "sdvar_op_cond_lin_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
+    "sdvar_op_cond_lin_bwd": (_I, [_P, _P, _I, C.c_int64, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sdvar_optim_grad_stats": (_I, [_P, _I, _P, _P, _D, _D, _D, _P, _U64, _P]),
     "sdvar_optim_adamw_step": (_I, [_P, _I, _D, _D, _D, _P, _U64, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
@@ -974,6 +977,116 @@ def gate_add_bwd(g: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, row_scal
         _check(lib.sdvar_op_gate_add_bwd(_ptr(g), _ptr(y), TRAIN_DTYPES[y.dtype], C.c_void_p(gamma.data_ptr()), gdt, gbs, _ptr(rs), _ptr(dy), _ptr(dgamma), gamma_rows,
                                          _ptr(ws), B, L, Cc, _stream()))
     return dy, dgamma
+
+
+COND_MAX_M, COND_MAX_K = 64, 4096          # csrc/cond_train.hip: the batch rows and the in_features of a conditioning linear
+COND_SLAB = 64                              # rows of W per workgroup of its backward: fixes the workspace size and the order of dc's sum over n
+
+
+def cond_lin_shape_ok(M: int, N: int, K: int) -> bool:
+    """The shape limits of sdvar_op_cond_lin_fwd / _bwd."""
+    return 1 <= M <= COND_MAX_M and 8 <= K <= COND_MAX_K and K % 8 == 0 and N >= 8 and N % 8 == 0 and N * K < 2 ** 31
+
+
+def cond_rows_in_place(t: torch.Tensor) -> bool:
+    """The 16-byte rule of the (M, K) operand c: unit last stride, a 16-byte aligned base and, with more than one row, a row stride of at least K that is a multiple
+    of 16 bytes (4 float32 elements, 8 half ones)."""
+    per16 = 16 // t.element_size()
+    return t.stride(1) == 1 and t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or (t.stride(0) >= t.shape[1] and t.stride(0) % per16 == 0))
+
+
+def _cond_operands(who: str, c, weight, dtype):
+    """The checks common to cond_lin_fwd / cond_lin_bwd -> (M, N, K, c's code, ldc, w's code, arithmetic code).  Nothing here touches the library."""
+    for name, t in (("c", c), ("weight", weight)):
+        if not isinstance(t, torch.Tensor):
+            raise SdvarError(f"{who}: {name} is not a tensor")
+        if not t.is_cuda:
+            raise SdvarError(f"{who}: {name} is a CPU tensor; the kernels run on the GPU and there is no CPU path (move it with .cuda())")
+        if t.dtype not in TRAIN_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; it must be float32, float16 or bfloat16 (pass {name}.float())")
+        if t.dim() != 2:
+            raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}; expected a matrix ({'M, K' if name == 'c' else 'N, K'})")
+    if dtype not in TRAIN_DTYPES:
+        raise SdvarError(f"{who}: dtype {dtype} is not an arithmetic code (float32, float16 or bfloat16)")
+    for name, t in (("c", c), ("weight", weight)):
+        if t.dtype != torch.float32 and t.dtype != dtype:
+            raise SdvarError(f"{who}: {name} is {t.dtype} next to {dtype} arithmetic; every operand must be float32 or the arithmetic's own dtype (pass {name}.float())")
+    (M, K), N = c.shape, weight.shape[0]
+    if weight.shape[1] != K or weight.device != c.device:
+        raise SdvarError(f"{who}: weight has shape {tuple(weight.shape)} on {weight.device}; expected (N, {K}) on c's device {c.device}")
+    if not cond_lin_shape_ok(M, N, K):
+        raise SdvarError(f"{who}: M = {M}, N = {N}, K = {K} is outside the limits: 1 <= M <= {COND_MAX_M}, K a multiple of 8 in [8, {COND_MAX_K}], N a multiple of 8, "
+                         f"N * K < 2^31 (larger batches belong to the GEMM seam)")
+    if not cond_rows_in_place(c):
+        raise SdvarError(f"{who}: c with strides {tuple(c.stride())} at address % 16 == {c.data_ptr() % 16} breaks the 16-byte rule: unit last stride, base and row "
+                         f"stride multiples of 16 bytes (pass c.clone(memory_format=torch.contiguous_format))")
+    if not weight.is_contiguous() or weight.data_ptr() % 16:
+        raise SdvarError(f"{who}: weight with strides {tuple(weight.stride())} at address % 16 == {weight.data_ptr() % 16} is not dense and 16-byte aligned "
+                         f"(pass weight.clone(memory_format=torch.contiguous_format))")
+    return M, N, K, TRAIN_DTYPES[c.dtype], (c.stride(0) if M > 1 else K), TRAIN_DTYPES[weight.dtype], TRAIN_DTYPES[dtype]
+
+
+def _cond_dense(who: str, name: str, t, dtype, shape, dev):
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
+        raise SdvarError(f"{who}: {name} must be a tensor on c's GPU ({dev}); there is no CPU path")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.data_ptr() % 16:
+        raise SdvarError(f"{who}: {name} is {t.dtype} of shape {tuple(t.shape)}, strides {tuple(t.stride())}, address % 16 == {t.data_ptr() % 16}; expected a dense, "
+                         f"16-byte aligned {dtype} tensor of shape {tuple(shape)}")
+
+
+def _launch_ctx(dev):
+    return _on_device(dev) if dev.type == "cuda" else contextlib.nullcontext()
+
+
+def _addr(t: Optional[torch.Tensor]):
+    """The address of an operand whose layout has been checked, or of a tensor allocated here."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def cond_lin_bwd_ws_bytes(M: int, N: int, K: int) -> int:
+    """Bytes of sdvar_op_cond_lin_bwd's workspace: ceil(N / COND_SLAB) * M * K floats."""
+    n = int(load_library().sdvar_op_cond_lin_bwd_ws_bytes(M, N, K))
+    if n < 0:
+        raise SdvarError(f"cond_lin_bwd_ws_bytes: {_lib.sdvar_last_error().decode()}")
+    return n
+
+
+def cond_lin_fwd(c: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
+    """sdvar_op_cond_lin_fwd: silu(c) W^T + b for c (M, K) read in place under the 16-byte rule (cond_rows_in_place), weight (N, K) dense, bias (N,) float32 or None;
+    `dtype` is the arithmetic: float32 (float32 operands only) or a half dtype (each operand float32 or that dtype; autocast's contract).  Returns (M, N) in `dtype`.
+    No host synchronisation."""
+    who = "cond_lin_fwd"
+    M, N, K, cdt, ldc, wdt, adt = _cond_operands(who, c, weight, dtype)
+    _cond_dense(who, "bias", bias, torch.float32, (N,), c.device)
+    y = torch.empty(M, N, dtype=dtype, device=c.device)
+    lib = load_library()
+    with _launch_ctx(c.device):
+        _check(lib.sdvar_op_cond_lin_fwd(_addr(c), cdt, ldc, _addr(weight), wdt, _addr(bias), _addr(y), adt, M, N, K, _stream()))
+    return y
+
+
+def cond_lin_bwd(dy: torch.Tensor, c: torch.Tensor, weight: torch.Tensor, dtype: torch.dtype, need=(True, True, True)):
+    """sdvar_op_cond_lin_bwd: (dc (M, K) in c's dtype, dW (N, K) in the weight's dtype, db (N,) float32) for the upstream gradient dy (M, N) dense in `dtype`; an entry
+    of `need` that is False is not computed (None), and W is read only for dc.  The workspace is allocated here, for dc only.  No host synchronisation."""
+    who = "cond_lin_bwd"
+    M, N, K, cdt, ldc, wdt, adt = _cond_operands(who, c, weight, dtype)
+    _cond_dense(who, "dy", dy, dtype, (M, N), c.device)
+    if dy is None:
+        raise SdvarError(f"{who}: dy is None")
+    nc, nw, nb = (bool(n) for n in need)
+    if not (nc or nw or nb):
+        return None, None, None
+    dev = c.device
+    dc = torch.empty(M, K, dtype=c.dtype, device=dev) if nc else None
+    dw = torch.empty(N, K, dtype=weight.dtype, device=dev) if nw else None
+    db = torch.empty(N, dtype=torch.float32, device=dev) if nb else None
+    ws = torch.empty(cond_lin_bwd_ws_bytes(M, N, K) // 4, dtype=torch.float32, device=dev) if nc else None
+    lib = load_library()
+    with _launch_ctx(dev):
+        _check(lib.sdvar_op_cond_lin_bwd(_addr(dy), _addr(c), cdt, ldc, _addr(weight), wdt, _addr(dc), _addr(dw), _addr(db), _addr(ws), adt, M, N, K, _stream()))
+    return dc, dw, db
 
 
 QKNORM_MAX_H = 48

@@ -32,6 +32,11 @@ maintainer of the reference who wants the kernels without adopting the sampling 
     seam.install_train_amp(basic_var, model, ffn="half", adaln=True, qknorm=True, linears=True)   # linear_grad / linear_amp_grad, picked per call; seam.install_linears(model)
                                                                                      # alone for inference, seam.uninstall_linears(model) takes them off again
 
+    seam.install_train(basic_var, model, ffn=True, adaln=True, qknorm=True, linears=True, cond=True)    # ... and the conditioning path Sequential(SiLU, Linear) of every
+    seam.install_train_amp(basic_var, model, ffn="half", adaln=True, qknorm=True, linears=True, cond=True)   # block and of the head norm: ada_lin, a skinny kernel of its
+                                                                                     # own (batches of at most 64 rows); seam.install_cond(model) alone for inference,
+                                                                                     # seam.uninstall_cond(model) takes the bound forwards off again
+
     seam.install_optimizer(var_opt)         # the AmpOptimizer's AdamW (utils/amp_sc.py): unscale + clip_grad_norm_ + AdamW.step as two passes on HIP (seam.AdamW)
 
 Inference only, except slow_attn_grad / memory_efficient_attention_grad (fp32 operands; backward = sdvar_op_sdpa_bwd, no gradient for the mask, no double backward),
@@ -53,6 +58,10 @@ normalisation of q and k and the learnt per-head scale of q, one kernel per dire
 parameter saved; no double backward).  The float32 master bias is added in float32 to the GEMM's output, where autocast rounds acc + half(bias) to half inside the GEMM.
 linear / linear_grad / linear_amp / linear_amp_grad are F.linear on the operator GEMMs of the configured mode, resp. on the half matrix cores (csrc/linear_train.hip:
 sdvar_op_grad_operands / _h read dy once for both gradient GEMMs and db; the amp path saves the forward's half operand of x, 2 M K bytes; no double backward).
+ada_lin is Sequential(SiLU, Linear(D, 6C)) of a block and Sequential(SiLU, Linear(D, 2C)) of the head norm (basic_var.py:147, 156, 170, 173): M is the batch, all the
+bytes are in W, so it streams W once per direction in plain float32 vector code with the SiLU folded into the read of cond (csrc/cond_train.hip: sdvar_op_cond_lin_fwd /
+_bwd; cond and the weight saved; no operand planes, no weight-operand cache, independent of seam.configure; no double backward).  The float32 sum dy W enters the SiLU
+derivative unrounded, where autocast rounds it to half first.
 AdamW / install_optimizer are the optimizer step outside the blocks (utils/amp_sc.py:39-75, train.py:118): torch's decoupled AdamW on float32 parameters with the
 GradScaler's unscale, clip_grad_norm_'s global norm and the non-finite skip folded into two passes over the tensors (csrc/optim.hip: sdvar_optim_grad_stats,
 sdvar_optim_adamw_step); the norm stays on the device as `global_grad_norm`, the reference's late-clipping slot.  The gradients are read, never modified.
@@ -82,7 +91,7 @@ __all__ = ["configure", "slow_attn", "memory_efficient_attention", "flash_attn_f
            "fused_mlp_func_grad", "slow_attn_amp_grad", "memory_efficient_attention_amp_grad", "flash_attn_func_grad", "install_train_amp",
            "cross_entropy", "CrossEntropyLoss", "install_trainer", "fused_mlp_func_amp", "fused_mlp_func_amp_grad", "adaln_modulate", "gated_residual",
            "uninstall_adaln", "qk_l2norm", "install_qknorm", "uninstall_qknorm", "AdamW", "install_optimizer", "linear", "linear_grad", "linear_amp", "linear_amp_grad",
-           "install_linears", "uninstall_linears"]
+           "install_linears", "uninstall_linears", "ada_lin", "install_cond", "uninstall_cond", "cond_serves"]
 
 _gemm_mode = E.DEFAULT_GEMM_MODE
 # (data_ptr, _version, shape, strides) -> (mask, skip map).  The entry holds the mask itself: while it is cached its memory cannot be handed to another tensor, so
@@ -1514,7 +1523,7 @@ def install_amp(module, model=None, ffn_half: bool = False) -> None:
         _set_ffn_slots(module, model, fused_mlp_func_amp)
 
 
-def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False, linears: bool = False) -> None:
+def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False, linears: bool = False, cond: bool = False) -> None:
     """For TRAINING the reference in fp32 with the seam's operators: `module.slow_attn = slow_attn_grad`.  ffn=False (default): `module.fused_mlp_func = None` plus
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
     state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
@@ -1529,18 +1538,24 @@ def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qk
     them.  qknorm=False (default) binds nothing.  linears=True (needs the model) binds install_linears' forward on every nn.Linear whose in_features and out_features
     are multiples of 32: mat_qkv (reached through qknorm=True's forward only - the class forward calls F.linear itself, basic_var.py:93), proj, the Linear inside
     ada_lin, word_embed and head, and fc1 / fc2 where ffn=False leaves them to the module - linear_grad, forward and backward on HIP.  uninstall_linears(model)
-    removes them.  linears=False (default) binds nothing."""
+    removes them.  linears=False (default) binds nothing.  cond=True (needs the model) binds install_cond's forward on every Sequential(SiLU, Linear) - the ada_lin of
+    the blocks and of the head norm: ada_lin, one kernel forward and two backward for the batches cond_serves() accepts (at most 64 rows; above 16 rows at most 2^23
+    weights), float32 arithmetic here; with linears=True the Linear
+    inside keeps its bound forward for larger batches and its weight stays out of the weight-operand cache otherwise.  uninstall_cond(model) removes them.  cond=False
+    (default) binds nothing."""
     if adaln:
         _install_adaln("install_train", model)
     if qknorm:
         _install_qknorm("install_train", model)
     if linears:
         _install_linears("install_train", model)
+    if cond:
+        _install_cond("install_train", model)
     module.slow_attn = slow_attn_grad
     _set_ffn_slots(module, model, fused_mlp_func_grad if ffn else None)
 
 
-def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False, linears: bool = False) -> None:
+def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False, linears: bool = False, cond: bool = False) -> None:
     """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
     `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
     the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
@@ -1552,13 +1567,16 @@ def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm
     seam.memory_efficient_attention_amp_grad yourself before building the model if you want the BLHc route.  adaln=True: as install_train's; under autocast the
     modulation vectors and the branch outputs arrive in half and are read as they are.  qknorm=True: as install_train's; under autocast qkv arrives in half, q and k
     leave in float32 and v in half (the mixed operands slow_attn_amp_grad takes).  linears=True: as install_train's; the bound forward picks linear_amp_grad where
-    autocast is enabled (or the input is half) and linear_grad where it is not - word_embed inside autocast(enabled=False), var.py:225-231."""
+    autocast is enabled (or the input is half) and linear_grad where it is not - word_embed inside autocast(enabled=False), var.py:225-231.  cond=True: as
+    install_train's; under autocast ada_lin computes in the autocast dtype and returns half, also for the float32 cond the head norm is given (var.py:125, 248)."""
     if adaln:
         _install_adaln("install_train_amp", model)
     if qknorm:
         _install_qknorm("install_train_amp", model)
     if linears:
         _install_linears("install_train_amp", model)
+    if cond:
+        _install_cond("install_train_amp", model)
     if isinstance(ffn, str):
         if ffn != "half":
             raise SdvarError(f"install_train_amp: ffn={ffn!r}; expected False, True or 'half'")
@@ -1739,6 +1757,173 @@ def uninstall_adaln(model) -> None:
     for m in model.modules():
         f = m.__dict__.get("forward")
         if getattr(f, "__func__", None) in (_adaln_block_forward, _adaln_head_forward):
+            del m.forward
+
+
+# ------------------------------------------------------------------------------------------------------- the conditioning linears (csrc/cond_train.hip)
+def _ada_lin_check(who: str, cond, weight, bias):
+    """The argument checks of ada_lin -> (arithmetic dtype, M, N, K).  Nothing here touches the library."""
+    named = [("cond", cond), ("weight", weight)] + ([] if bias is None else [("bias", bias)])
+    for name, t in named:
+        _gpu_tensor(who, name, t)
+        if t.dtype == torch.float64:
+            raise SdvarError(f"{who}: {name} is torch.float64; only float32, float16 and bfloat16 operands are supported - pass {name}.float()")
+        if t.dtype != torch.float32 and t.dtype not in _HALF_DTYPES:
+            raise SdvarError(f"{who}: {name} is {t.dtype}; only float32, float16 and bfloat16 operands are supported")
+    halves = {t.dtype for _, t in named if t.dtype in _HALF_DTYPES}
+    if len(halves) > 1:
+        raise SdvarError(f"{who}: float16 mixed with bfloat16 ({', '.join(f'{n} is {t.dtype}' for n, t in named if t.dtype in _HALF_DTYPES)}); use one half dtype, or pass .float()")
+    dtype = cond.dtype if cond.dtype in _HALF_DTYPES else _autocast_gpu_dtype()
+    if dtype not in _HALF_DTYPES:
+        dtype = torch.float32
+    for name, t in named:
+        if t.dtype in _HALF_DTYPES and t.dtype != dtype:
+            if dtype == torch.float32:
+                raise SdvarError(f"{who}: {name} is {t.dtype} next to float32 arithmetic (cond is float32 and torch.autocast is not enabled for the GPU); call it under "
+                                 f"torch.autocast, pass a half cond, or pass {name}.float()")
+            raise SdvarError(f"{who}: float16 mixed with bfloat16: {name} is {t.dtype} but the half dtype of the call is {dtype}; use one half dtype, or pass {name}.float()")
+    if weight.dim() != 2 or cond.dim() < 1 or cond.shape[-1] != weight.shape[1]:
+        raise SdvarError(f"{who}: shapes do not chain: cond {tuple(cond.shape)}, weight {tuple(weight.shape)} (cond (..., K) with weight (N, K))")
+    N, K = weight.shape
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise SdvarError(f"{who}: bias has shape {tuple(bias.shape)}, expected ({N},)")
+    if any(t.device != cond.device for _, t in named):
+        raise SdvarError(f"{who}: operands live on different devices; move weight and bias to cond's device")
+    if K < 8 or K > E.COND_MAX_K or K % 8:
+        raise SdvarError(f"{who}: in_features {K} (the last dim of cond) must be a multiple of 8 in [8, {E.COND_MAX_K}]; use linear_grad / linear_amp_grad behind torch's SiLU")
+    if N < 8 or N % 8 or N * K >= 2 ** 31:
+        raise SdvarError(f"{who}: out_features {N} (weight.shape[0]) must be a multiple of 8, at least 8, with N * K below 2^31; use linear_grad / linear_amp_grad behind torch's SiLU")
+    M = cond.numel() // K
+    if M > E.COND_MAX_M:
+        raise SdvarError(f"{who}: cond has {M} rows; this kernel serves batches of at most {E.COND_MAX_M} rows - larger products belong to the GEMMs: use linear_grad / "
+                         f"linear_amp_grad behind torch's SiLU")
+    return dtype, M, N, K
+
+
+def _cond_rows(cond: torch.Tensor, K: int) -> torch.Tensor:
+    """cond (..., K) as the (M, K) matrix the kernels read: a view where its rows meet the 16-byte rule (unit last stride, aligned base, row stride a multiple of
+    16 bytes - a column slice of a wider buffer is read in place), else one dense copy."""
+    xr = cond.detach().reshape(-1, K)
+    return xr if E.cond_rows_in_place(xr) else xr.clone(memory_format=torch.contiguous_format)
+
+
+def _ada_lin_forward(cond, weight, bias, dtype, M: int, N: int, K: int):
+    if M == 0:
+        return torch.empty(tuple(cond.shape[:-1]) + (N,), dtype=dtype, device=cond.device)
+    y = E.cond_lin_fwd(_cond_rows(cond, K), _dense16(weight.detach()), _bias_f32(bias), dtype)
+    return y.view(tuple(cond.shape[:-1]) + (N,))
+
+
+class _AdaLinGrad(torch.autograd.Function):
+    """ada_lin with a HIP backward (sdvar_op_cond_lin_fwd / sdvar_op_cond_lin_bwd).  Saved: cond and the weight; s = silu(cond) is recomputed in the backward with the
+    forward's code."""
+
+    @staticmethod
+    def forward(ctx, cond, weight, bias, dtype, dims):
+        y = _ada_lin_forward(cond, weight, bias, dtype, *dims)
+        ctx.save_for_backward(cond, weight)
+        ctx.cl = (dtype, dims, None if bias is None else bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _no_double_backward("ada_lin")
+        nc, nw, nb = ctx.needs_input_grad[:3]
+        if not (nc or nw or nb):
+            return None, None, None, None, None
+        cond, weight = ctx.saved_tensors
+        dtype, (M, N, K), bdt = ctx.cl
+        if dy.dtype != dtype:
+            raise SdvarError(f"ada_lin: the gradient of the output is {dy.dtype} but the output is {dtype}; the backward reads dy in the output's dtype")
+        if M == 0:
+            z = lambda need, t, *shape: torch.zeros(*shape, dtype=t, device=dy.device) if need else None
+            return z(nc, cond.dtype, *cond.shape), z(nw, weight.dtype, N, K), z(nb, bdt, N), None, None
+        dy = _dense16(dy.reshape(M, N))             # a stride-0 expansion (y.sum().backward()) or a misaligned gradient: one fresh dense copy
+        dc, dw, db = E.cond_lin_bwd(dy, _cond_rows(cond, K), _dense16(weight.detach()), dtype, (nc, nw, nb))
+        return None if dc is None else dc.view(cond.shape), dw, None if db is None else db.to(bdt), None, None
+
+
+def ada_lin(cond, weight, bias=None):
+    """The conditioning path of a block and of the head norm, `Sequential(SiLU, Linear)(cond)` (basic_var.py:147, 156; :170, 173), as one kernel forward and two
+    backward: y = silu(cond) W^T + b.  cond (..., K), weight (N, K), bias (N,) on the GPU -> (..., N).  A skinny product - the rows are the batch, at most 64 - so
+    nothing of the GEMM seam is involved: no matrix cores, no operand planes, no weight-operand cache, and seam.configure(gemm_mode=...) has NO influence; W is
+    streamed once per direction and the SiLU is folded into the read of cond (x / (1 + expf(-x)), the same code in both directions).
+    Arithmetic (fused_mlp_func_amp's dtype rule): cond.dtype when cond is float16 / bfloat16, else the GPU's autocast dtype when autocast is enabled, else float32.
+    float32: float32 operands only, every product enters a float32 sum by one fmaf in an order that depends on K alone, result float32.  Half (autocast's contract):
+    s = silu(cond) is rounded once to the half dtype, a float32 weight is rounded to it as it is read (the bits of .to(dtype)), the sums are float32, the float32
+    bias is added to the float32 sum, the result is rounded once to half and an overflow is +-inf; a float32 cond under autocast - the head norm's case, var.py:125,
+    248 - gives a half result.  A row's bits do not depend on the batch size or on the other rows.
+    Differentiable: dW = dy^T s (float32 sums over the batch in row order, written in the weight's own dtype: unrounded float32 for float32 master weights),
+    db = sum_m dy, dcond = (dy W) silu'(cond) rounded once to cond's dtype.  THE ONE NUMERICAL DIFFERENCE from torch's autocast: there dy W is rounded to half before
+    the SiLU derivative multiplies it; here the float32 sum goes into the derivative unrounded - this side is the more accurate one.  Only the gradients autograd
+    asks for are computed (a frozen weight costs no dW, a cond without grad no read of W at all), each with the bits it has in the full run; no atomics, repeats are
+    bit-identical; neither direction synchronises with the host.  Saved for the backward: cond and weight, nothing else.  With grad mode off, or nothing requiring
+    grad, the same forward launch gives the same bits.  cond is read in place when its rows have unit last stride, a row stride that is a multiple of 4 elements
+    (8 when half) and a 16-byte aligned base, else copied once; a dy that is not dense or not 16-byte aligned is copied once.  M == 0 returns without a launch.
+    Limits: at most 64 rows (beyond: linear_grad / linear_amp_grad), K % 8 == 0 in [8, 4096], N % 8 == 0.  Above 16 rows the kernels are bound by arithmetic, not by
+    the bytes of W, and lose to the GEMM path on a large weight (d30's ada_lin at 32 rows): install_cond's forward does not hand such calls here (cond_serves).  CPU tensors, float64, float16 mixed with bfloat16, a half
+    weight next to float32 arithmetic and shapes that do not chain raise SdvarError - there is no fall-back to torch.  No double backward."""
+    who = "ada_lin"
+    dtype, M, N, K = _ada_lin_check(who, cond, weight, bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (cond, weight, bias)):
+        return _AdaLinGrad.apply(cond, weight, bias, dtype, (M, N, K))
+    return _ada_lin_forward(cond, weight, bias, dtype, M, N, K)
+
+
+# Where the bound forward hands a call to ada_lin.  Up to 16 rows the kernels stream W once and are bound by its bytes.  Beyond, the forward takes a pass over W per 16
+# rows and both directions are bound by their 2 M N K flop of plain fp32 fmaf: measured at 32 rows (tools/seam_cond_bench.py, DESIGN.md 4p) that still beats the GEMM path
+# at N K = 2.1 M - 7.4 M (d16's ada_lin and head norm, d30's head norm) and loses to it at 22 M (d30's ada_lin), so wide batches are served up to 2^23 weights only.
+COND_WIDE_ROWS = 16
+COND_WIDE_MAX_WEIGHTS = 1 << 23
+
+
+def cond_serves(rows: int, N: int, K: int) -> bool:
+    """Whether install_cond's bound forward calls ada_lin for a batch of `rows` rows into a Linear(K, N): at most 64 rows, and above 16 rows at most 2^23 weights."""
+    return rows <= E.COND_MAX_M and (rows <= COND_WIDE_ROWS or N * K <= COND_WIDE_MAX_WEIGHTS)
+
+
+def _cond_seq_forward(self, input):
+    """nn.Sequential(SiLU, Linear).forward on ada_lin; a batch that cond_serves() declines (more than 64 rows; more than 16 rows into a large Linear) takes the class's
+    own forward (and with it whatever is bound on the Linear)."""
+    lin = self[1]
+    if isinstance(input, torch.Tensor) and input.dim() >= 1 and input.shape[-1] > 0 and not cond_serves(input.numel() // input.shape[-1], lin.out_features, lin.in_features):
+        return torch.nn.Sequential.forward(self, input)
+    return ada_lin(input, lin.weight, lin.bias)
+
+
+def _cond_served(m) -> bool:
+    """Sequential(SiLU(inplace=False), Linear) with nn.Linear's own forward and sizes inside ada_lin's limits."""
+    if not isinstance(m, torch.nn.Sequential) or len(m) != 2:
+        return False
+    act, lin = m[0], m[1]
+    if type(act) is not torch.nn.SiLU or act.inplace or not isinstance(lin, torch.nn.Linear) or type(lin).forward is not torch.nn.Linear.forward:
+        return False
+    return E.cond_lin_shape_ok(1, lin.out_features, lin.in_features)
+
+
+def _install_cond(who: str, model) -> None:
+    if model is None:
+        raise SdvarError(f"{who}: cond=True binds a forward on the model's own Sequential(SiLU, Linear) modules; pass the model (model=None has nothing to bind)")
+    for m in model.modules():
+        if _cond_served(m):
+            m.forward = types.MethodType(_cond_seq_forward, m)
+
+
+def install_cond(model) -> None:
+    """Bind ada_lin on every nn.Sequential of `model` that is exactly (nn.SiLU(inplace=False), nn.Linear) with nn.Linear's own forward and sizes inside ada_lin's
+    limits: the ada_lin of every block and of the head norm.  A Sequential around a Linear SUBCLASS with a forward of its own (the reference's shared_ada_lin, whose
+    SharedAdaLin reshapes its result, var.py:16-19), an in-place SiLU or any other length is left alone.  The bound forward serves batches of at most 64 rows, and of
+    more than 16 rows only into a Linear of at most 2^23 weights (cond_serves: beyond that the kernels, bound by plain fp32 arithmetic, lose to the GEMM path - d30's
+    ada_lin at B = 32); any other batch goes through nn.Sequential.forward, the path it takes today (through linears=True's forward where that is installed).  A served weight never enters
+    the weight-operand cache.  uninstall_cond(model) removes the bound forwards."""
+    _install_cond("install_cond", model)
+
+
+def uninstall_cond(model) -> None:
+    """Delete the instance-level `forward` that install_cond / install_train(..., cond=True) / install_train_amp(..., cond=True) bound: nn.Sequential's own is back."""
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if getattr(f, "__func__", None) is _cond_seq_forward:
             del m.forward
 
 
