@@ -664,6 +664,51 @@ int64_t sdvar_op_cond_lin_bwd_ws_bytes(int32_t M, int32_t N, int32_t K);
 int sdvar_op_cond_lin_bwd(const void* dy, const void* c, int32_t c_dtype, int64_t ldc, const void* w, int32_t w_dtype, void* dc, void* dW, float* db, float* ws /*workspace*/,
                           int32_t dtype, int32_t M, int32_t N, int32_t K, void* stream);
 
+/* ---- the teacher-forcing input embedding under autograd (the prologue of VAR.forward, var.py:225-243) ----------------------------------------------------------------
+ * csrc/embed_train.hip; sdvar_amd/seam.py teacher_embed.  Added without an ABI bump (purely additive).  Plain fp32 vector code: no matrix cores, no operand planes, no
+ * atomics.  S stages, lvl[l] the stage of token l; L tokens, T of them used; first_l = patch_nums[0]^2; K = Cvae; NC1 = num_classes + 1 rows of class_emb.
+ *   - label (B) int32 (label_i64 = 0) or int64 (1); r (B) fp32 or NULL; lvl (L) int64; xv fp32 with dense rows of K values at a batch stride and a row stride in elements
+ *     (multiples of 4, row stride >= K), NULL allowed when T == first_l; class_emb (NC1, C), pos_start (first_l, C), w (C, K), bias (C), lvl_emb (S, C), pos_1LC (L, C):
+ *     dense fp32.
+ *   - C % 4 == 0 with 4 <= C <= 3072; K % 4 == 0 with 4 <= K <= 64; B >= 1, B * T <= 2^29; 1 <= first_l <= T <= L <= 2^19; every pointer 16-byte aligned.  Argument errors
+ *     are reported before any launch.  No allocation, no host synchronisation: repeats are bit-identical.  Nothing is clamped.
+ *   - j_b, the effective label of image b: (r != NULL && r[b] < (float)rate) ? NC1 - 1 : label[b], a float32 comparison.  A label outside [0, NC1) and a level lvl[l]
+ *     outside [0, S) are never used as an index: cond[b] and the rows l < first_l of such an image, and all B rows of such a token, are written as quiet NaN; in the
+ *     backward such an image adds nothing to dclass and such a token nothing to dlvl (the other gradients are the plain sums below over whatever g holds).
+ * sdvar_op_embed_fwd writes x (B, T, C) - fp32 for x_dtype 0, fp16 / bf16 for 1 / 2, rounded once (nearest even) from the fp32 value - and cond (B, C) fp32:
+ *     e[l, c]    = lvl_emb[lvl[l], c] + pos_1LC[l, c]
+ *     l <  first_l:  x[b, l, c] = (class_emb[j_b, c] + pos_start[l, c]) + e[l, c]
+ *     l >= first_l:  a = 0; for k = 0 .. K - 1: a = fmaf(xv[b, l - first_l, k], w[c, k], a);   x[b, l, c] = (a + bias[c]) + e[l, c]
+ *     cond[b, c] = class_emb[j_b, c]
+ * One launch.  The order of a sum depends on K alone: a row's bits do not depend on B or on the other rows. */
+int sdvar_op_embed_fwd(const void* label, int32_t label_i64, const float* r, double rate, const int64_t* lvl, const float* xv, int64_t xv_batch_stride, int64_t xv_row_stride,
+                       const float* class_emb, const float* pos_start, const float* w, const float* bias, const float* lvl_emb, const float* pos_1LC, void* x, int32_t x_dtype,
+                       float* cond, int32_t B, int32_t T, int32_t L, int32_t first_l, int32_t C, int32_t K, int32_t S, int32_t NC1, void* stream);
+/* Bytes of the workspace of sdvar_op_embed_bwd: (T * C + ceil(T / 8) * C * K) floats (8 = tokens per workgroup, a compile-time constant); -1 on a bad shape.  Host only. */
+int64_t sdvar_op_embed_bwd_ws_bytes(int32_t B, int32_t T, int32_t C, int32_t K);
+/* The backward of sdvar_op_embed_fwd for the upstream gradients g (B, T, C) of x, dense in x's dtype (g_dtype) and widened to fp32 as it is read, and gc (B, C) fp32 of
+ * cond; either may be NULL (no gradient reached that output).  label, r, rate, lvl, xv, w: the forward's, so that j_b is recomputed with the forward's code.  Each output
+ * may be NULL (not computed), not all of them; all are dense fp32:
+ *   dpos_1LC[l, c]   = p[l, c] = sum_b g[b, l, c]            b ascending from 0.0f, for l < T; exactly 0 for T <= l < L                      (L, C)
+ *   dpos_start[l, c] = p[l, c]                                for l < first_l                                                                  (first_l, C)
+ *   dlvl[s, c]       = sum of p[l, c] over l < T with lvl[l] = s: slice t of 4 adds the qualifying tokens among t, t + 4, .. in index order from 0.0f, the slices are added as
+ *                      ((t0 + t1) + t2) + t3; exactly 0 for a stage no token reaches                                                          (S, C)
+ *   dbias[c]         = sum of p[l, c] over first_l <= l < T, in dlvl's order                                                                  (C)
+ *   dclass[j, c]     = sum over the images with j_b = j, b ascending from 0.0f, of (gc[b, c] + t_b[c]), t_b[c] = sum_{l < first_l} g[b, l, c] with l ascending from 0.0f
+ *                      (gc NULL: t_b; g NULL: gc[b, c]); rows no image selects are 0; every row is written                                    (NC1, C)
+ *   dW[c, k]         = sum_b sum_{l >= first_l} g[b, l, c] xv[b, l - first_l, k], one fmaf per term: a workgroup owns the 8 tokens 8 i .. 8 i + 7, its wave v adds tokens
+ *                      8 i + v and 8 i + v + 4 in that order, b ascending inside a token; the four waves are added as ((v0 + v1) + v2) + v3 into the workspace; a second kernel
+ *                      adds the workgroups' partial matrices (slice t of 4: workgroups t, t + 4, .. in index order; the slices as ((t0 + t1) + t2) + t3)   (C, K)
+ *   dxv[b, t, k]     = sum_c g[b, t + first_l, c] w[c, k] for t < T - first_l, exactly 0 for the other rows: lane n of a wave adds c = 4 n + 256 i + e in the order i = 0, 1,
+ *                      .., e = 0 .. 3 with one fmaf per term, then six butterfly levels (xor 32, 16, .., 1) add the lanes                     (B, xv_rows, K), xv_rows >= T - first_l
+ * Every order depends on (B, T, first_l, C, K) and lvl alone.  An output asked for alone has the bits it has in the full run.  With T == first_l, dW and dbias are exact
+ * zeros; with g == NULL everything but dclass is.  An fp16 g arrives as it is: an inf propagates.  ws: the workspace above (needed with g for everything but dclass and
+ * dxv).  One launch over g, plus one each for dW, for dlvl / dbias, for dclass and for dxv. */
+int sdvar_op_embed_bwd(const void* g, int32_t g_dtype, const float* gc, const void* label, int32_t label_i64, const float* r, double rate, const int64_t* lvl, const float* xv,
+                       int64_t xv_batch_stride, int64_t xv_row_stride, const float* w, float* dpos_1LC, float* dpos_start, float* dlvl, float* dclass, float* dbias, float* dW,
+                       float* dxv, int32_t xv_rows, float* ws /*workspace*/, int32_t B, int32_t T, int32_t L, int32_t first_l, int32_t C, int32_t K, int32_t S, int32_t NC1,
+                       void* stream);
+
 /* ---- the optimizer step of the reference's trainer (AmpOptimizer.backward_clip_step, utils/amp_sc.py:39-75: unscale_, clip_grad_norm_, AdamW.step) -------------------
  * csrc/optim.hip; sdvar_amd/seam.py AdamW.  Added without an ABI bump (purely additive).  Two calls over a HOST list of n tensor descriptors: float32 param, grad,
  * exp_avg, exp_avg_sq (device, 4-byte aligned, numel elements each, dense), the tensor's float32 `step` counter (device) and its lr and weight_decay.  The descriptors

@@ -61,6 +61,13 @@ int cond_lin_fwd(const void* c, int cdt, long long ldc, const void* w, int wdt, 
 int cond_lin_bwd(const void* dy, const void* c, int cdt, long long ldc, const void* w, int wdt, void* dc, void* dW, float* db, float* ws, int adt, int M, int N, int K,
                  hipStream_t stream);
 long long cond_lin_bwd_ws_bytes(int M, int N, int K);
+int embed_fwd(const void* label, int i64, const float* r, double rate, const long long* lvl, const float* xv, long long xbs, long long xrs, const float* class_emb,
+              const float* pos_start, const float* W, const float* bias, const float* lvl_emb, const float* pos, void* x, int xdt, float* cond, int B, int T, int L, int first_l,
+              int C, int K, int S, int NC1, hipStream_t stream);
+int embed_bwd(const void* g, int gdt, const float* gc, const void* label, int i64, const float* r, double rate, const long long* lvl, const float* xv, long long xbs,
+              long long xrs, const float* W, float* dpos, float* dpos_start, float* dlvl, float* dclass, float* dbias, float* dW, float* dxv, int xv_rows, float* ws, int B, int T,
+              int L, int first_l, int C, int K, int S, int NC1, hipStream_t stream);
+long long embed_bwd_ws_bytes(int B, int T, int C, int K);
 int optim_grad_stats(const sdvar_optim_tensor_t* ts, int n, const float* grad_scale, const float* found_inf, double max_norm, double beta1, double beta2, void* ws,
                      unsigned long long ws_bytes, hipStream_t stream);
 int optim_adamw_step(const sdvar_optim_tensor_t* ts, int n, double beta1, double beta2, double eps, void* ws, unsigned long long ws_bytes, hipStream_t stream);
@@ -603,6 +610,21 @@ int64_t sdvar_op_cond_lin_bwd_ws_bytes(int32_t M, int32_t N, int32_t K) { return
 int sdvar_op_cond_lin_bwd(const void* dy, const void* c, int32_t c_dtype, int64_t ldc, const void* w, int32_t w_dtype, void* dc, void* dW, float* db, float* ws, int32_t dtype,
                           int32_t M, int32_t N, int32_t K, void* stream) {
     return cond_lin_bwd(dy, c, c_dtype, ldc, w, w_dtype, dc, dW, db, ws, dtype, M, N, K, (hipStream_t)stream);
+}
+
+// the teacher-forcing input embedding under autograd (var.py:225-243; sdvar_amd/seam.py teacher_embed): csrc/embed_train.hip
+int sdvar_op_embed_fwd(const void* label, int32_t label_i64, const float* r, double rate, const int64_t* lvl, const float* xv, int64_t xv_batch_stride, int64_t xv_row_stride,
+                       const float* class_emb, const float* pos_start, const float* w, const float* bias, const float* lvl_emb, const float* pos_1LC, void* x, int32_t x_dtype,
+                       float* cond, int32_t B, int32_t T, int32_t L, int32_t first_l, int32_t C, int32_t K, int32_t S, int32_t NC1, void* stream) {
+    return embed_fwd(label, label_i64, r, rate, (const long long*)lvl, xv, xv_batch_stride, xv_row_stride, class_emb, pos_start, w, bias, lvl_emb, pos_1LC, x, x_dtype, cond, B, T,
+                     L, first_l, C, K, S, NC1, (hipStream_t)stream);
+}
+int64_t sdvar_op_embed_bwd_ws_bytes(int32_t B, int32_t T, int32_t C, int32_t K) { return embed_bwd_ws_bytes(B, T, C, K); }
+int sdvar_op_embed_bwd(const void* g, int32_t g_dtype, const float* gc, const void* label, int32_t label_i64, const float* r, double rate, const int64_t* lvl, const float* xv,
+                       int64_t xv_batch_stride, int64_t xv_row_stride, const float* w, float* dpos_1LC, float* dpos_start, float* dlvl, float* dclass, float* dbias, float* dW,
+                       float* dxv, int32_t xv_rows, float* ws, int32_t B, int32_t T, int32_t L, int32_t first_l, int32_t C, int32_t K, int32_t S, int32_t NC1, void* stream) {
+    return embed_bwd(g, g_dtype, gc, label, label_i64, r, rate, (const long long*)lvl, xv, xv_batch_stride, xv_row_stride, w, dpos_1LC, dpos_start, dlvl, dclass, dbias, dW, dxv,
+                     xv_rows, ws, B, T, L, first_l, C, K, S, NC1, (hipStream_t)stream);
 }
 
 // the trainer's optimizer step (utils/amp_sc.py:39-75; sdvar_amd/seam.py AdamW): csrc/optim.hip

@@ -156,6 +156,9 @@ _SIGNATURES = {
     "sdvar_op_cond_lin_fwd": (_I, [_P, _I, C.c_int64, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "sdvar_op_cond_lin_bwd_ws_bytes": (C.c_int64, [_I, _I, _I]),
     "sdvar_op_cond_lin_bwd": (_I, [_P, _P, _I, C.c_int64, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sdvar_op_embed_fwd": (_I, [_P, _I, _P, _D, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sdvar_op_embed_bwd_ws_bytes": (C.c_int64, [_I, _I, _I, _I]),
+    "sdvar_op_embed_bwd": (_I, [_P, _I, _P, _P, _I, _P, _D, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sdvar_optim_grad_stats": (_I, [_P, _I, _P, _P, _D, _D, _D, _P, _U64, _P]),
     "sdvar_optim_adamw_step": (_I, [_P, _I, _D, _D, _D, _P, _U64, _P]),
     "sdvar_debug_set_gemm_cfg": (_I, [_I, _I]),
@@ -1087,6 +1090,177 @@ def cond_lin_bwd(dy: torch.Tensor, c: torch.Tensor, weight: torch.Tensor, dtype:
     with _launch_ctx(dev):
         _check(lib.sdvar_op_cond_lin_bwd(_addr(dy), _addr(c), cdt, ldc, _addr(weight), wdt, _addr(dc), _addr(dw), _addr(db), _addr(ws), adt, M, N, K, _stream()))
     return dc, dw, db
+
+
+EMBED_MAX_K = 64          # csrc/embed_train.hip: Cvae, the in_features of word_embed
+EMBED_TOK = 8             # tokens per workgroup of its backward: fixes the workspace size and the order of dW's sum
+
+
+def embed_xv_in_place(t: torch.Tensor) -> bool:
+    """The 16-byte rule of the (B, rows, K) operand xv: unit last stride, a 16-byte aligned base, row and batch strides that are multiples of 4 elements, rows that do
+    not overlap.  The reference's slice x_BLCv_wo_first_l[:, :ed - first_l] meets it."""
+    B, rows, K = t.shape
+    return (t.stride(2) == 1 and t.data_ptr() % 16 == 0 and (rows <= 1 or (t.stride(1) >= K and t.stride(1) % 4 == 0))
+            and (B <= 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= (rows - 1) * (t.stride(1) if rows > 1 else 0) + K)))
+
+
+def _embed_tensor(who: str, name: str, t, dtypes, hint: str):
+    if not isinstance(t, torch.Tensor):
+        raise SdvarError(f"{who}: {name} is not a tensor")
+    if not t.is_cuda:
+        raise SdvarError(f"{who}: {name} is a CPU tensor; the kernels run on the GPU and there is no CPU path (move it with .cuda())")
+    if t.dtype not in dtypes:
+        raise SdvarError(f"{who}: {name} is {t.dtype}; it must be {' or '.join(str(d) for d in dtypes)} ({hint})")
+
+
+def _embed_dense(who: str, name: str, t, shape, dev):
+    if tuple(t.shape) != tuple(shape):
+        raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}; expected {tuple(shape)}")
+    if t.device != dev:
+        raise SdvarError(f"{who}: {name} is on {t.device}; every operand must be on label's GPU ({dev})")
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise SdvarError(f"{who}: {name} with strides {tuple(t.stride())} at address % 16 == {t.data_ptr() % 16} is not dense and 16-byte aligned "
+                         f"(pass {name}.clone(memory_format=torch.contiguous_format))")
+
+
+def _embed_operands(who: str, label, xv, word_w, lvl_1L, drop, first_l: int, tokens: Optional[int]):
+    """The checks common to embed_fwd / embed_bwd -> (B, T, L, K, C, label's int64 flag, r, rate, xv's batch and row strides).  Nothing here touches the library."""
+    _embed_tensor(who, "label_B", label, (torch.int64, torch.int32), "pass label_B.long()")
+    _embed_tensor(who, "lvl_1L", lvl_1L, (torch.int64,), "pass lvl_1L.long()")
+    _embed_tensor(who, "word_w", word_w, (torch.float32,), "the parameters are float32 master weights: pass word_w.float()")
+    dev = label.device
+    if label.dim() != 1 or label.shape[0] < 1:
+        raise SdvarError(f"{who}: label_B has shape {tuple(label.shape)}; expected (B,) with B >= 1")
+    B = label.shape[0]
+    _embed_dense(who, "label_B", label, (B,), dev)
+    if lvl_1L.dim() not in (1, 2) or lvl_1L.numel() != lvl_1L.shape[-1] or lvl_1L.numel() < 1:
+        raise SdvarError(f"{who}: lvl_1L has shape {tuple(lvl_1L.shape)}; expected (1, L) or (L,)")
+    L = lvl_1L.shape[-1]
+    _embed_dense(who, "lvl_1L", lvl_1L, lvl_1L.shape, dev)
+    if word_w.dim() != 2:
+        raise SdvarError(f"{who}: word_w has shape {tuple(word_w.shape)}; expected (C, K)")
+    Cc, K = word_w.shape
+    if Cc < 4 or Cc > TRAIN_MAX_C or Cc % 4:
+        raise SdvarError(f"{who}: C = {Cc} (word_w.shape[0]) is outside the supported range: a multiple of 4 in [4, {TRAIN_MAX_C}] (pad the channel dimension)")
+    if K < 4 or K > EMBED_MAX_K or K % 4:
+        raise SdvarError(f"{who}: K = {K} (word_w.shape[1], Cvae) is outside the supported range: a multiple of 4 in [4, {EMBED_MAX_K}] (use linear_grad for a wider word_embed)")
+    _embed_dense(who, "word_w", word_w, (Cc, K), dev)
+    T = L if tokens is None else int(tokens)
+    if not (1 <= first_l <= T <= L):
+        raise SdvarError(f"{who}: tokens = {T} is outside [first_l, L] = [{first_l}, {L}] (pos_start has {first_l} rows, lvl_1L {L} entries)")
+    if B * T > 2 ** 29:
+        raise SdvarError(f"{who}: B * tokens = {B * T} is above 2^29 (split the batch)")
+    xbs = xrs = 0
+    if T > first_l:
+        _embed_tensor(who, "x_BLCv_wo_first_l", xv, (torch.float32,), "pass x_BLCv_wo_first_l.float()")
+        if xv.dim() != 3 or xv.shape[0] != B or xv.shape[2] != K or xv.shape[1] < T - first_l or xv.device != dev:
+            raise SdvarError(f"{who}: x_BLCv_wo_first_l has shape {tuple(xv.shape)} on {xv.device}; expected ({B}, >= {T - first_l}, {K}) on {dev}")
+        if not embed_xv_in_place(xv):
+            raise SdvarError(f"{who}: x_BLCv_wo_first_l with strides {tuple(xv.stride())} at address % 16 == {xv.data_ptr() % 16} breaks the 16-byte rule: unit last "
+                             f"stride, base, row and batch strides multiples of 16 bytes (pass x_BLCv_wo_first_l.clone(memory_format=torch.contiguous_format))")
+        xbs, xrs = (xv.stride(0) if B > 1 else 0), (xv.stride(1) if xv.shape[1] > 1 else K)
+    elif xv is not None and not isinstance(xv, torch.Tensor):
+        raise SdvarError(f"{who}: x_BLCv_wo_first_l is not a tensor")
+    r, rate = None, 0.0
+    if drop is not None:
+        if not isinstance(drop, (tuple, list)) or len(drop) != 2:
+            raise SdvarError(f"{who}: drop must be None or (r, rate): the float32 (B,) uniform draws and the drop rate")
+        r, rate = drop
+        _embed_tensor(who, "drop's r", r, (torch.float32,), "draw it with torch.rand(B, device=label_B.device)")
+        _embed_dense(who, "drop's r", r, (B,), dev)
+        rate = float(rate)
+    return B, T, L, K, Cc, (1 if label.dtype == torch.int64 else 0), r, rate, xbs, xrs
+
+
+def embed_bwd_ws_bytes(B: int, T: int, Cc: int, K: int) -> int:
+    """Bytes of sdvar_op_embed_bwd's workspace: T * C + ceil(T / EMBED_TOK) * C * K floats."""
+    n = int(load_library().sdvar_op_embed_bwd_ws_bytes(B, T, Cc, K))
+    if n < 0:
+        raise SdvarError(f"embed_bwd_ws_bytes: {_lib.sdvar_last_error().decode()}")
+    return n
+
+
+def embed_fwd(label, xv, class_emb, pos_start, word_w, word_b, lvl_emb, pos_1LC, lvl_1L, tokens: Optional[int] = None, drop=None, out_dtype: torch.dtype = torch.float32,
+              who: str = "embed_fwd"):
+    """sdvar_op_embed_fwd: (x (B, T, C) in out_dtype, cond (B, C) float32) from label (B,) int32 / int64, xv (B, >= T - first_l, K) float32 read in place under the 16-byte
+    rule (embed_xv_in_place; None allowed when T == first_l), the float32 parameters class_emb (NC1, C), pos_start (1, first_l, C), word_w (C, K), word_b (C,),
+    lvl_emb (S, C), pos_1LC (1, L, C) - dense, 16-byte aligned - and lvl_1L (1, L) int64.  T = tokens (None: L); drop = None or (r (B,) float32, rate).  No host
+    synchronisation.  `who` names the caller in the refusals."""
+    if out_dtype not in TRAIN_DTYPES:
+        raise SdvarError(f"{who}: out_dtype {out_dtype} is not float32, float16 or bfloat16")
+    for name, t in (("class_emb", class_emb), ("pos_start", pos_start), ("word_b", word_b), ("lvl_emb", lvl_emb), ("pos_1LC", pos_1LC)):
+        _embed_tensor(who, name, t, (torch.float32,), f"the parameters are float32 master weights: pass {name}.float()")
+    if pos_start.dim() not in (2, 3) or pos_start.numel() != pos_start.shape[-2] * pos_start.shape[-1]:
+        raise SdvarError(f"{who}: pos_start has shape {tuple(pos_start.shape)}; expected (1, first_l, C)")
+    first_l = pos_start.shape[-2]
+    B, T, L, K, Cc, i64, r, rate, xbs, xrs = _embed_operands(who, label, xv, word_w, lvl_1L, drop, first_l, tokens)
+    dev = label.device
+    if class_emb.dim() != 2 or lvl_emb.dim() != 2:
+        raise SdvarError(f"{who}: class_emb has shape {tuple(class_emb.shape)} and lvl_emb {tuple(lvl_emb.shape)}; expected (NC1, {Cc}) and (S, {Cc})")
+    NC1, S = class_emb.shape[0], lvl_emb.shape[0]
+    _embed_dense(who, "class_emb", class_emb, (NC1, Cc), dev)
+    _embed_dense(who, "pos_start", pos_start, tuple(pos_start.shape[:-2]) + (first_l, Cc), dev)
+    _embed_dense(who, "word_b", word_b, (Cc,), dev)
+    _embed_dense(who, "lvl_emb", lvl_emb, (S, Cc), dev)
+    _embed_dense(who, "pos_1LC", pos_1LC, ((1, L, Cc) if pos_1LC.dim() == 3 else (L, Cc)), dev)
+    x = torch.empty(B, T, Cc, dtype=out_dtype, device=dev)
+    cond = torch.empty(B, Cc, dtype=torch.float32, device=dev)
+    lib = load_library()
+    with _launch_ctx(dev):
+        _check(lib.sdvar_op_embed_fwd(_addr(label), i64, _addr(r), rate, _addr(lvl_1L), _addr(xv) if T > first_l else None, xbs, xrs, _addr(class_emb), _addr(pos_start),
+                                      _addr(word_w), _addr(word_b), _addr(lvl_emb), _addr(pos_1LC), _addr(x), TRAIN_DTYPES[out_dtype], _addr(cond), B, T, L, first_l, Cc, K, S,
+                                      NC1, _stream()))
+    return x, cond
+
+
+EMBED_GRADS = ("xv", "class_emb", "pos_start", "word_w", "word_b", "lvl_emb", "pos_1LC")
+
+
+def embed_bwd(g, gc, label, xv, word_w, lvl_1L, tokens: Optional[int], drop, first_l: int, NC1: int, S: int, need=(False, True, True, True, True, True, True),
+              who: str = "embed_bwd"):
+    """sdvar_op_embed_bwd: the gradients EMBED_GRADS = (dxv in xv's full shape, dclass (NC1, C), dpos_start (1, first_l, C), dW (C, K), dbias (C,), dlvl (S, C),
+    dpos_1LC (1, L, C)), all float32, for the upstream gradients g (B, T, C) of x - float32, float16 or bfloat16, dense - and gc (B, C) float32 of cond; either may be
+    None.  An entry of `need` that is False is not computed (None).  The workspace is allocated here.  No host synchronisation."""
+    B, T, L, K, Cc, i64, r, rate, xbs, xrs = _embed_operands(who, label, xv, word_w, lvl_1L, drop, first_l, tokens)
+    dev = label.device
+    gdt = 0
+    if g is not None:
+        _embed_tensor(who, "g", g, tuple(TRAIN_DTYPES), "the gradient of x in x's dtype")
+        _embed_dense(who, "g", g, (B, T, Cc), dev)
+        gdt = TRAIN_DTYPES[g.dtype]
+    if gc is not None:
+        _embed_tensor(who, "gc", gc, (torch.float32,), "the gradient of cond_BD is float32")
+        _embed_dense(who, "gc", gc, (B, Cc), dev)
+    need = tuple(bool(n) for n in need)
+    if len(need) != 7:
+        raise SdvarError(f"{who}: need has {len(need)} entries; expected one per gradient of {EMBED_GRADS}")
+    if not any(need):
+        return (None,) * 7
+    nx, ncls, nps, nw, nb, nl, npos = need
+    if nx and not isinstance(xv, torch.Tensor):
+        raise SdvarError(f"{who}: the gradient of x_BLCv_wo_first_l is asked for but it is None")
+    f = dict(dtype=torch.float32, device=dev)
+    if g is None and gc is None:          # nothing reached either output
+        shapes = (tuple(xv.shape) if nx else None, (NC1, Cc), (1, first_l, Cc), (Cc, K), (Cc,), (S, Cc), (1, L, Cc))
+        return tuple(torch.zeros(sh, **f) if n else None for n, sh in zip(need, shapes))
+    dxv = None
+    if nx:          # a row of xv the forward did not read has a zero gradient; without such rows in the call (T == first_l) nothing is launched for it
+        dxv, nx = (torch.empty(tuple(xv.shape), **f), True) if T > first_l else (torch.zeros(tuple(xv.shape), **f), False)
+    if not (nx or ncls or nps or nw or nb or nl or npos):
+        return dxv, None, None, None, None, None, None
+    dcls = torch.empty(NC1, Cc, **f) if ncls else None
+    dps = torch.empty(1, first_l, Cc, **f) if nps else None
+    dw = torch.empty(Cc, K, **f) if nw else None
+    db = torch.empty(Cc, **f) if nb else None
+    dl = torch.empty(S, Cc, **f) if nl else None
+    dpos = torch.empty(1, L, Cc, **f) if npos else None
+    ws = torch.empty(embed_bwd_ws_bytes(B, T, Cc, K) // 4, **f) if g is not None and (nps or nw or nb or nl or npos) else None
+    lib = load_library()
+    with _launch_ctx(dev):
+        _check(lib.sdvar_op_embed_bwd(_addr(g), gdt, _addr(gc), _addr(label), i64, _addr(r), rate, _addr(lvl_1L), _addr(xv) if T > first_l else None, xbs, xrs, _addr(word_w),
+                                      _addr(dpos), _addr(dps), _addr(dl), _addr(dcls), _addr(db), _addr(dw), _addr(dxv) if nx else None, (xv.shape[1] if nx else 0), _addr(ws), B, T, L, first_l,
+                                      Cc, K, S, NC1, _stream()))
+    return dxv, dcls, dps, dw, db, dl, dpos
 
 
 QKNORM_MAX_H = 48

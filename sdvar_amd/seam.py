@@ -1523,7 +1523,8 @@ def install_amp(module, model=None, ffn_half: bool = False) -> None:
         _set_ffn_slots(module, model, fused_mlp_func_amp)
 
 
-def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False, linears: bool = False, cond: bool = False) -> None:
+def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qknorm: bool = False, linears: bool = False, cond: bool = False,
+                  embed: bool = False) -> None:
     """For TRAINING the reference in fp32 with the seam's operators: `module.slow_attn = slow_attn_grad`.  ffn=False (default): `module.fused_mlp_func = None` plus
     `m.fused_mlp_func = None` on every FFN of `model` that captured one, so that the reference runs its own fc2(act(fc1(x))) under autograd (basic_var.py:52) - the
     state it is in without flash-attn installed.  ffn=True: those slots are set to fused_mlp_func_grad instead (HIP forward + backward for the FFN, out_features % 32
@@ -1542,7 +1543,8 @@ def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qk
     the blocks and of the head norm: ada_lin, one kernel forward and two backward for the batches cond_serves() accepts (at most 64 rows; above 16 rows at most 2^23
     weights), float32 arithmetic here; with linears=True the Linear
     inside keeps its bound forward for larger batches and its weight stays out of the weight-operand cache otherwise.  uninstall_cond(model) removes them.  cond=False
-    (default) binds nothing."""
+    (default) binds nothing.  embed=True (needs the model) binds install_embed's forward on the VAR-like module itself: var.py:217-259 with teacher_embed - one kernel -
+    for everything in front of the blocks; word_embed's module forward is no longer called.  uninstall_embed(model) removes it.  embed=False (default) binds nothing."""
     if adaln:
         _install_adaln("install_train", model)
     if qknorm:
@@ -1551,11 +1553,14 @@ def install_train(module, model=None, ffn: bool = False, adaln: bool = False, qk
         _install_linears("install_train", model)
     if cond:
         _install_cond("install_train", model)
+    if embed:
+        _install_embed("install_train", model)
     module.slow_attn = slow_attn_grad
     _set_ffn_slots(module, model, fused_mlp_func_grad if ffn else None)
 
 
-def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False, linears: bool = False, cond: bool = False) -> None:
+def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm: bool = False, linears: bool = False, cond: bool = False,
+                      embed: bool = False) -> None:
     """For TRAINING the reference under torch.autocast (utils/amp_sc.py; fp16 with a GradScaler, or bf16): `module.slow_attn = slow_attn_amp_grad` and
     `module.flash_attn_func = flash_attn_func_grad`, and with a model `using_flash = True` on every submodule that has the attribute (as enable_flash does), so that
     the unmasked calls on half operands take the flash slot.  The FFN slots are handled as install_train handles them: ffn=False (default) sets them to None and the
@@ -1568,7 +1573,9 @@ def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm
     modulation vectors and the branch outputs arrive in half and are read as they are.  qknorm=True: as install_train's; under autocast qkv arrives in half, q and k
     leave in float32 and v in half (the mixed operands slow_attn_amp_grad takes).  linears=True: as install_train's; the bound forward picks linear_amp_grad where
     autocast is enabled (or the input is half) and linear_grad where it is not - word_embed inside autocast(enabled=False), var.py:225-231.  cond=True: as
-    install_train's; under autocast ada_lin computes in the autocast dtype and returns half, also for the float32 cond the head norm is given (var.py:125, 248)."""
+    install_train's; under autocast ada_lin computes in the autocast dtype and returns half, also for the float32 cond the head norm is given (var.py:125, 248).  embed=True: as
+    install_train's; the blocks are handed x_BLC in float32 when adaln=True's forward is bound on them (the seam's float32 residual stream - the reference's own forward
+    casts x_BLC to half, which adaln_modulate refuses, so adaln=True needs embed=True to run the reference model under autocast) and in the autocast dtype otherwise."""
     if adaln:
         _install_adaln("install_train_amp", model)
     if qknorm:
@@ -1577,6 +1584,8 @@ def install_train_amp(module, model=None, ffn=False, adaln: bool = False, qknorm
         _install_linears("install_train_amp", model)
     if cond:
         _install_cond("install_train_amp", model)
+    if embed:
+        _install_embed("install_train_amp", model)
     if isinstance(ffn, str):
         if ffn != "half":
             raise SdvarError(f"install_train_amp: ffn={ffn!r}; expected False, True or 'half'")
@@ -1924,6 +1933,179 @@ def uninstall_cond(model) -> None:
     for m in model.modules():
         f = m.__dict__.get("forward")
         if getattr(f, "__func__", None) is _cond_seq_forward:
+            del m.forward
+
+
+# ------------------------------------------------------------------------------------------------------- the teacher-forcing input embedding (csrc/embed_train.hip)
+def _embed_xv(xv, rows=None):
+    """x_BLCv_wo_first_l as the kernels read it: of a half tensor the `rows` rows the call uses go through .float() (var.py:231 converts the slice, not the whole
+    tensor), a float32 one is read in place under engine.embed_xv_in_place - the reference's slice of a longer tensor meets it - and copied once otherwise (all
+    differentiable).  Anything else is left for the engine's checks to name."""
+    if not isinstance(xv, torch.Tensor) or not xv.is_cuda or xv.dim() != 3:
+        return xv
+    if xv.dtype in _HALF_DTYPES:
+        xv = (xv if rows is None or not 0 <= rows < xv.shape[1] else xv[:, :rows]).float()
+    if xv.dtype == torch.float32 and not E.embed_xv_in_place(xv):
+        xv = xv.clone(memory_format=torch.contiguous_format)
+    return xv
+
+
+def _embed_param(t):
+    """A parameter or index vector as the kernels read it: itself when dense and 16-byte aligned, else one dense copy (differentiable)."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and (not t.is_contiguous() or t.data_ptr() % 16):
+        return t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+class _EmbedGrad(torch.autograd.Function):
+    """teacher_embed with a HIP backward (sdvar_op_embed_fwd / sdvar_op_embed_bwd).  Saved: label, r, xv and the word-embedding weight - nothing of x's size; the
+    effective labels are recomputed in the backward with the forward's code.  lvl_1L, a buffer without gradient, is kept by reference."""
+
+    @staticmethod
+    def forward(ctx, label, xv, class_emb, pos_start, word_w, word_b, lvl_emb, pos_1LC, lvl_1L, tokens, r, rate, out_dtype):
+        drop = None if r is None else (r, rate)
+        x, cond = E.embed_fwd(label, xv, class_emb, pos_start, word_w, word_b, lvl_emb, pos_1LC, lvl_1L, tokens, drop, out_dtype, who="teacher_embed")
+        ctx.set_materialize_grads(False)
+        kept = [t for t in (label, r, xv, word_w) if t is not None]
+        ctx.save_for_backward(*kept)
+        ctx.emb = (r is not None, xv is not None, rate, tokens, lvl_1L, pos_start.shape[-2], class_emb.shape[0], lvl_emb.shape[0], out_dtype,
+                   tuple(pos_start.shape), tuple(pos_1LC.shape))
+        return x, cond
+
+    @staticmethod
+    def backward(ctx, g, gc):
+        who = "teacher_embed"
+        _no_double_backward(who)
+        need = tuple(ctx.needs_input_grad[1:8])
+        if not any(need) or (g is None and gc is None):
+            return (None,) * 13
+        has_r, has_xv, rate, tokens, lvl_1L, first_l, NC1, S, out_dtype, ps_shape, pos_shape = ctx.emb
+        saved = list(ctx.saved_tensors)
+        label = saved.pop(0)
+        r = saved.pop(0) if has_r else None
+        xv = saved.pop(0) if has_xv else None
+        word_w = saved.pop(0)
+        if g is not None:
+            if g.dtype != out_dtype:
+                raise SdvarError(f"{who}: the gradient of x_BLC is {g.dtype} but x_BLC is {out_dtype}; the backward reads it in the output's dtype")
+            g = _dense16(g)          # a stride-0 expansion (out.sum().backward()) or a misaligned gradient: one fresh dense copy
+        if gc is not None:
+            if gc.dtype != torch.float32:
+                raise SdvarError(f"{who}: the gradient of cond_BD is {gc.dtype} but cond_BD is float32")
+            gc = _dense16(gc)
+        dxv, dcls, dps, dw, db, dl, dpos = E.embed_bwd(g, gc, label, xv, word_w, lvl_1L, tokens, None if r is None else (r, rate), first_l, NC1, S, need, who=who)
+        return (None, dxv, dcls, None if dps is None else dps.view(ps_shape), dw, db, dl, None if dpos is None else dpos.view(pos_shape), None, None, None, None, None)
+
+
+def teacher_embed(label_B, x_BLCv_wo_first_l, class_emb, pos_start, word_w, word_b, lvl_emb, pos_1LC, lvl_1L, tokens=None, drop=None, out_dtype=torch.float32):
+    """The prologue of a teacher-forced training step (VAR.forward, var.py:225-243: condition drop, class_emb gather, expand + pos_start, word_embed, cat, lvl_embed
+    gather, + pos_1LC, the cast to the blocks' dtype) as ONE kernel forward - and one pass over the gradient plus a small launch per parameter group backward:
+        j_b = r[b] < rate ? num_classes : label_B[b]      (drop = (r, rate); drop=None: label_B[b]);       cond_BD[b] = class_emb[j_b]
+        x_BLC[b, l] = (class_emb[j_b] + pos_start[l]) + (lvl_emb[lvl_1L[l]] + pos_1LC[l])                   l <  first_l = pos_start.shape[-2]
+        x_BLC[b, l] = (word_w x_BLCv_wo_first_l[b, l - first_l] + word_b) + (lvl_emb[lvl_1L[l]] + pos_1LC[l])    first_l <= l < tokens (None: L)
+    -> (x_BLC (B, tokens, C) in out_dtype, cond_BD (B, C) float32).  label_B (B,) int64 or int32; x_BLCv_wo_first_l (B, >= tokens - first_l, K) float32 - a half tensor
+    goes through .float() as in the reference - read in place (the reference's slice of a longer tensor included) when its rows are 16-byte aligned, else copied once;
+    None allowed when tokens == first_l.  The parameters are the float32 master weights, dense: class_emb (num_classes + 1, C), pos_start (1, first_l, C), word_w (C, K),
+    word_b (C,), lvl_emb (S, C), pos_1LC (1, L, C); lvl_1L (1, L) int64, the model's buffer.  r (B,) float32 is compared with float32(rate), as torch compares a
+    float32 tensor with a Python number.  C % 4 == 0 in [4, 3072], K % 4 == 0 in [4, 64].
+    Bits: the rows l < first_l and cond_BD carry the bits of torch's own float32 expression.  The word rows add the K products in the order k = 0 .. K - 1 with one fmaf
+    each, where torch's GEMM picks its own order: THE numerical difference from the reference in float32.  out_dtype float16 / bfloat16 rounds the float32 value once:
+    the bits of x_BLC.to(out_dtype), without a cast launch.  A row's bits do not depend on B.
+    A label outside [0, num_classes] or a level outside [0, S) is never used as an index: the rows it would have fed are NaN and it adds nothing to the gradient of
+    class_emb / lvl_emb (torch raises a device-side assert instead).
+    Differentiable in both outputs: gradients of class_emb (rows no image selects are 0; repeated labels are added in image order), pos_start, word_w, word_b, lvl_emb
+    (stages beyond `tokens` are 0), pos_1LC (rows beyond `tokens` are 0) and, where it requires grad, x_BLCv_wo_first_l - all float32 sums in a fixed order that depends
+    on the shapes alone (include/sdvar_hip.h), no atomics, repeats bit-identical; only the gradients autograd asks for are computed, each with the bits it has in the
+    full run; a missing upstream gradient costs nothing; a half upstream gradient is widened as it is read and nothing is clamped (an inf reaches the GradScaler).
+    Saved for the backward: label_B, r, x_BLCv_wo_first_l and word_w - nothing of x_BLC's size.  There is no operand cache: an in-place update of a parameter is seen
+    by the next call.  Under torch.no_grad(), or when nothing requires grad, the same forward kernel runs: the same bits.  Neither direction synchronises with the
+    host.  CPU tensors, float64, half parameters, shapes that do not agree, C / K / tokens outside their limits raise SdvarError - there is no fall-back to torch.  No
+    double backward."""
+    who = "teacher_embed"
+    if out_dtype not in E.TRAIN_DTYPES:
+        raise SdvarError(f"{who}: out_dtype {out_dtype} is not float32, float16 or bfloat16")
+    r = rate = None
+    if drop is not None:
+        if not isinstance(drop, (tuple, list)) or len(drop) != 2:
+            raise SdvarError(f"{who}: drop must be None or (r, rate): the float32 (B,) uniform draws and the drop rate")
+        r, rate = drop
+        if isinstance(r, torch.Tensor):
+            if r.requires_grad and torch.is_grad_enabled():
+                raise SdvarError(f"{who}: drop's r requires grad; it carries no gradient (pass r.detach())")
+            r = _embed_param(r.detach())
+        rate = float(rate)
+        drop = (r, rate)
+    rows = None          # the rows of x_BLCv_wo_first_l this call reads, where the shapes say so (the engine names what is wrong with them otherwise)
+    if isinstance(pos_start, torch.Tensor) and pos_start.dim() >= 2 and isinstance(lvl_1L, torch.Tensor) and lvl_1L.dim() >= 1:
+        rows = (lvl_1L.shape[-1] if tokens is None else int(tokens)) - pos_start.shape[-2]
+    xv = _embed_xv(x_BLCv_wo_first_l, rows)
+    label_B, lvl_1L = _embed_param(label_B), _embed_param(lvl_1L)
+    params = [_embed_param(t) for t in (class_emb, pos_start, word_w, word_b, lvl_emb, pos_1LC)]
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in [xv] + params):
+        return _EmbedGrad.apply(label_B, xv, *params, lvl_1L, tokens, r, rate, out_dtype)
+    d = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    return E.embed_fwd(d(label_B), d(xv), *(d(t) for t in params), d(lvl_1L), tokens, drop, out_dtype, who=who)
+
+
+_EMBED_NEEDS = ("class_emb", "pos_start", "word_embed", "lvl_embed", "pos_1LC", "lvl_1L", "blocks", "get_logits", "begin_ends", "prog_si", "cond_drop_rate")
+
+
+def _embed_var_forward(self, label_B, x_BLCv_wo_first_l):
+    """VAR.forward (var.py:217-259) with teacher_embed in front of the blocks.  The uniform draws of the condition drop are taken once per call, at rate 0 too, so the
+    generator moves as in the reference.  The blocks' dtype is the GPU's autocast dtype (float32 without autocast) - no matmul probe.  The residual stream leaves the
+    kernel in float32 when blocks[0] carries adaln=True's bound forward (the seam keeps a float32 residual stream: adaln_modulate and gated_residual take and return
+    float32), else in the blocks' dtype, as the reference casts it."""
+    L = self.lvl_1L.shape[-1]
+    ed = self.begin_ends[self.prog_si][1] if self.prog_si >= 0 else L
+    B = x_BLCv_wo_first_l.shape[0]
+    r = torch.rand(B, device=label_B.device)
+    main_type = _autocast_gpu_dtype()
+    if main_type not in _HALF_DTYPES:
+        main_type = torch.float32
+    fp32_stream = getattr(self.blocks[0].__dict__.get("forward"), "__func__", None) is _adaln_block_forward
+    we = self.word_embed
+    x_BLC, cond_BD = teacher_embed(label_B, x_BLCv_wo_first_l, self.class_emb.weight, self.pos_start, we.weight, we.bias, self.lvl_embed.weight, self.pos_1LC, self.lvl_1L,
+                                   tokens=ed, drop=(r, self.cond_drop_rate), out_dtype=torch.float32 if fp32_stream else main_type)
+    attn_bias = self.attn_bias_for_masking[:, :, :ed, :ed].to(dtype=main_type)
+    cond_BD_or_gss = self.shared_ada_lin(cond_BD).to(dtype=main_type)
+    for blk in self.blocks:
+        x_BLC = blk(x=x_BLC, cond_BD=cond_BD_or_gss, attn_bias=attn_bias)
+    # Stage 0 (prog_si == 0) has no word rows, and the reference keeps word_embed in the graph with two `* 0` terms on the logits (var.py:250-258; DDP needs every
+    # parameter to receive a gradient).  Nothing of the kind is needed here: word_embed's weight and bias are operands of teacher_embed at every stage, and with
+    # tokens == first_l its backward returns exact zeros for them, not None.
+    return self.get_logits(x_BLC.float(), cond_BD)
+
+
+def _install_embed(who: str, model) -> None:
+    if model is None:
+        raise SdvarError(f"{who}: embed=True binds a forward on the model itself; pass the model (model=None has nothing to bind)")
+    hosts = [m for m in model.modules() if all(hasattr(m, n) for n in _EMBED_NEEDS)]
+    if not hosts:
+        missing = [n for n in _EMBED_NEEDS if not hasattr(model, n)]
+        raise SdvarError(f"{who}: embed=True found no VAR-like module: {type(model).__name__} has no {' / '.join(missing)} (needed: {', '.join(_EMBED_NEEDS)})")
+    for m in hosts:
+        extra = [n for n in ("attn_bias_for_masking", "shared_ada_lin") if not hasattr(m, n)]
+        we = m.word_embed
+        if extra or not isinstance(getattr(we, "weight", None), torch.Tensor) or not isinstance(getattr(we, "bias", None), torch.Tensor):
+            what = " / ".join(extra) if extra else "word_embed.weight / word_embed.bias (a Linear with a bias)"
+            raise SdvarError(f"{who}: {type(m).__name__} has no {what}; embed=True knows VAR-like models only")
+        m.forward = types.MethodType(_embed_var_forward, m)
+
+
+def install_embed(model) -> None:
+    """Bind an instance-level `forward(label_B, x_BLCv_wo_first_l)` on the module of `model` that has class_emb, pos_start, word_embed, lvl_embed, pos_1LC, lvl_1L,
+    blocks, get_logits, begin_ends, prog_si and cond_drop_rate (the reference's VAR): var.py:217-259 with teacher_embed for everything in front of the blocks.
+    word_embed's module forward is not called on this path, so with linears=True its weight never enters the weight-operand cache.  Under autocast the blocks are handed
+    a float32 x_BLC when adaln=True's forward is bound on them - which is what lets install_train_amp(..., adaln=True) run the reference model: its own forward casts
+    x_BLC to half, which adaln_modulate refuses - and the autocast dtype otherwise.  A model without one of the attributes raises.  uninstall_embed(model) removes it."""
+    _install_embed("install_embed", model)
+
+
+def uninstall_embed(model) -> None:
+    """Delete the instance-level `forward` that install_embed / install_train(..., embed=True) / install_train_amp(..., embed=True) bound: the class's own is back."""
+    for m in model.modules():
+        f = m.__dict__.get("forward")
+        if getattr(f, "__func__", None) is _embed_var_forward:
             del m.forward
 
 
