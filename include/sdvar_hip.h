@@ -440,6 +440,10 @@ int sdvar_debug_get_gemm_cfg(int32_t* out4);
 /* test aid: out1[0] = 1 if the LAST convolution launch (sdvar_op_conv_planes / _ex, the decoder's convolutions) of this host thread took the tap-reuse K loop
  * (f16x2 planes, "conv_pp" 2, "conv_tap_reuse" 1, 3x3 or fused up-sampling taps, no split-K, H W % 256 == 0, W % 256 == 0 or 256 % W == 0 with W >= 64), else 0. */
 int sdvar_debug_get_conv_cfg(int32_t* out1);
+/* test aid: out4 = what the LAST convolution launch of this host thread ran: {kernel: 0 bf16x3 | 1 f16x2 | 2 f16x2 tap-reuse; the "conv_pp" loop actually used (2 falls
+ * back to 1 when N % 4 != 0; 0 for bf16x3, which has one loop); the K split actually used (1 = none; a forced split is rounded to the number of non-empty slices);
+ * 1 if the GroupNorm statistics were fused into the epilogue}.  All four are -1 before the first launch.  Thread-local, like sdvar_debug_get_conv_cfg. */
+int sdvar_debug_get_conv_plan(int32_t* out4);
 /* The GEMM planner (csrc/gemm_plan.h) on its own: what a GEMM of this shape would launch.  Pure host code - no HIP call, no GPU needed; a pure function of the
  * arguments, the switches above and the SDVAR_GEMM_* environment.  mode: 0 f32, 1 bf16x3, 2 f16x2.  flags: bit 0 = the caller defers the K-slice sum to its
  * consumer kernel, bit 1 = the call offers a QKV finish for the epilogue (sdvar_stage_forward's QKV launch), bit 2 = every output pointer and leading dimension

@@ -101,6 +101,7 @@ int weight_scale_f16(const float* w, size_t n, float* sc, hipStream_t stream);
 void debug_set_gemm_stamps(unsigned long long* p);
 void debug_get_gemm_cfg_h(int* out);
 int debug_get_conv_tap_reuse();
+void debug_get_conv_plan(int* out4);
 int planes_guard(const uint16_t* h_plane, size_t n, unsigned long long* cnt, hipStream_t stream);
 int cfg_sample(const float* logits, int B, int l, int V, float one_plus_t, float t, int top_k, int use_top_p, float top_p_thr, const float* q, uint64_t seed,
                uint32_t draw, uint32_t image_offset, long long* ids, int ids_stride, float* dbg_masked, hipStream_t stream);
@@ -1143,6 +1144,13 @@ int sdvar_debug_get_gemm_cfg(int32_t* out4) {
 int sdvar_debug_get_conv_cfg(int32_t* out1) {
     SDVAR_CHECK_ARG(out1, "debug_get_conv_cfg: null");
     out1[0] = debug_get_conv_tap_reuse();
+    return SDVAR_OK;
+}
+
+int sdvar_debug_get_conv_plan(int32_t* out4) {
+    SDVAR_CHECK_ARG(out4, "debug_get_conv_plan: null");
+    int v[4]; debug_get_conv_plan(v);
+    for (int i = 0; i < 4; ++i) out4[i] = v[i];
     return SDVAR_OK;
 }
 

@@ -875,6 +875,8 @@ int upconv_weights(const float* w, float* weff, int Cout, int Cin, hipStream_t s
 
 static thread_local int g_conv_last_reuse = 0;      // 1: the last conv_planes launch of this host thread took conv_f16x2_reuse_kernel (test aid)
 int debug_get_conv_tap_reuse() { return g_conv_last_reuse; }
+static thread_local int g_conv_last_plan[4] = {-1, -1, -1, -1};      // {kernel 0 bf16x3 | 1 f16x2 | 2 f16x2 tap-reuse, conv_pp used, K split used, statistics fused} of that launch (test aid)
+void debug_get_conv_plan(int* out4) { for (int i = 0; i < 4; ++i) out4[i] = g_conv_last_plan[i]; }
 
 // split heuristic: fill the 256 CUs (one resident workgroup each) without leaving a mostly empty last round
 static int conv_choose_split(int M, int N, int nkt, size_t ws_floats, double kstep_cycles) {
@@ -938,11 +940,15 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
     const bool reuse = F16 && pp == 2 && variant(VAR_CONV_TAP_REUSE) == 1 && (taps == 9 || taps == 4) && split == 1 && (H * Wd) % CBM == 0 &&
                        (Wd % CBM == 0 || (CBM % Wd == 0 && Wd >= 64)) && x_rows * 64 <= 0xFFFFFFFFull;
     g_conv_last_reuse = reuse ? 1 : 0;
+    g_conv_last_plan[0] = reuse ? 2 : F16 ? 1 : 0;
+    g_conv_last_plan[1] = F16 ? pp : 0;
+    g_conv_last_plan[2] = split;
+    g_conv_last_plan[3] = 0;
     static LdsOptIn opt_in, opt_in_h, opt_in_r;
     if (reuse) {
         SDVAR_LDS_OPT_IN(opt_in_r, CLDS_R, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 3>, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3>,
                          (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 2>);
-        if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; }
+        if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; g_conv_last_plan[3] = 1; }
         if (taps == 4) hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS, 2>), dim3(tiles, 4), dim3(512), CLDS_R, stream, a);
         else if (res) hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3>), dim3(tiles), dim3(512), CLDS_R, stream, a);
         else hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS, 3>), dim3(tiles), dim3(512), CLDS_R, stream, a);
@@ -967,7 +973,7 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
         SDVAR_LAUNCH_CHECK();
         return SDVAR_OK;
     }
-    if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0 && (H * Wd) % CBM == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; }
+    if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0 && (H * Wd) % CBM == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; g_conv_last_plan[3] = 1; }
     if (F16) {
         if (res && pp == 2) hipLaunchKernelGGL((conv_f16x2_kernel<CEPI_BIAS_RES, 2>), dim3(tiles), dim3(512), lds, stream, a);
         else if (res && pp) hipLaunchKernelGGL((conv_f16x2_kernel<CEPI_BIAS_RES, 1>), dim3(tiles), dim3(512), lds, stream, a);

@@ -169,6 +169,7 @@ _SIGNATURES = {
     "sdvar_debug_set_variant": (_I, [C.c_char_p, _I]),
     "sdvar_debug_get_gemm_cfg": (_I, [C.POINTER(_I)]),
     "sdvar_debug_get_conv_cfg": (_I, [C.POINTER(_I)]),
+    "sdvar_debug_get_conv_plan": (_I, [C.POINTER(_I)]),
     "sdvar_debug_plan_gemm": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sdvar_debug_set_f16x2_guard": (_I, [_I]),
     "sdvar_debug_get_f16x2_guard": (_I, [C.POINTER(_U64), _I]),
