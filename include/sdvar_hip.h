@@ -105,6 +105,14 @@ int sdvar_embed_teacher(sdvar_model_t* m, const float* xv, float* x, void* strea
  * with the mask rows of var.py:108-113 derived from the stage table).  x (R, lsum, C) is the input and is CLOBBERED
  * (it is the residual stream); logits (R, lsum, V).  Requires kv_len == begin(s0); appends lsum keys. */
 int sdvar_stage_forward(sdvar_model_t* m, float* x, int32_t s0, int32_t n_stages, float* logits, void* stream);
+/* Stage 0 of the current call from the model's OWN first-token map (var.py:162-183: class_emb[label | uncond] + pos_start + lvl_pos[0]) - no x argument;
+ * logits (R, 1, V).  Requires kv_len == 0 at origin 0 and a one-token first stage; appends one key.  The result equals
+ * sdvar_model_place_first + sdvar_stage_forward(x, 0, 1) bit for bit.  After sdvar_model_begin (labels) stage 0 is a pure function of (weights, class): the
+ * first such call after a bind computes it for every class - by the ordinary launch sequence, in batches of the call's R rows - into a per-class table
+ * (logits row + the bytes left at cache position 0 of every block's K and V), and this call then is ONE launch that copies the R rows out.  The table is
+ * rebuilt when R, the weights or a kernel-variant switch change; it is not used after _begin_cond / _begin_rows, for shared_aln models, with the f16x2 guard
+ * on, with "stage0_table" 0 (SDVAR_STAGE0_TABLE=0) or above "stage0_table_mb" MiB (SDVAR_STAGE0_TABLE_MB, default 1024): then the pass is computed. */
+int sdvar_stage_first(sdvar_model_t* m, float* logits, void* stream);
 /* The same pass under an EXPLICIT additive attention mask instead of the block-causal rows: bias (lsum, kv_len + lsum) fp32, 0 or -inf, the
  * reference's (1, 1, l, K) attn_bias.  For the ablation masks of the hand-off sampler (var.py:557-578 attn_bias_for_sdmasking /
  * attn_bias_for_block, applied at var.py:777-804). */
@@ -431,7 +439,9 @@ int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const 
  * name: "gemm_h4_var" 0..3, "gemm_h2_stages" 2..6, "gemm_small_pp" 0..2, "attn_pp_sched" 0..3, "conv_pp" 0..2, "conv_tap_reuse" 0..1 (SDVAR_CONV_TAP_REUSE, read per call like
  * SDVAR_CONV_PP: 1 = the f16x2 decoder convolution stages X once per row of taps where the shape allows it, 0 = never); value < 0 restores the environment / default.
  * A lookup in the library's one table of process-wide switches (csrc/gemm_plan.h), which sdvar_debug_set_rowblk ("rowblk" 0..2), sdvar_debug_set_qkv_fuse
- * ("qkv_fuse" 0..1) and sdvar_debug_set_gemm_cfg write too; "gemm_v2" 0..1 (bf16x3: the 128-row tile on the LDS-DMA kernel, default 1) has no other setter. */
+ * ("qkv_fuse" 0..1) and sdvar_debug_set_gemm_cfg write too; "gemm_v2" 0..1 (bf16x3: the 128-row tile on the LDS-DMA kernel, default 1) has no other setter.
+ * "stage0_table" 0..1 (SDVAR_STAGE0_TABLE) and "stage0_table_mb" 0..2^20 (SDVAR_STAGE0_TABLE_MB, default 1024): sdvar_stage_first's per-class table and its size cap.
+ * Every one of these setters except the two stage-0 ones moves an epoch that makes the next sdvar_model_begin rebuild that table. */
 int sdvar_debug_set_variant(const char* name, int32_t value);
 /* test aid: out4 = {kernel code (as sdvar_debug_plan_gemm; 17 = row-block launch) of the LAST f16x2 GEMM call of this host thread, its K split, number of launches that took the hybrid tail
  * split since the last read, number of QKV launches that finished q and k in their epilogue since the last read}; reading resets the two counters.

@@ -32,7 +32,10 @@ int gemm_f16x2_rowblk(const float* x, int ldx, const float* scale, const float* 
 int silu_rows(const float* x, float* y, int n, hipStream_t stream);
 int add_row_vector(const float* src, const float* vec, float* out, int rows, int cols, hipStream_t stream);
 int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int R, int nlab, int num_classes,
-               hipStream_t stream);
+               int* row_cls, hipStream_t stream);
+struct Stage0Geom { int n16, np; size_t kes, ves, plane, head; };
+int stage0_rows(uint16_t* tab, size_t row16, const int* cls, uint16_t* const* kv, float* logits, int R, int V, int depth, int H, const Stage0Geom& g, int nvalid,
+                int to_table, hipStream_t stream);
 int prologue(const long long* labels, const float* cond_in, const float* class_emb, const float* pos_start, const float* lvl_pos, float* cond, float* x0, int R, int nlab, int C, int num_classes, hipStream_t stream);
 int build_lvl_pos(const float* lvl_embed, const float* pos, const int* stage_of_tok, float* out, int L, int C, hipStream_t stream);
 int embed_next(const float* nxt, const float* Ww, const float* bw, const float* lvl_pos, float* x, int B, int l, int C, int t0, int ltot, int tok_off, int pair, hipStream_t stream);
@@ -100,6 +103,8 @@ int split_planes_f16(const float* x, uint16_t* planes, int rows, int cols, size_
 int weight_scale_f16(const float* w, size_t n, float* sc, hipStream_t stream);
 void debug_set_gemm_stamps(unsigned long long* p);
 void debug_get_gemm_cfg_h(int* out);
+void debug_peek_gemm_cfg_h(int* out6);
+void debug_restore_gemm_cfg_h(const int* in6);
 int debug_get_conv_tap_reuse();
 void debug_get_conv_plan(int* out4);
 int planes_guard(const uint16_t* h_plane, size_t n, unsigned long long* cnt, hipStream_t stream);
@@ -202,6 +207,24 @@ struct sdvar_model {
     // gathers its 2B rows.  0.4 GB for d16, 1.4 GB for d30 - HBM the card has.  Not for shared_aln models (one GEMM per call there) nor for sdvar_model_begin_cond.
     float* ada_tab = nullptr;
     bool ada_tab_ready = false;
+    // owned (num_classes + 1) rows of s0_row16 2-byte units: stage 0 of EVERY class - its logits row and the bytes it leaves at cache position 0 of every block's K
+    // and V, in the bound cache format (elementwise.hip stage0_rows).  At l = 1 LayerNorm, the GEMMs and the one-key attention are row-wise, so stage 0 of a
+    // label-conditioned row depends on (weights, class) only; it used to run in full three times per speculative step (98 launches / 0.51 ms for d12, 130 / 0.78 ms
+    // for d16).  Built by the first sdvar_model_begin after a bind (stage0_build below) with the ordinary launch sequence in batches of that call's R rows - the same
+    // M, hence the same kernels, K splits and bits as the computed pass - and rebuilt when R or the variant epoch (gemm_plan.h) has moved.  sdvar_stage_first
+    // copies a call's R rows out in one launch.  147 KB per class for d16 with the f16x2 planes cache (144 MB), 90 MB for d12, 0.5 GB for d30; cache format and
+    // GEMM mode are fixed per model object, so they need no tag.  Not for shared_aln models, _begin_cond, _begin_rows, nor with the f16x2 guard on.
+    uint16_t* s0_tab = nullptr;
+    bool s0_ready = false;       // the table holds stage 0 of the bound weights for s0_R rows under variant epoch s0_epoch
+    bool s0_live = false;        // the current call may take its stage 0 from the table (set by sdvar_model_begin)
+    int s0_R = 0;
+    unsigned s0_epoch = 0;
+    size_t s0_row16 = 0;
+    Stage0Geom s0_geom{};
+    long long* s0_labels = nullptr;    // owned (num_classes + 1 + Rmax): 0, 1, .. num_classes, then the padding of the build's last batch
+    int* row_cls = nullptr;            // owned (Rmax): class of every row of the current label-conditioned call (ada_gather writes it)
+    uint16_t** s0_kv = nullptr;        // owned (2 depth): device copy of the blocks' {kc, vc}
+    float *x_first = nullptr, *lg_first = nullptr;     // owned (Rmax, C) / (Rmax, V): input of a computed sdvar_stage_first; logits of the table build
     float* ws_own = nullptr;   // this model's split-K slabs: two models of one host thread may run on different streams
     int lens[SDVAR_MAX_STAGES], cum[SDVAR_MAX_STAGES];
     // borrowed
@@ -338,6 +361,21 @@ int sdvar_model_create(const sdvar_model_desc* desc, sdvar_model_t** out) {
         SDVAR_HIP(hipMemset(b.vc, 0, kvb));
     }
     SDVAR_TRY(dmalloc(&m->ws_own, splitk_workspace_floats()));
+    {       // stage-0 table (sdvar_stage_first): the small fixed parts; the table itself is allocated by its first build
+        SDVAR_TRY(dmalloc(&m->row_cls, R));
+        SDVAR_TRY(dmalloc(&m->x_first, R * C));
+        SDVAR_TRY(dmalloc(&m->s0_kv, (size_t)2 * desc->depth));
+        std::vector<uint16_t*> kv;
+        for (auto& b : m->blk) { kv.push_back((uint16_t*)b.kc); kv.push_back((uint16_t*)b.vc); }
+        SDVAR_HIP(hipMemcpy(m->s0_kv, kv.data(), kv.size() * sizeof(uint16_t*), hipMemcpyHostToDevice));
+        const size_t lp = m->Lkv;
+        Stage0Geom& g = m->s0_geom;
+        g.n16 = m->kv_fmt == 0 ? 128 : 64;                          // one position of one head: 64 values, an fp32 value = two units
+        g.np = m->kv_fmt == 2 ? 3 : m->kv_fmt == 3 ? 2 : 1;
+        g.kes = 1; g.ves = m->kv_fmt == 2 ? lp : 1;                 // format 2 keeps V transposed: [plane][64][Lp], key 0 in column 0
+        g.plane = lp * 64; g.head = (size_t)g.np * lp * g.n16;
+        m->s0_row16 = (size_t)2 * desc->vocab + (size_t)desc->depth * 2 * m->H * g.np * g.n16;
+    }
     guard.keep = true;
     *out = m;
     return SDVAR_OK;
@@ -348,6 +386,8 @@ int sdvar_model_destroy(sdvar_model_t* m) {
     float* bufs[] = {m->lvl_pos, m->cond, m->cond_silu, m->x0, m->ada, m->ada_head, m->xn, m->qkv, m->qbuf, m->att, m->hid, m->ws_own, m->gss_lin, m->head_wsc, m->ada_tab};
     for (float* p : bufs) if (p) (void)hipFree(p);
     if (m->stage_of_tok) (void)hipFree(m->stage_of_tok);
+    void* s0b[] = {m->s0_tab, m->s0_labels, m->row_cls, m->s0_kv, m->x_first, m->lg_first};
+    for (void* p : s0b) if (p) (void)hipFree(p);
     uint16_t* pb[] = {m->xn_p, m->att_p, m->hid_p, m->head_wp};
     for (uint16_t* p : pb) if (p) (void)hipFree(p);
     for (auto& b : m->blk) { uint16_t* wp[] = {b.qkv_wp, b.proj_wp, b.fc1_wp, b.fc2_wp}; for (uint16_t* p : wp) if (p) (void)hipFree(p); }
@@ -361,7 +401,7 @@ int sdvar_model_bind_embed(sdvar_model_t* m, const float* class_emb, const float
     SDVAR_CHECK_ARG(m && class_emb && pos_start && pos_1LC && lvl_embed && word_w && word_b, "bind_embed: null argument");
     m->class_emb = class_emb; m->pos_start = pos_start; m->word_w = word_w; m->word_b = word_b;
     SDVAR_TRY(build_lvl_pos(lvl_embed, pos_1LC, m->stage_of_tok, m->lvl_pos, m->L, m->C, (hipStream_t)stream));
-    m->embed_bound = true; m->ada_tab_ready = false;
+    m->embed_bound = true; m->ada_tab_ready = false; m->s0_ready = false;
     return SDVAR_OK;
 }
 
@@ -394,20 +434,20 @@ int sdvar_model_bind_block(sdvar_model_t* m, int32_t i, const float* ada_w, cons
             SDVAR_TRY(split_planes_f16(ws[k], wp[k], rows[k], cols[k], (size_t)rows[k] * cols[k], b.wsc + 4 * k, s));
         }
     }
-    b.bound = true; m->ada_tab_ready = false;
+    b.bound = true; m->ada_tab_ready = false; m->s0_ready = false;
     return SDVAR_OK;
 }
 
 int sdvar_model_bind_shared_aln(sdvar_model_t* m, const float* w, const float* b) {
     SDVAR_CHECK_ARG(m && w && b, "bind_shared_aln: null argument");
-    m->shared_w = w; m->shared_b = b;
+    m->shared_w = w; m->shared_b = b; m->s0_ready = false;
     if (!m->gss_lin) SDVAR_TRY(dmalloc(&m->gss_lin, (size_t)m->Rmax * 6 * m->C));
     return SDVAR_OK;
 }
 
 int sdvar_model_bind_head(sdvar_model_t* m, const float* nm_w, const float* nm_b, const float* head_w, const float* head_b, void* stream) {
     SDVAR_CHECK_ARG(m && nm_w && nm_b && head_w && head_b, "bind_head: null argument");
-    m->nm_w = nm_w; m->nm_b = nm_b; m->head_w = head_w; m->head_b = head_b; m->head_bound = true; m->ada_tab_ready = false;
+    m->nm_w = nm_w; m->nm_b = nm_b; m->head_w = head_w; m->head_b = head_b; m->head_bound = true; m->ada_tab_ready = false; m->s0_ready = false;
     if (m->d.gemm_mode == 1) SDVAR_TRY(split_planes(head_w, m->head_wp, m->d.vocab, m->C, (size_t)m->d.vocab * m->C, (hipStream_t)stream));
     if (m->d.gemm_mode == 2) {
         SDVAR_TRY(weight_scale_f16(head_w, (size_t)m->d.vocab * m->C, m->head_wsc, (hipStream_t)stream));
@@ -427,11 +467,57 @@ static int check_bound(const sdvar_model* m) {
 }
 
 // R rows; rows r < nlab are conditioned on labels[r], the others on the unconditional class (the CFG pair: R = 2B, nlab = B)
-static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int64_t* labels, const float* cond_in, void* stream);
+static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int64_t* labels, const float* cond_in, void* stream, bool first_tab = false);
+static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream);
+
+// label-conditioned calls of a model with per-block ada_lin take their adaLN parameters from the per-class table (SDVAR_ADALN_TABLE=0: A/B runs)
+static bool ada_table_wanted(const sdvar_model* m) {
+    static const bool tab_off = getenv("SDVAR_ADALN_TABLE") && atoi(getenv("SDVAR_ADALN_TABLE")) == 0;
+    const size_t C = m->C, NC = (size_t)m->d.num_classes + 1, row = (size_t)m->d.depth * 6 * C + 2 * C;
+    return !m->shared_w && !tab_off && NC * (row + C) * sizeof(float) <= ((size_t)8 << 30);
+}
+
+// sdvar_model_begin may serve stage 0 from the per-class table: the rows' classes come from ada_gather, the first stage is one token, the table fits under its cap,
+// and no f16x2 guard wants to count the operand planes of the pass
+static bool stage0_table_wanted(const sdvar_model* m) {
+    if (!ada_table_wanted(m) || g_guard_on || m->lens[0] != 1 || variant(VAR_STAGE0_TABLE) == 0) return false;
+    const size_t bytes = ((size_t)m->d.num_classes + 1) * m->s0_row16 * sizeof(uint16_t);
+    return bytes <= ((size_t)variant(VAR_STAGE0_TABLE_MB) << 20);
+}
+
+// Stage 0 of every class into m->s0_tab, by the launch sequence a call of R rows runs (prologue -> ada_gather -> stage_forward_impl(.., 0, 1)): ceil((num_classes + 1) / R)
+// passes over batches of exactly R rows, each row its own class, the last batch padded with the unconditional class; the rows are snapshot after every pass.  A
+// large-M GEMM over all classes would be faster and sum in another order.  Runs in the model's own buffers; the caller's prologue comes after it.
+static int stage0_build(sdvar_model_t* m, int R, hipStream_t s) {
+    const int NC = m->d.num_classes + 1, nb = (NC + R - 1) / R, V = m->d.vocab;
+    m->s0_ready = false;
+    if (!m->s0_tab) SDVAR_HIP(hipMalloc((void**)&m->s0_tab, (size_t)NC * m->s0_row16 * sizeof(uint16_t)));
+    if (!m->lg_first) SDVAR_TRY(dmalloc(&m->lg_first, (size_t)m->Rmax * V));
+    if (!m->s0_labels) {
+        std::vector<long long> lab((size_t)NC + m->Rmax);
+        for (size_t i = 0; i < lab.size(); ++i) lab[i] = i < (size_t)NC ? (long long)i : (long long)NC - 1;
+        SDVAR_TRY(dmalloc(&m->s0_labels, lab.size()));
+        SDVAR_HIP(hipMemcpy(m->s0_labels, lab.data(), lab.size() * sizeof(long long), hipMemcpyHostToDevice));
+    }
+    // a build is not part of any call's profile, nor of the launch diagnostics tests read around a call (sdvar_debug_get_gemm_cfg)
+    struct Quiet { bool was; int cfg[6]; Quiet() : was(g_prof_on) { g_prof_on = false; debug_peek_gemm_cfg_h(cfg); } ~Quiet() { g_prof_on = was; debug_restore_gemm_cfg_h(cfg); } } quiet;
+    for (int b = 0; b < nb; ++b) {
+        SDVAR_TRY(model_begin_impl(m, R, R, (const int64_t*)(m->s0_labels + (size_t)b * R), nullptr, s));
+        SDVAR_HIP(hipMemcpyAsync(m->x_first, m->x0, (size_t)R * m->C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SDVAR_TRY(stage_forward_impl(m, m->x_first, 0, 1, nullptr, m->lg_first, s));
+        const int nvalid = NC - b * R < R ? NC - b * R : R;
+        SDVAR_TRY(stage0_rows(m->s0_tab, m->s0_row16, m->row_cls, m->s0_kv, m->lg_first, R, V, m->d.depth, m->H, m->s0_geom, nvalid, 1, s));
+        m->kv_len = 0;
+    }
+    m->begun = false;
+    SDVAR_HIP(hipStreamSynchronize(s));          // once per (bind, R): later calls may come on other streams and only READ the table
+    m->s0_ready = true; m->s0_R = R; m->s0_epoch = variant_epoch();
+    return SDVAR_OK;
+}
 int sdvar_model_begin(sdvar_model_t* m, int32_t B, const int64_t* labels, void* stream) {
     SDVAR_CHECK_ARG(labels, "model_begin: null labels");
     SDVAR_CHECK_ARG(m && B >= 1 && B <= m->d.max_batch, "model_begin: B=%d (max %d)", B, m ? m->d.max_batch : 0);
-    SDVAR_TRY(model_begin_impl(m, 2 * B, B, labels, nullptr, stream));
+    SDVAR_TRY(model_begin_impl(m, 2 * B, B, labels, nullptr, stream, true));
     m->B = B;
     return SDVAR_OK;
 }
@@ -447,11 +533,16 @@ int sdvar_model_begin_rows(sdvar_model_t* m, int32_t R, const int64_t* labels, v
     SDVAR_CHECK_ARG(m && R >= 1 && R <= 2 * m->d.max_batch, "model_begin_rows: R=%d rows (max 2 * max_batch = %d)", R, m ? 2 * m->d.max_batch : 0);
     return model_begin_impl(m, R, R, labels, nullptr, stream);
 }
-static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int64_t* labels, const float* cond_in, void* stream) {
+static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int64_t* labels, const float* cond_in, void* stream, bool first_tab) {
     SDVAR_TRY(check_bound(m));
     hipStream_t s = (hipStream_t)stream;
     WsScope wsg(m->ws_own);
     const int C = m->C;
+    m->s0_live = false;
+    if (first_tab && stage0_table_wanted(m)) {      // before this call's own prologue: a build runs in the model's buffers
+        if (!m->s0_ready || m->s0_R != R || m->s0_epoch != variant_epoch()) SDVAR_TRY(stage0_build(m, R, s));
+        m->s0_live = true;
+    }
     m->B = 0; m->R = R; m->kv_len = 0; m->kv_origin = 0;
     {
         ProfScope ps(7, 0, 0, s);
@@ -459,9 +550,8 @@ static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int
         SDVAR_TRY(silu_rows(m->cond, m->cond_silu, R * C, s));
     }
     // adaLN parameters of every block: stage-invariant, computed once per call instead of once per stage - or, for label-conditioned calls, once per BIND:
-    static const bool tab_off = getenv("SDVAR_ADALN_TABLE") && atoi(getenv("SDVAR_ADALN_TABLE")) == 0;          // A/B runs
     const size_t NC = (size_t)m->d.num_classes + 1, row = (size_t)m->d.depth * 6 * C + 2 * C;
-    if (labels && !m->shared_w && !tab_off && NC * (row + C) * sizeof(float) <= ((size_t)8 << 30)) {
+    if (labels && ada_table_wanted(m)) {
         if (!m->ada_tab_ready) {
             if (!m->ada_tab) SDVAR_TRY(dmalloc(&m->ada_tab, NC * (row + C)));
             float* sil = m->ada_tab + NC * row;                  // silu(class_emb), scratch behind the table
@@ -474,7 +564,7 @@ static int model_begin_impl(sdvar_model_t* m, int32_t R, int32_t nlab, const int
             m->ada_tab_ready = true;
         }
         ProfScope ps(7, 0, 8.0 * R * (double)row, s);
-        SDVAR_TRY(ada_gather((const long long*)labels, m->ada_tab, row, m->d.depth, C, m->ada, (size_t)m->Rmax * 6 * C, m->ada_head, R, nlab, m->d.num_classes, s));
+        SDVAR_TRY(ada_gather((const long long*)labels, m->ada_tab, row, m->d.depth, C, m->ada, (size_t)m->Rmax * 6 * C, m->ada_head, R, nlab, m->d.num_classes, m->row_cls, s));
         m->begun = true;
         return SDVAR_OK;
     }
@@ -646,6 +736,23 @@ int sdvar_stage_forward(sdvar_model_t* m, float* x, int32_t s0, int32_t n, float
 int sdvar_stage_forward_masked(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream) {
     SDVAR_CHECK_ARG(bias, "stage_forward_masked: null mask");
     return stage_forward_impl(m, x, s0, n, bias, logits, stream);
+}
+
+int sdvar_stage_first(sdvar_model_t* m, float* logits, void* stream) {
+    SDVAR_TRY(check_bound(m));
+    SDVAR_CHECK_ARG(m->begun && logits, "stage_first: model not begun or null logits");
+    SDVAR_CHECK_ARG(m->lens[0] == 1, "stage_first: the first stage has %d tokens, the prologue makes one", m->lens[0]);
+    if (m->kv_len != 0 || m->kv_origin != 0) { set_error("stage_first: KV cache holds %d keys at origin %d, stage 0 needs an empty cache at origin 0", m->kv_len, m->kv_origin); return SDVAR_ERR_STATE; }
+    hipStream_t s = (hipStream_t)stream;
+    // the table of this call's begin, unless a switch has moved since: then the computed pass, which is always right
+    if (m->s0_live && m->s0_ready && m->s0_R == m->R && m->s0_epoch == variant_epoch() && !g_guard_on && variant(VAR_STAGE0_TABLE) != 0) {
+        ProfScope ps(7, 0, 4.0 * m->R * (double)m->s0_row16, s);
+        SDVAR_TRY(stage0_rows(m->s0_tab, m->s0_row16, m->row_cls, m->s0_kv, logits, m->R, m->d.vocab, m->d.depth, m->H, m->s0_geom, m->R, 0, s));
+        m->kv_len = 1;
+        return SDVAR_OK;
+    }
+    SDVAR_HIP(hipMemcpyAsync(m->x_first, m->x0, (size_t)m->R * m->C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return stage_forward_impl(m, m->x_first, 0, 1, nullptr, logits, stream);
 }
 
 static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n, const float* bias, float* logits, void* stream) {
@@ -1100,12 +1207,12 @@ int sdvar_debug_set_gemm_cfg(int32_t bm, int32_t split) {
     // f16x2 only: bm 512 = the 256 x 256 tile kernel, 768 = the 256 x 192 one; bm 16 = the skinny kernel (M <= 80); bm 256 with split -T = hybrid tail split T ways (the other modes take their nearest tile)
     SDVAR_CHECK_ARG(bm == 0 || bm == 16 || bm == 32 || bm == 64 || bm == 128 || bm == 256 || bm == 512 || bm == 768, "debug_set_gemm_cfg: bm %d", bm);
     SDVAR_CHECK_ARG(split >= -64 && split <= 64 && (split >= 0 || bm == 256), "debug_set_gemm_cfg: split %d", split);
-    g_variants[VAR_FORCE_BM].store(bm); g_variants[VAR_FORCE_SPLIT].store(split);
+    g_variants[VAR_FORCE_BM].store(bm); g_variants[VAR_FORCE_SPLIT].store(split); bump_variant_epoch();
     return SDVAR_OK;
 }
 
-int sdvar_debug_set_qkv_fuse(int32_t on) { g_variants[VAR_QKV_FUSE].put(on); return SDVAR_OK; }
-int sdvar_debug_set_rowblk(int32_t on) { g_variants[VAR_ROWBLK].put(on); return SDVAR_OK; }          // 0 off, 1 default (32 .. 80 rows), 2 every call of at most 80 rows
+int sdvar_debug_set_qkv_fuse(int32_t on) { g_variants[VAR_QKV_FUSE].put(on); bump_variant_epoch(); return SDVAR_OK; }
+int sdvar_debug_set_rowblk(int32_t on) { g_variants[VAR_ROWBLK].put(on); bump_variant_epoch(); return SDVAR_OK; }          // 0 off, 1 default (32 .. 80 rows), 2 every call of at most 80 rows
 int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const float* shift, int32_t rows_per_img, int32_t mod_stride, const uint16_t* Xp, uint64_t x_plane_stride,
                          const uint16_t* Wp, uint64_t w_plane_stride, const float* w_scale, const float* bias, float* out, int32_t ldo, uint16_t* out_planes, uint64_t out_plane_stride,
                          int32_t M, int32_t N, int32_t K, int32_t epi, const float* res, int32_t ldres, const float* gate, int32_t rows_per_gate, int32_t gate_stride,

@@ -24,6 +24,9 @@ struct PendingSplitK {
     int split, rows_per_gate, gate_stride;
 };
 
+// Where cache position 0 of one (row, head) lies in a KV cache, in 2-byte units (stage0_rows at the end of this file; api.hip fills it from the cache format)
+struct Stage0Geom { int n16, np; size_t kes, ves, plane, head; };
+
 // ------------------------------------------------------------------------------------------------ ln_modulate
 // x (rows, C) ; scale/shift: row r of the CFG batch = row / rows_per_img, element stride `mod_stride` between r's.
 // A wave holds one row as LN_MAX_V4 float4 per lane: the kernels are instantiated for 4 / 8 / 12 (C <= 1024 / 2048 / 3072; VAR-d36-s,
@@ -613,10 +616,12 @@ int prologue(const long long* labels, const float* cond_in, const float* class_e
 // adaLN parameters of a call from the per-class table (api.hip: model_begin): row r of block i = tab[label(r)][i * 6C ..], head row = tab[label(r)][depth * 6C ..];
 // label(r) = labels[r] for r < nlab, else the unconditional class (grid: one workgroup per row)
 __global__ __launch_bounds__(256) void ada_gather_kernel(const long long* __restrict__ labels, const float* __restrict__ tab, size_t row_floats, int depth, int C,
-                                                         float* __restrict__ ada, size_t blk_stride, float* __restrict__ ada_head, int nlab, int num_classes) {
+                                                         float* __restrict__ ada, size_t blk_stride, float* __restrict__ ada_head, int nlab, int num_classes,
+                                                         int* __restrict__ row_cls) {
     const int r = blockIdx.x, i = blockIdx.y;
     long long lab = (r < nlab) ? labels[r] : (long long)num_classes;
     if (lab < 0 || lab > num_classes) lab = num_classes;
+    if (row_cls && i == 0 && threadIdx.x == 0) row_cls[r] = (int)lab;      // the class of every row of the call, for stage0_rows below
     const int n4 = (i < depth ? 6 * C : 2 * C) / 4;
     const float4* src = reinterpret_cast<const float4*>(tab + (size_t)lab * row_floats + (size_t)i * 6 * C);
     float4* dst = reinterpret_cast<float4*>(i < depth ? ada + (size_t)i * blk_stride + (size_t)r * 6 * C : ada_head + (size_t)r * 2 * C);
@@ -624,8 +629,60 @@ __global__ __launch_bounds__(256) void ada_gather_kernel(const long long* __rest
 }
 
 int ada_gather(const long long* labels, const float* tab, size_t row_floats, int depth, int C, float* ada, size_t blk_stride, float* ada_head, int R, int nlab, int num_classes,
-               hipStream_t stream) {
-    hipLaunchKernelGGL(ada_gather_kernel, dim3(R, depth + 1), dim3(256), 0, stream, labels, tab, row_floats, depth, C, ada, blk_stride, ada_head, nlab, num_classes);
+               int* row_cls, hipStream_t stream) {
+    hipLaunchKernelGGL(ada_gather_kernel, dim3(R, depth + 1), dim3(256), 0, stream, labels, tab, row_floats, depth, C, ada, blk_stride, ada_head, nlab, num_classes, row_cls);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// The stage-0 table of api.hip (sdvar_stage_first): row cls = [logits: V floats][block 0: K bytes, V bytes][block 1: ...], where the K (V) bytes of a block are what a
+// stage-0 forward leaves at cache position 0 of one row of that block's K (V) cache, copied verbatim.  Everything is counted in 2-byte units (an fp32 cache: two per
+// value) so that one kernel serves every cache format; Stage0Geom says where position 0 lies: per head `np` planes of `n16` units, `plane` units apart, unit e of a
+// plane at e * kes (K) / e * ves (V) - 1 everywhere except the transposed V planes of format 2, where channel d of key 0 sits at d * Lp.
+// to_table = 1 snapshots rows r < nvalid of the live caches + logits into the table rows cls[r]; 0 scatters the table rows cls[r] back into the caches + logits.
+// thread = one 16-byte chunk (8 units) of a table row; grid (chunks / 256, R).
+__global__ __launch_bounds__(256) void stage0_rows_kernel(uint16_t* __restrict__ tab, size_t row16, const int* __restrict__ cls, uint16_t* const* __restrict__ kv,
+                                                          float* __restrict__ logits, int V, int depth, int H, Stage0Geom g, int nvalid, int to_table) {
+    const int r = blockIdx.y;
+    const int c = blockIdx.x * 256 + threadIdx.x;          // chunk of the table row
+    const int lg8 = V / 4;                                 // chunks of the logits part
+    const int pl8 = g.n16 / 8, hd8 = g.np * pl8, kv8 = H * hd8;
+    if (r >= nvalid || c >= lg8 + depth * 2 * kv8) return;
+    const int k = cls[r];
+    if (k < 0) return;
+    uint16_t* t = tab + (size_t)k * row16 + (size_t)c * 8;
+    if (c < lg8) {
+        uint16_t* p = reinterpret_cast<uint16_t*>(logits + (size_t)r * V) + (size_t)c * 8;
+        if (to_table) *reinterpret_cast<u32x4*>(t) = *reinterpret_cast<const u32x4*>(p);
+        else *reinterpret_cast<u32x4*>(p) = *reinterpret_cast<const u32x4*>(t);
+        return;
+    }
+    int q = c - lg8;
+    const int blk = q / (2 * kv8); q -= blk * 2 * kv8;
+    const int isv = q / kv8; q -= isv * kv8;
+    const int h = q / hd8; q -= h * hd8;
+    const int pi = q / pl8, e = (q - pi * pl8) * 8;
+    const size_t es = isv ? g.ves : g.kes;
+    uint16_t* p = kv[2 * blk + isv] + (size_t)r * H * g.head + (size_t)h * g.head + (size_t)pi * g.plane + (size_t)e * es;
+    if (es == 1) {
+        if (to_table) *reinterpret_cast<u32x4*>(t) = *reinterpret_cast<const u32x4*>(p);
+        else *reinterpret_cast<u32x4*>(p) = *reinterpret_cast<const u32x4*>(t);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (to_table) t[u] = p[(size_t)u * es];
+            else p[(size_t)u * es] = t[u];
+        }
+    }
+}
+
+int stage0_rows(uint16_t* tab, size_t row16, const int* cls, uint16_t* const* kv, float* logits, int R, int V, int depth, int H, const Stage0Geom& g, int nvalid,
+                int to_table, hipStream_t stream) {
+    SDVAR_CHECK_ARG(tab && cls && kv && logits && R > 0 && nvalid >= 0 && nvalid <= R && V % 4 == 0 && g.n16 % 8 == 0 && row16 % 8 == 0,
+                    "stage0_rows: bad arguments (R=%d nvalid=%d V=%d n16=%d)", R, nvalid, V, g.n16);
+    SDVAR_CHECK_ARG(row16 == (size_t)2 * V + (size_t)depth * 2 * H * g.np * g.n16, "stage0_rows: row of %zu units does not match the geometry", row16);
+    const size_t chunks = row16 / 8;
+    hipLaunchKernelGGL(stage0_rows_kernel, dim3((unsigned)((chunks + 255) / 256), R), dim3(256), 0, stream, tab, row16, cls, kv, logits, V, depth, H, g, nvalid, to_table);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }

@@ -185,6 +185,7 @@ float* splitk_workspace(size_t* floats) {          // shared with gemm_bf16x3.hi
 }
 
 // every process-wide switch with a setter: name (sdvar_debug_set_variant), environment variable, default, legal range, value an out-of-range environment maps to
+std::atomic<unsigned> g_variant_epoch{0};
 Variant g_variants[VAR_COUNT] = {
     {"gemm_h4_var", "SDVAR_GEMM_H4_VAR", 3, 0, 3, 3, false, false},             // which 256 x 256 kernel: 3 = 16x16x32 MFMAs, 0 - 2 = 32x32x16 and its DMA placements
     {"gemm_h2_stages", "SDVAR_GEMM_H2_STAGES", 6, 2, 6, 6, false, false},       // ring of the 128 x 128 kernel
@@ -195,6 +196,8 @@ Variant g_variants[VAR_COUNT] = {
     {"rowblk", "SDVAR_ROWBLK", 1, 0, 2, 1, false, false},                       // 0 off, 1 from 32 rows, 2 every call of at most 80 rows (sdvar_debug_set_rowblk)
     {"qkv_fuse", "SDVAR_NO_QKV_FUSE", 1, 0, 1, 1, false, true},                 // QKV finish in the GEMM epilogue (sdvar_debug_set_qkv_fuse)
     {"gemm_v2", nullptr, 1, 0, 1, 1, false, false},                             // bf16x3 128-row tile on the LDS-DMA kernel
+    {"stage0_table", "SDVAR_STAGE0_TABLE", 1, 0, 1, 1, false, false},           // stage 0 of a label-conditioned call from the per-class table (api.hip: sdvar_stage_first); 0 = always computed
+    {"stage0_table_mb", "SDVAR_STAGE0_TABLE_MB", 1024, 0, 1 << 20, 1024, false, false},      // size cap of that table in MiB; a larger table is not built and stage 0 is computed
     {nullptr, nullptr, 0, 0, 768, 0, false, false},                             // forced tile, in f16x2's codes (sdvar_debug_set_gemm_cfg); 0 = automatic
     {nullptr, nullptr, 0, -64, 64, 0, false, false},                            // forced K split; < 0 with tile 256: hybrid tail split
 };

@@ -1963,6 +1963,9 @@ void debug_get_gemm_cfg_h(int* out) {
     out[0] = g_last_plan.plan.kernel; out[1] = g_last_plan.plan.split; out[2] = g_last_plan.tail_launches; out[3] = g_last_plan.fused_launches;
     g_last_plan.tail_launches = g_last_plan.fused_launches = 0;
 }
+// api.hip's stage-0 table build runs whole passes inside another call: it puts these diagnostics back as it found them (peek: read without the reset)
+void debug_peek_gemm_cfg_h(int* out) { out[0] = g_last_plan.plan.kernel; out[1] = g_last_plan.plan.split; out[2] = g_last_plan.tail_launches; out[3] = g_last_plan.fused_launches; out[4] = g_last_plan.plan.tail; out[5] = g_last_plan.plan.qkv_fused; }
+void debug_restore_gemm_cfg_h(const int* in) { g_last_plan.plan = GemmPlan{in[0], in[1], in[4], in[5] != 0}; g_last_plan.tail_launches = in[2]; g_last_plan.fused_launches = in[3]; }
 
 // gemm_h2_stages, the variant of the 128 x 128 kernel: 6 (default, round 3) = 4-stage ring, the two waves of a SIMD alternate (1 - 7 % faster than 4: profiles/r03_l_v2pp_ab.log;
 // the same kernel on 16x16x32 MFMAs was built, passed the suite and was no faster - this tile is DMA / CU-intake bound, not power bound: profiles/r03_r_v6_ab.log);

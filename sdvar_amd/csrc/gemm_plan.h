@@ -18,7 +18,7 @@ namespace sdvar {
 // ---- variant table -----------------------------------------------------------------------------------------------------------------------------------------
 // One entry per switch that has a setter.  The value is env-or-default until a setter stores one; a setter value < 0 goes back to env-or-default.  An environment
 // value outside [lo, hi] maps to `fallback`.  The atomics make reads from concurrent host threads safe; the setters are still meant for single-threaded tools.
-enum VariantId { VAR_GEMM_H4, VAR_GEMM_H2_STAGES, VAR_GEMM_SMALL_PP, VAR_ATTN_PP_SCHED, VAR_CONV_PP, VAR_CONV_TAP_REUSE, VAR_ROWBLK, VAR_QKV_FUSE, VAR_GEMM_V2, VAR_FORCE_BM, VAR_FORCE_SPLIT, VAR_COUNT };
+enum VariantId { VAR_GEMM_H4, VAR_GEMM_H2_STAGES, VAR_GEMM_SMALL_PP, VAR_ATTN_PP_SCHED, VAR_CONV_PP, VAR_CONV_TAP_REUSE, VAR_ROWBLK, VAR_QKV_FUSE, VAR_GEMM_V2, VAR_STAGE0_TABLE, VAR_STAGE0_TABLE_MB, VAR_FORCE_BM, VAR_FORCE_SPLIT, VAR_COUNT };
 
 struct Variant {
     const char* name;           // sdvar_debug_set_variant's name; null: set only through its own ABI function
@@ -47,11 +47,17 @@ struct Variant {
 };
 extern Variant g_variants[VAR_COUNT];       // gemm.hip
 inline int variant(VariantId id) { return g_variants[id].get(); }
+// Bumped by every setter that can change which kernel, K split or launch sequence a call gets: results cached across calls (the stage-0 table of api.hip) carry the
+// epoch they were computed under and are rebuilt when it has moved.  The two stage-0 switches only choose between the table and the computed path: no bump.
+extern std::atomic<unsigned> g_variant_epoch;       // gemm.hip
+inline unsigned variant_epoch() { return g_variant_epoch.load(std::memory_order_relaxed); }
+inline void bump_variant_epoch() { g_variant_epoch.fetch_add(1, std::memory_order_relaxed); }
 inline int set_variant_by_name(const char* name, int value) {
     for (Variant& v : g_variants) {
         if (!v.name || strcmp(v.name, name)) continue;
         SDVAR_CHECK_ARG(value <= v.hi && (value < 0 || value >= v.lo), "%s %d", name, value);
         v.put(value);
+        if (&v != &g_variants[VAR_STAGE0_TABLE] && &v != &g_variants[VAR_STAGE0_TABLE_MB]) bump_variant_epoch();
         return SDVAR_OK;
     }
     set_error("debug_set_variant: unknown variant '%s'", name);

@@ -74,6 +74,7 @@ _SIGNATURES = {
     "sdvar_embed_next": (_I, [_P, _P, _I, _P, _I, _I, _P]),
     "sdvar_embed_next_at": (_I, [_P, _P, _I, _I, _P, _I, _I, _P]),
     "sdvar_stage_forward": (_I, [_P, _P, _I, _I, _P, _P]),
+    "sdvar_stage_first": (_I, [_P, _P, _P]),
     "sdvar_stage_forward_masked": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "sdvar_quant_create": (_I, [_I, C.POINTER(_I), _I, _I, _I, _I, C.POINTER(_P)]),
     "sdvar_quant_destroy": (_I, [_P]),
@@ -313,6 +314,11 @@ class ModelCtx:
             _check(self.lib.sdvar_stage_forward(self.h, _ptr(x), s0, n, _ptr(logits), _stream()))
         else:
             _check(self.lib.sdvar_stage_forward_masked(self.h, _ptr(x), s0, n, _ptr(bias), _ptr(logits), _stream()))
+
+    def forward_first(self, logits: torch.Tensor):
+        """Stage 0 from the model's own first-token map: equals place_first + forward(x, 0, 1), bit for bit.  After begin(labels) it is one launch that copies
+        the call's rows out of the per-class stage-0 table (include/sdvar_hip.h: sdvar_stage_first); otherwise the computed pass."""
+        _check(self.lib.sdvar_stage_first(self.h, _ptr(logits), _stream()))
 
     def kv_len(self) -> int:
         return self.lib.sdvar_kv_len(self.h)
@@ -1519,10 +1525,12 @@ class Sampler:
         with torch.cuda.device(self.dev):
             m.begin(labels)
             f_hat = self.f_work[:B]; f_hat.zero_()
-            m.place_first(self.x_t, lad.lens[0])
             for si in range(S):
                 l = lad.lens[si]
-                m.forward(self.x_t, si, 1, self.logits_t)
+                if si == 0:
+                    m.forward_first(self.logits_t)
+                else:
+                    m.forward(self.x_t, si, 1, self.logits_t)
                 if trace:
                     res.trace.setdefault("logits", []).append(self.logits_t[:2 * B * l * V].view(2 * B, l, V).clone())
                 self._sample_stage(self.logits_t, B, si, cfg, top_k, top_p, noise, si, more_smooth, f_hat, self.nxt[0])
@@ -1675,13 +1683,17 @@ class Sampler:
         with torch.cuda.device(self.dev):
             x_t = self._xt[st.xt_idx]
             if cur == 0:
-                d.place_first(self.x_d, lens[0]); t.place_first(x_t, lsum)
+                if g > 1:                                  # the draft's stage 0 and a one-stage verify take forward_first: only a chunk needs the first-token map in x
+                    t.place_first(x_t, lsum)
             else:
                 d.embed_next(self.nxt_cur, cur, self.x_d, lens[cur], 0); t.embed_next(self.nxt_cur, cur, x_t, lsum, 0)
             for j in range(g):
                 s = cur + j
                 lg = dl[2 * B * V * offs[j]:] if keep_logits else self.logits_d
-                d.forward(self.x_d, s, 1, lg)
+                if s == 0:
+                    d.forward_first(lg)
+                else:
+                    d.forward(self.x_d, s, 1, lg)
                 st.stats["draft_stage_calls"] += 1
                 q = st.noise.tensor(st.draw, B, lens[s], V, self.dev)
                 cfg_sample(lg, B, lens[s], V, lad.cfg_t(st.cfg, s), st.top_k, st.top_p, q, st.noise.seed, st.draw, st.noise.image_offset,
@@ -1702,7 +1714,10 @@ class Sampler:
         assert st.drafted, "draft_generate_batch must run before target_verify_batch"
         lsum = sum(st.glen)
         with torch.cuda.device(self.dev):
-            self.t.forward(self._xt[st.xt_idx], st.current_stage, st.g, self.logits_t)
+            if st.current_stage == 0 and st.g == 1:
+                self.t.forward_first(self.logits_t)
+            else:
+                self.t.forward(self._xt[st.xt_idx], st.current_stage, st.g, self.logits_t)
         st.stats["target_calls"] += 1
         st.target_calls += 1
         st.verified = True
@@ -1914,7 +1929,10 @@ class Sampler:
                 ready = torch.cuda.Event(); ready.record(D)
                 T.wait_event(ready)
                 with torch.cuda.stream(T):
-                    self.t.forward(self._xt[st.xt_idx], cur, 1, self.logits_t)
+                    if cur == 0:
+                        self.t.forward_first(self.logits_t)
+                    else:
+                        self.t.forward(self._xt[st.xt_idx], cur, 1, self.logits_t)
                     verify_accept(self.logits_t, B, st.glen, V, [lad.cfg_t(st.cfg, cur)], self.ids, lad.begin(cur), lad.L, st.thr, self.counts_ra[row0 + r])
                     ev = torch.cuda.Event(); ev.record(T); t_done.append(ev)
                 st.stats["target_calls"] += 1

@@ -16,7 +16,7 @@ def one_pass(profile):
     for s in range(lad.S):
         if profile: E.prof_enable(True)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); ctx.forward(x, s, 1, lg); e1.record(); torch.cuda.synchronize()
+        e0.record(); (ctx.forward_first(lg) if s == 0 else ctx.forward(x, s, 1, lg)); e1.record(); torch.cuda.synchronize()       # stage 0 as the samplers run it (SDVAR_STAGE0_TABLE=0: computed)
         cls = E.prof_collect() if profile else None
         if profile: E.prof_enable(False)
         out.append((e0.elapsed_time(e1), cls))
