@@ -42,7 +42,9 @@ typedef struct {
     int32_t gemm_mode;                      /* 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = bf16x3 split operands on the bf16 MFMA
                                                (fp32-accurate: x = x1+x2+x3 exactly, 6 of 9 plane products, fp32 accumulate), 2 = f16x2 split
                                                operands on the f16 MFMA (x ~ xh + xl to 2^-22, 3 of 4 plane products, weights scaled by a power of
-                                               two per tensor, activations saturate at +-65504: csrc/gemm_f16x2.hip) */
+                                               two per tensor, activations saturate at +-65504: csrc/gemm_f16x2.hip), 3 = f16: a mode-2 model in every
+                                               respect (planes, caches, tables, small-M kernels) whose block and head GEMMs run as ONE fp16 product
+                                               on the high planes (csrc/gemm_half.hip) in calls of at least "h16_min_m" rows; NOT fp32-accurate */
 } sdvar_model_desc;
 
 int sdvar_abi_version(void);
@@ -441,6 +443,7 @@ int sdvar_op_gemm_rowblk(const float* x, int32_t ldx, const float* scale, const 
  * A lookup in the library's one table of process-wide switches (csrc/gemm_plan.h), which sdvar_debug_set_rowblk ("rowblk" 0..2), sdvar_debug_set_qkv_fuse
  * ("qkv_fuse" 0..1) and sdvar_debug_set_gemm_cfg write too; "gemm_v2" 0..1 (bf16x3: the 128-row tile on the LDS-DMA kernel, default 1) has no other setter.
  * "stage0_table" 0..1 (SDVAR_STAGE0_TABLE) and "stage0_table_mb" 0..2^20 (SDVAR_STAGE0_TABLE_MB, default 1024): sdvar_stage_first's per-class table and its size cap.
+ * "h16_min_m" 1..2^30 (SDVAR_H16_MIN_M): rows from which a call of a gemm_mode 3 model takes the half kernel; below it the call is mode 2's, bit for bit.
  * Every one of these setters except the two stage-0 ones moves an epoch that makes the next sdvar_model_begin rebuild that table. */
 int sdvar_debug_set_variant(const char* name, int32_t value);
 /* test aid: out4 = {kernel code (as sdvar_debug_plan_gemm; 17 = row-block launch) of the LAST f16x2 GEMM call of this host thread, its K split, number of launches that took the hybrid tail
@@ -459,7 +462,10 @@ int sdvar_debug_get_conv_plan(int32_t* out4);
  * consumer kernel, bit 1 = the call offers a QKV finish for the epilogue (sdvar_stage_forward's QKV launch), bit 2 = every output pointer and leading dimension
  * allows 16-byte accesses (bits 0 and 1 matter in mode 2 only).  out4 = {kernel code, K split, hybrid tail split (0 = none), 1 if the QKV finish runs in the
  * epilogue}; kernel codes: 16 = skinny (M <= 80), 32 / 64 / 128 / 256 = rows of a (rows x 128) tile, 512 = 256 x 256, 768 = 256 x 192 (17, the row-block
- * launch, is asked for by its callers and never planned).  After an f16x2 GEMM call sdvar_debug_get_gemm_cfg reports the same kernel code and split. */
+ * launch, is asked for by its callers and never planned).  After an f16x2 GEMM call sdvar_debug_get_gemm_cfg reports the same kernel code and split.
+ * The f16 tier (sdvar_model_desc.gemm_mode 3) is a mode-2 model with one flag, and is planned as such: mode 2 with flags bit 3 (value 8) gives {1128, 1, 0, 0} = the
+ * 128 x 128 half kernel when M >= "h16_min_m", else mode 2's plan for the other flag bits; sdvar_debug_get_gemm_cfg reports 1128 after such a launch.  `mode` itself stays
+ * 0..2: 3 is rejected as before. */
 int sdvar_debug_plan_gemm(int32_t mode, int32_t M, int32_t N, int32_t K, int32_t flags, int32_t* out4);
 /* f16x2 guard (debug, off by default; mode f16x2 only).  The f16x2 operand format of the default GEMM mode saturates finite activations at +-65504 and loses
  * relative precision below ~1e-3 (the reference computes these GEMMs in fp32: basic_var.py:44-52, 87-119).  With the guard on, every producer of GEMM operand
@@ -542,6 +548,18 @@ int sdvar_op_sdpa_h_bwd(const void* q, const void* k, const void* v, const void*
  *     not depend on M or N.  Argument errors (NULL / misaligned pointers, K % 32, N % 8, unknown dtype / epilogue / out_dtype) are reported before any launch. */
 int sdvar_op_gemm_h(const void* x, const void* w, int32_t dtype, const float* bias, void* out, int32_t out_dtype, int32_t ldo, void* h_out, void* pre_out, int32_t M, int32_t N,
                     int32_t K, int32_t epilogue, void* stream);
+/* The same kernel as the engine's GEMM mode 3 ("f16") launches it on the HIGH planes of f16x2 operands (added without an ABI bump; fp16 only: dtype must be 1).  Differences
+ * from sdvar_op_gemm_h:
+ *   - w_scale (device float, may be NULL = 1): the fp32 sum is multiplied by *w_scale before the bias is added, in every epilogue.  The engine passes the 2^-S entry of an
+ *     f16x2 weight scale (the high plane of such a weight is fp16(w * 2^S)); a power of two makes the product exact.
+ *   - out is fp32 only (no out_dtype).
+ *   - epilogue 1 saturates the pre-activation at +-65504 before it is rounded to fp16, as every f16x2 operand producer does; finite results are those of sdvar_op_gemm_h.
+ *   - epilogue 2 (gated residual): out[m,n] = res[m,n] + (sum * *w_scale + bias[n]) * gate[(m / rows_per_gate) * gate_stride + n]; res, gate, out fp32 row-major with leading
+ *     dimensions ldres / ldo (each >= N, % 4 == 0; gate_stride % 4 == 0), rows_per_gate >= 1.  res == out (in place) is allowed: an element is read and written by one lane.
+ *     h_out and pre_out must be NULL; res and gate must be NULL for epilogues 0 and 1.
+ * Argument errors, also a NULL res / gate with epilogue 2, rows_per_gate < 1 and a pointer that is not 16-byte aligned, are reported before any launch. */
+int sdvar_op_gemm_h_ex(const void* x, const void* w, int32_t dtype, const float* w_scale, const float* bias, float* out, int32_t ldo, void* h_out, void* pre_out, const float* res,
+                       int32_t ldres, const float* gate, int32_t rows_per_gate, int32_t gate_stride, int32_t M, int32_t N, int32_t K, int32_t epilogue, void* stream);
 /* x row-major (rows, cols), leading dimension ldx, fp32 (x_dtype 0; ldx % 4 == 0) or already of dtype (x_dtype = dtype; ldx % 8 == 0) -> an OPERAND of dtype.  fp32 values are
  * rounded to nearest even - the bits of a cast - and an fp16 overflow becomes inf; half values are copied bit for bit.  transpose 0: the operand (rows x cols), cols % 32 == 0.
  * transpose 1: the operand of x^T, (cols x Kp), Kp = rows rounded up to 32, cols % 8 == 0; the tail k >= rows is written as zeros by this kernel.  colsum_part (transpose 1 only,

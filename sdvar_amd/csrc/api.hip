@@ -97,6 +97,9 @@ int attention_sdpa_h_bwd(const void* q, const void* k, const void* v, const void
                          const long long* strides, int dtype, int q_f32, int k_f32, const void* bias, int kind, const long long* bs, const uint8_t* skip, int B, int H,
                          int Lq, int Lk, int head_dim, double scale, hipStream_t stream);
 int split_planes(const float* x, uint16_t* planes, int rows, int cols, size_t plane_stride, hipStream_t stream);
+int gemm_half_ex(const void* x, const void* w, int dtype, const float* w_scale, const float* bias, float* out, int ldo, void* h_out, void* p_out, const float* res, int ldres,
+                 const float* gate, int rows_per_gate, int gate_stride, int M, int N, int K, int epi, hipStream_t stream);
+void debug_note_gemm_cfg_h(int kernel);
 int gemm_f16x2_nt(const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsi, const float* bias, float* out, int ldo, uint16_t* outp, size_t ops,
                   int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride, int* defer, hipStream_t stream);
 int split_planes_f16(const float* x, uint16_t* planes, int rows, int cols, size_t plane_stride, const float* scale, hipStream_t stream);
@@ -199,6 +202,9 @@ using namespace sdvar;
 struct sdvar_model {
     sdvar_model_desc d;
     int C, H, L, Rmax, lmax, S;
+    // desc.gemm_mode 3 ("f16"): d.gemm_mode holds 2 - the object IS an f16x2 model (planes, weight scales, cache formats, tables, guard, small-M kernels) - and this
+    // flag sends the GEMM launches of calls with at least h16_min_m rows to the half kernel on the high planes (plane_gemm, gemm_plan.h use_half)
+    bool half_tier = false;
     int kv_fmt, Lkv;     // cache format handed to the kernels (0 fp32, 1 fp16, 2 planes) and its row capacity
     const float *shared_w = nullptr, *shared_b = nullptr;   // shared_aln=True: shared_ada_lin.1.{weight (6C,C), bias} (var.py:16-19, 81)
     float* gss_lin = nullptr;  // owned (Rmax, 6C): shared_ada_lin(cond) of the current call
@@ -268,6 +274,14 @@ static inline int begin_of(const sdvar_model* m, int s) { return s == 0 ? 0 : m-
 static int plane_gemm(const sdvar_model* m, const uint16_t* X, size_t xps, const uint16_t* W, size_t wps, const float* wsc, const float* bias, float* out, int ldo,
                       uint16_t* outp, size_t ops, int M, int N, int K, int epi, const float* res, int ldres, const float* gate, int rows_per_gate, int gate_stride,
                       int* defer, hipStream_t s) {
+    if (use_half(m->half_tier ? 3 : m->d.gemm_mode, M)) {
+        // ONE fp16 product on plane 0 of X and W (fp16(clamp(x)) and fp16(w 2^S), K-blocked as gemm_half.hip reads them); the epilogue codes are the same three.  The
+        // GELU epilogue writes the high plane of `outp` only: fc2 of the same call has the same M and reads nothing else.  Unsplit: no slabs for the next row kernel.
+        if (defer) *defer = 0;
+        debug_note_gemm_cfg_h(PLAN_KERNEL_HALF);
+        return gemm_half_ex(X, W, 1, wsc + 1, bias, epi == EPI_BIAS_GELU ? nullptr : out, ldo, epi == EPI_BIAS_GELU ? outp : nullptr, nullptr, res, ldres, gate, rows_per_gate,
+                            gate_stride, M, N, K, epi, s);
+    }
     if (m->d.gemm_mode == 2) return gemm_f16x2_nt(X, xps, W, wps, wsc + 1, bias, out, ldo, outp, ops, M, N, K, epi, res, ldres, gate, rows_per_gate, gate_stride, defer, s);
     return gemm_bf16x3_nt(X, xps, W, wps, bias, out, ldo, outp, ops, M, N, K, epi, res, ldres, gate, rows_per_gate, gate_stride, defer, s);
 }
@@ -286,7 +300,8 @@ int sdvar_model_create(const sdvar_model_desc* desc, sdvar_model_t** out) {
     SDVAR_CHECK_ARG(desc->cvae == 32, "model_create: cvae must be 32 (got %d)", desc->cvae);
     SDVAR_CHECK_ARG(desc->max_batch >= 1 && desc->num_classes >= 1, "model_create: batch/classes");
     SDVAR_CHECK_ARG(desc->kv_dtype == 0 || desc->kv_dtype == 1, "model_create: kv_dtype %d (0 = fp32, 1 = fp16)", desc->kv_dtype);
-    SDVAR_CHECK_ARG(desc->gemm_mode >= 0 && desc->gemm_mode <= 2, "model_create: gemm_mode %d (0 = fp32 MFMA, 1 = bf16x3, 2 = f16x2 split operands)", desc->gemm_mode);
+    SDVAR_CHECK_ARG(desc->gemm_mode >= 0 && desc->gemm_mode <= 3, "model_create: gemm_mode %d (0 = fp32 MFMA, 1 = bf16x3, 2 = f16x2 split operands, 3 = f16)", desc->gemm_mode);
+    SDVAR_CHECK_ARG(desc->gemm_mode != 3 || desc->vocab % 8 == 0, "model_create: gemm_mode 3 needs vocab %% 8 == 0 (got %d)", desc->vocab);
     SDVAR_CHECK_ARG(desc->max_chunk_stages >= 1 && desc->max_chunk_stages <= SDVAR_MAX_STAGES, "model_create: max_chunk_stages %d", desc->max_chunk_stages);
     sdvar_model* m = new sdvar_model();
     struct Guard {          // every early return below (argument error, out of memory) releases what was allocated so far
@@ -296,6 +311,9 @@ int sdvar_model_create(const sdvar_model_desc* desc, sdvar_model_t** out) {
     m->lvl_pos = m->cond = m->cond_silu = m->x0 = m->ada = m->ada_head = m->xn = m->qkv = m->qbuf = m->att = m->hid = nullptr;
     m->xn_p = m->att_p = m->hid_p = m->head_wp = nullptr; m->stage_of_tok = nullptr;
     m->d = *desc;
+    m->half_tier = desc->gemm_mode == 3;
+    if (m->half_tier) m->d.gemm_mode = 2;      // everything below, and every later test of the mode, sees an f16x2 model
+    desc = &m->d;
     m->C = 64 * desc->depth; m->H = desc->depth; m->S = desc->n_stages; m->Rmax = 2 * desc->max_batch;
     int c = 0;
     for (int s = 0; s < m->S; ++s) {
@@ -792,7 +810,8 @@ static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n,
     // 32 .. 80 rows in GEMM mode f16x2 (round 4; stage 1 and the first verify chunk at B = 8): FIVE launches per block instead of eight - LayerNorm + modulation run in the operand prologue of the QKV / fc1 / head
     // launch (gemm_f16x2_rowblk_kernel), the QKV launch finishes q, k and v (no qk_norm_append), fc2 streams K = 4C unsplit (no slabs for the next LayerNorm to sum).
     // The f16x2 guard counts the operand planes ln_modulate writes, so a guarded call keeps the old sequence.
-    const bool RB = m->d.gemm_mode == 2 && (m->kv_fmt == 3 || m->kv_fmt == 4) && !g_guard_on && skip == 0 && gemm_f16x2_rowblk_want(M, C, V, lsum);
+    const bool HALF = use_half(m->half_tier ? 3 : m->d.gemm_mode, M);     // GEMM mode f16, a call of at least h16_min_m rows: every GEMM below on the half kernel
+    const bool RB = !HALF && m->d.gemm_mode == 2 && (m->kv_fmt == 3 || m->kv_fmt == 4) && !g_guard_on && skip == 0 && gemm_f16x2_rowblk_want(M, C, V, lsum);
     for (int i = 0; i < m->d.depth && RB; ++i) {
         const BlockW& b = m->blk[i];
         const float* ada = m->ada + (size_t)i * m->Rmax * 6 * C;
@@ -827,7 +846,7 @@ static int stage_forward_impl(sdvar_model_t* m, float* x, int32_t s0, int32_t n,
         PendingSplitK pq{nullptr, nullptr, nullptr, 0, 1, 0};
         int qk_fused = 0;        // the QKV launch came out unsplit and finished q, k and v in its epilogue (f16x2 planes cache): no qk_norm_append
         if (!(skip & 16)) { ProfScope pp(GC, 2 * dM * 3 * dC * dC, 4 * (dM * dC + 3 * dC * dC + 3 * dM * dC), s);
-          if (P && m->d.gemm_mode == 2 && (m->kv_fmt == 3 || m->kv_fmt == 4)) {
+          if (P && !HALF && m->d.gemm_mode == 2 && (m->kv_fmt == 3 || m->kv_fmt == 4)) {
                    SDVAR_TRY(gemm_f16x2_qkv(m->xn_p, ps, b.qkv_wp, (size_t)3 * C * C, b.wsc + 1, b.qkv_bias, m->qkv, 3 * C, M, 3 * C, C, b.scale_mul, m->qbuf, b.kc, b.vc, lsum, H, m->Lkv,
                                             m->kv_len, m->kv_fmt, dp, &qk_fused, s));
                    if (defer) pq = PendingSplitK{ws, b.qkv_bias, nullptr, defer, 1, 0}; }
@@ -1230,13 +1249,14 @@ int sdvar_debug_set_variant(const char* name, int32_t value) {
     return set_variant_by_name(name, value);
 }
 
-// The plan a GEMM of this shape gets (gemm_plan.h), without launching anything: pure host code, no HIP call.  mode: 0 f32, 1 bf16x3, 2 f16x2; flags: bit 0 the caller
+// The plan a GEMM of this shape gets (gemm_plan.h), without launching anything: pure host code, no HIP call.  mode: 0 f32, 1 bf16x3, 2 f16x2 (with flags bit 3: an f16x2 model of the f16 tier, sdvar_model_desc.gemm_mode 3); flags: bit 0 the caller
 // defers the K-slice sum, bit 1 a QKV epilogue is offered, bit 2 the outputs allow 16-byte accesses; out4 = {kernel code, K split, hybrid tail split, QKV fused}.
 int sdvar_debug_plan_gemm(int32_t mode, int32_t M, int32_t N, int32_t K, int32_t flags, int32_t* out4) {
     SDVAR_CHECK_ARG(out4 && mode >= 0 && mode <= 2, "debug_plan_gemm: mode %d", mode);
     SDVAR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 32 == 0, "debug_plan_gemm: need K %% 32 == 0 (M=%d N=%d K=%d)", M, N, K);
     const size_t wsf = splitk_workspace_floats();
-    const GemmPlan p = mode == 0 ? plan_f32(M, N, K, wsf) : mode == 1 ? plan_bf16x3(M, N, K, wsf) : plan_f16x2(M, N, K, wsf, flags & 1, flags & 2, flags & 4);
+    const GemmPlan p = mode == 0 ? plan_f32(M, N, K, wsf) : mode == 1 ? plan_bf16x3(M, N, K, wsf) : !(flags & 8) ? plan_f16x2(M, N, K, wsf, flags & 1, flags & 2, flags & 4)
+                                                                                                                : plan_f16(M, N, K, wsf, flags & 1, flags & 2, flags & 4);
     out4[0] = p.kernel; out4[1] = p.split; out4[2] = p.tail; out4[3] = p.qkv_fused;
     return SDVAR_OK;
 }

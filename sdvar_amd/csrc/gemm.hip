@@ -198,6 +198,7 @@ Variant g_variants[VAR_COUNT] = {
     {"gemm_v2", nullptr, 1, 0, 1, 1, false, false},                             // bf16x3 128-row tile on the LDS-DMA kernel
     {"stage0_table", "SDVAR_STAGE0_TABLE", 1, 0, 1, 1, false, false},           // stage 0 of a label-conditioned call from the per-class table (api.hip: sdvar_stage_first); 0 = always computed
     {"stage0_table_mb", "SDVAR_STAGE0_TABLE_MB", 1024, 0, 1 << 20, 1024, false, false},      // size cap of that table in MiB; a larger table is not built and stage 0 is computed
+    {"h16_min_m", "SDVAR_H16_MIN_M", 2704, 1, 1 << 30, 2704, false, false},     // GEMM mode f16: rows from which a call runs on the half kernel (gemm_plan.h use_half)
     {nullptr, nullptr, 0, 0, 768, 0, false, false},                             // forced tile, in f16x2's codes (sdvar_debug_set_gemm_cfg); 0 = automatic
     {nullptr, nullptr, 0, -64, 64, 0, false, false},                            // forced K split; < 0 with tile 256: hybrid tail split
 };

@@ -1963,6 +1963,8 @@ void debug_get_gemm_cfg_h(int* out) {
     out[0] = g_last_plan.plan.kernel; out[1] = g_last_plan.plan.split; out[2] = g_last_plan.tail_launches; out[3] = g_last_plan.fused_launches;
     g_last_plan.tail_launches = g_last_plan.fused_launches = 0;
 }
+// api.hip's plane_gemm, GEMM mode f16: the launch went to gemm_half.hip's kernel (code PLAN_KERNEL_HALF), unsplit
+void debug_note_gemm_cfg_h(int kernel) { g_last_plan.plan = GemmPlan{kernel, 1, 0, false}; }
 // api.hip's stage-0 table build runs whole passes inside another call: it puts these diagnostics back as it found them (peek: read without the reset)
 void debug_peek_gemm_cfg_h(int* out) { out[0] = g_last_plan.plan.kernel; out[1] = g_last_plan.plan.split; out[2] = g_last_plan.tail_launches; out[3] = g_last_plan.fused_launches; out[4] = g_last_plan.plan.tail; out[5] = g_last_plan.plan.qkv_fused; }
 void debug_restore_gemm_cfg_h(const int* in) { g_last_plan.plan = GemmPlan{in[0], in[1], in[4], in[5] != 0}; g_last_plan.tail_launches = in[2]; g_last_plan.fused_launches = in[3]; }

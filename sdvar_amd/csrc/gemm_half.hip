@@ -17,6 +17,10 @@
 // Edge rows are clamped on load (row min(m, M - 1)) and never stored; N % 8 == 0 makes every 4-column register group lie inside or outside N as a whole.  No
 // split-K, no atomics: repeats are bit-identical, and an output element's value does not depend on M, N or the tile it falls into (each element is one fp32
 // MFMA chain over k in ascending order).
+//
+// The engine's GEMM mode f16 (api.hip plane_gemm) launches the same kernel on the HIGH planes of f16x2 operands - plane 0 of an activation is fp16(clamp(x)), of a
+// weight fp16(w 2^S), both in this layout: the EX instances (gemm_half_ex, sdvar_op_gemm_h_ex; fp16 only) multiply the fp32 sum by the weight's 2^-S before the bias,
+// saturate the GELU's pre-activation at +-65504 like every f16x2 producer, and add the gated-residual epilogue.  The seam's instances (EX = false) are unchanged.
 #include "../../include/sdvar_hip.h"
 #include "common.h"
 
@@ -26,7 +30,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-enum { GH_EPI_BIAS = 0, GH_EPI_GELU = 1 };
+enum { GH_EPI_BIAS = 0, GH_EPI_GELU = 1, GH_EPI_GATED_RES = 2 };
 constexpr int GH_BM = 128, GH_BN = 128, GH_BK = 32, GH_NS = 4;
 constexpr int GH_STAGE = 2 * 128 * 32;          // half elements per stage (16 KB)
 #define SDVAR_GH_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
@@ -37,6 +41,10 @@ struct GemmHalfArgs {
     void* out; int out_half; int ldo;            // GH_EPI_BIAS: row-major fp32 or half
     uint16_t* h_out; uint16_t* p_out;            // GH_EPI_GELU: h as the K-blocked (M x N) operand; p row-major (M, N) or null
     int M, N, K;
+    // the engine's tier (EX kernels, sdvar_op_gemm_h_ex; fp16 only): v = acc * *scale + bias in every epilogue, and
+    const float* scale;                          // device scalar (the 2^-S of an f16x2 weight's high plane) or null = 1
+    const float* res; int ldres;                 // GH_EPI_GATED_RES: out = res + v * gate[(m / rows_per_gate) * gate_stride + n], all fp32; res may be out
+    const float* gate; int rows_per_gate, gate_stride;
 };
 
 template <bool BF16>
@@ -46,20 +54,37 @@ __device__ __forceinline__ f32x16 gh_mfma(const f16x8& a, const f16x8& b, const 
 }
 
 // One 32 x 32 accumulator tile (transposed layout): this lane's row m, columns nb + 8 g + {0..3} for g = 0..3 (nb already holds the lane half's + 4 lh).
-template <bool BF16, int EPI>
-__device__ __forceinline__ void gh_store_tile(const GemmHalfArgs& a, const f32x16& acc, int m, int nb) {
+// EX (the engine's tier): sc = *a.scale multiplies the fp32 sum before the bias (a power of two, so the fused form rounds like mul + add), the GELU's
+// pre-activation saturates at the fp16 range like every other f16x2 operand producer (split2h), and GH_EPI_GATED_RES exists.
+template <bool BF16, int EPI, bool EX>
+__device__ __forceinline__ void gh_store_tile(const GemmHalfArgs& a, const f32x16& acc, float sc, int m, int nb) {
     if (m >= a.M) return;
+    const size_t grow = (EPI == GH_EPI_GATED_RES) ? (size_t)(m / a.rows_per_gate) * a.gate_stride : 0;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int n = nb + 8 * g;
         if (n >= a.N) continue;                  // N % 8 == 0 and n % 4 == 0: the four columns are inside together
         f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+        if (EX) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] *= sc;
+        }
         if (a.bias) {
             const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + n);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += bv[e];
         }
-        if (EPI == GH_EPI_GELU) {
+        if (EPI == GH_EPI_GATED_RES) {           // each lane reads its four residuals before it writes them: res == out is fine
+            const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + (size_t)m * a.ldres + n);
+            const f32x4 gv = *reinterpret_cast<const f32x4*>(a.gate + grow + n);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rv[e] + v[e] * gv[e];
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + (size_t)m * a.ldo + n) = v;
+        } else if (EPI == GH_EPI_GELU) {
+            if (EX) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = clamp_f16_range(v[e]);
+            }
             uint2 p;                             // p = half(acc + b1); h = half(gelu_tanh(float(p)))
             p.x = half_pack2(v[0], v[1], BF16); p.y = half_pack2(v[2], v[3], BF16);
             if (a.p_out) *reinterpret_cast<uint2*>(a.p_out + (size_t)m * a.N + n) = p;
@@ -77,7 +102,7 @@ __device__ __forceinline__ void gh_store_tile(const GemmHalfArgs& a, const f32x1
     }
 }
 
-template <bool BF16, int EPI>
+template <bool BF16, int EPI, bool EX>
 __global__ __launch_bounds__(512, 2) void gemm_half_kernel(GemmHalfArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t ghsm[];
     constexpr int NS = GH_NS;
@@ -146,8 +171,18 @@ __global__ __launch_bounds__(512, 2) void gemm_half_kernel(GemmHalfArgs a) {
         }
     }
 
+    const float sc = (EX && a.scale) ? *a.scale : 1.0f;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) gh_store_tile<BF16, EPI>(a, acc[i], m0 + wm * 64 + i * 32 + li, n0 + wn * 32 + 4 * lh);
+    for (int i = 0; i < 2; ++i) gh_store_tile<BF16, EPI, EX>(a, acc[i], sc, m0 + wm * 64 + i * 32 + li, n0 + wn * 32 + 4 * lh);
+}
+
+template <bool BF16, int EPI, bool EX>
+static int gh_launch(const GemmHalfArgs& a, hipStream_t stream) {
+    const long long ntile = (long long)((a.M + GH_BM - 1) / GH_BM) * ((a.N + GH_BN - 1) / GH_BN);
+    SDVAR_CHECK_ARG(ntile <= 0x7fffffffLL, "gemm_h: too many tiles");
+    hipLaunchKernelGGL((gemm_half_kernel<BF16, EPI, EX>), dim3((unsigned)ntile), dim3(512), (size_t)GH_NS * GH_STAGE * 2, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
 }
 
 int gemm_half(const void* x, const void* w, int dtype, const float* bias, void* out, int out_dtype, int ldo, void* h_out, void* p_out, int M, int N, int K, int epi,
@@ -166,21 +201,40 @@ int gemm_half(const void* x, const void* w, int dtype, const float* bias, void* 
         SDVAR_CHECK_ARG(h_out && !out, "gemm_h: epilogue 1 writes h_out (and p_out on request), not `out`");
         SDVAR_CHECK_ARG(N % 32 == 0, "gemm_h: epilogue 1 writes the next GEMM's operand: N %% 32 == 0 (N=%d)", N);
     }
-    const long long ntile = (long long)((M + GH_BM - 1) / GH_BM) * ((N + GH_BN - 1) / GH_BN);
-    SDVAR_CHECK_ARG(ntile <= 0x7fffffffLL, "gemm_h: too many tiles");
     const GemmHalfArgs a{reinterpret_cast<const uint16_t*>(x), reinterpret_cast<const uint16_t*>(w), bias, out, out_dtype != 0, ldo,
-                         reinterpret_cast<uint16_t*>(h_out), reinterpret_cast<uint16_t*>(p_out), M, N, K};
-    const size_t lds = (size_t)GH_NS * GH_STAGE * 2;
-    const dim3 grid((unsigned)ntile), block(512);
-    if (dtype == 2) {
-        if (epi == GH_EPI_GELU) hipLaunchKernelGGL((gemm_half_kernel<true, GH_EPI_GELU>), grid, block, lds, stream, a);
-        else hipLaunchKernelGGL((gemm_half_kernel<true, GH_EPI_BIAS>), grid, block, lds, stream, a);
+                         reinterpret_cast<uint16_t*>(h_out), reinterpret_cast<uint16_t*>(p_out), M, N, K, nullptr, nullptr, 0, nullptr, 1, 0};
+    if (dtype == 2) return epi == GH_EPI_GELU ? gh_launch<true, GH_EPI_GELU, false>(a, stream) : gh_launch<true, GH_EPI_BIAS, false>(a, stream);
+    return epi == GH_EPI_GELU ? gh_launch<false, GH_EPI_GELU, false>(a, stream) : gh_launch<false, GH_EPI_BIAS, false>(a, stream);
+}
+
+// The engine's tier (GEMM mode f16, api.hip plane_gemm) and sdvar_op_gemm_h_ex: fp16 operands, fp32 `out`, an optional per-tensor scale and the gated residual.
+int gemm_half_ex(const void* x, const void* w, int dtype, const float* w_scale, const float* bias, float* out, int ldo, void* h_out, void* p_out, const float* res, int ldres,
+                 const float* gate, int rows_per_gate, int gate_stride, int M, int N, int K, int epi, hipStream_t stream) {
+    auto al16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
+    SDVAR_CHECK_ARG(dtype == 1, "gemm_h_ex: dtype %d (1 = fp16; bf16 has no engine tier)", dtype);
+    SDVAR_CHECK_ARG(epi >= GH_EPI_BIAS && epi <= GH_EPI_GATED_RES, "gemm_h_ex: epilogue %d (0 = bias, 1 = bias + GELU -> operand, 2 = gated residual)", epi);
+    SDVAR_CHECK_ARG(x && w, "gemm_h_ex: null operand");
+    SDVAR_CHECK_ARG(M >= 1 && N >= 8 && N % 8 == 0 && K >= 32 && K % 32 == 0 && M <= (1 << 24) && N <= (1 << 24), "gemm_h_ex: need M >= 1, N %% 8 == 0 and K %% 32 == 0 (M=%d N=%d K=%d)", M, N, K);
+    SDVAR_CHECK_ARG(al16(x) && al16(w) && al16(bias) && al16(out) && al16(h_out) && al16(p_out) && al16(res) && al16(gate), "gemm_h_ex: operands must be 16-byte aligned");
+    SDVAR_CHECK_ARG(((uintptr_t)w_scale % 4) == 0, "gemm_h_ex: w_scale must be 4-byte aligned");
+    if (epi == GH_EPI_GELU) {
+        SDVAR_CHECK_ARG(h_out && !out, "gemm_h_ex: epilogue 1 writes h_out (and pre_out on request), not `out`");
+        SDVAR_CHECK_ARG(N % 32 == 0, "gemm_h_ex: epilogue 1 writes the next GEMM's operand: N %% 32 == 0 (N=%d)", N);
     } else {
-        if (epi == GH_EPI_GELU) hipLaunchKernelGGL((gemm_half_kernel<false, GH_EPI_GELU>), grid, block, lds, stream, a);
-        else hipLaunchKernelGGL((gemm_half_kernel<false, GH_EPI_BIAS>), grid, block, lds, stream, a);
+        SDVAR_CHECK_ARG(out && !h_out && !p_out, "gemm_h_ex: epilogue %d writes `out` only", epi);
+        SDVAR_CHECK_ARG(ldo >= N && ldo % 4 == 0, "gemm_h_ex: need ldo >= N and ldo %% 4 == 0 (ldo=%d N=%d)", ldo, N);
     }
-    SDVAR_LAUNCH_CHECK();
-    return SDVAR_OK;
+    if (epi == GH_EPI_GATED_RES) {
+        SDVAR_CHECK_ARG(res && gate, "gemm_h_ex: epilogue 2 needs res and gate");
+        SDVAR_CHECK_ARG(rows_per_gate >= 1, "gemm_h_ex: rows_per_gate %d", rows_per_gate);
+        SDVAR_CHECK_ARG(ldres >= N && ldres % 4 == 0 && gate_stride >= 0 && gate_stride % 4 == 0, "gemm_h_ex: need ldres >= N, ldres %% 4 == 0 and gate_stride %% 4 == 0 (ldres=%d gate_stride=%d)", ldres, gate_stride);
+    } else {
+        SDVAR_CHECK_ARG(!res && !gate, "gemm_h_ex: res / gate belong to epilogue 2");
+    }
+    const GemmHalfArgs a{reinterpret_cast<const uint16_t*>(x), reinterpret_cast<const uint16_t*>(w), bias, out, 0, ldo,
+                         reinterpret_cast<uint16_t*>(h_out), reinterpret_cast<uint16_t*>(p_out), M, N, K, w_scale, res, ldres, gate, rows_per_gate > 0 ? rows_per_gate : 1, gate_stride};
+    if (epi == GH_EPI_GATED_RES) return gh_launch<false, GH_EPI_GATED_RES, true>(a, stream);
+    return epi == GH_EPI_GELU ? gh_launch<false, GH_EPI_GELU, true>(a, stream) : gh_launch<false, GH_EPI_BIAS, true>(a, stream);
 }
 
 }  // namespace sdvar
@@ -189,5 +243,9 @@ extern "C" {
 int sdvar_op_gemm_h(const void* x, const void* w, int32_t dtype, const float* bias, void* out, int32_t out_dtype, int32_t ldo, void* h_out, void* p_out, int32_t M, int32_t N,
                     int32_t K, int32_t epilogue, void* stream) {
     return sdvar::gemm_half(x, w, dtype, bias, out, out_dtype, ldo, h_out, p_out, M, N, K, epilogue, (hipStream_t)stream);
+}
+int sdvar_op_gemm_h_ex(const void* x, const void* w, int32_t dtype, const float* w_scale, const float* bias, float* out, int32_t ldo, void* h_out, void* pre_out, const float* res,
+                       int32_t ldres, const float* gate, int32_t rows_per_gate, int32_t gate_stride, int32_t M, int32_t N, int32_t K, int32_t epilogue, void* stream) {
+    return sdvar::gemm_half_ex(x, w, dtype, w_scale, bias, out, ldo, h_out, pre_out, res, ldres, gate, rows_per_gate, gate_stride, M, N, K, epilogue, (hipStream_t)stream);
 }
 }  // extern "C"

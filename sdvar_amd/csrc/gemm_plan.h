@@ -18,7 +18,7 @@ namespace sdvar {
 // ---- variant table -----------------------------------------------------------------------------------------------------------------------------------------
 // One entry per switch that has a setter.  The value is env-or-default until a setter stores one; a setter value < 0 goes back to env-or-default.  An environment
 // value outside [lo, hi] maps to `fallback`.  The atomics make reads from concurrent host threads safe; the setters are still meant for single-threaded tools.
-enum VariantId { VAR_GEMM_H4, VAR_GEMM_H2_STAGES, VAR_GEMM_SMALL_PP, VAR_ATTN_PP_SCHED, VAR_CONV_PP, VAR_CONV_TAP_REUSE, VAR_ROWBLK, VAR_QKV_FUSE, VAR_GEMM_V2, VAR_STAGE0_TABLE, VAR_STAGE0_TABLE_MB, VAR_FORCE_BM, VAR_FORCE_SPLIT, VAR_COUNT };
+enum VariantId { VAR_GEMM_H4, VAR_GEMM_H2_STAGES, VAR_GEMM_SMALL_PP, VAR_ATTN_PP_SCHED, VAR_CONV_PP, VAR_CONV_TAP_REUSE, VAR_ROWBLK, VAR_QKV_FUSE, VAR_GEMM_V2, VAR_STAGE0_TABLE, VAR_STAGE0_TABLE_MB, VAR_H16_MIN_M, VAR_FORCE_BM, VAR_FORCE_SPLIT, VAR_COUNT };
 
 struct Variant {
     const char* name;           // sdvar_debug_set_variant's name; null: set only through its own ABI function
@@ -78,7 +78,8 @@ float* splitk_workspace(size_t* floats);     // gemm.hip: the calling model's sl
 // ---- planner -----------------------------------------------------------------------------------------------------------------------------------------------
 constexpr int PLAN_BK = 32, PLAN_BN = 128;   // K-step and column tile of every tile family the cost model ranks
 
-// kernel codes: 16 skinny, 17 row-block (never planned: its callers ask for it), 32 / 64 / 128 / 256 = rows of a (rows x 128) tile, 512 = 256 x 256, 768 = 256 x 192
+// kernel codes: 16 skinny, 17 row-block (never planned: its callers ask for it), 32 / 64 / 128 / 256 = rows of a (rows x 128) tile, 512 = 256 x 256, 768 = 256 x 192,
+// 1128 = gemm_half.hip's 128 x 128 kernel on the high planes (GEMM mode f16 only: PLAN_KERNEL_HALF below)
 struct GemmPlan { int kernel; int split; int tail; bool qkv_fused; };
 
 // What a call hands down to its launcher besides the operands: where to report a deferred K-slice sum (null: launch the reduce), the QKV finish the epilogue may
@@ -237,6 +238,15 @@ inline GemmPlan plan_f16x2(int M, int N, int K, size_t ws_floats, bool deferred,
     if (p.kernel == 16) p.kernel = 32;      // forced, but the shape is outside the skinny kernel's range
     p.qkv_fused = qkv && p.split == 1 && p.tail == 0;
     return p;
+}
+
+// GEMM mode 3 ("f16"): an f16x2 model whose GEMM launches of at least h16_min_m rows run as one fp16 product on the high planes (gemm_half.hip, kernel code
+// PLAN_KERNEL_HALF).  The rule depends on the mode and M only, so that fc1 and fc2 of one call (same M) agree on whether the hidden operand has a low plane.
+constexpr int PLAN_KERNEL_HALF = 1128;
+inline bool use_half(int mode, int M) { return mode == 3 && M >= variant(VAR_H16_MIN_M); }
+inline GemmPlan plan_f16(int M, int N, int K, size_t ws_floats, bool deferred, bool qkv_offered, bool vec) {
+    if (use_half(3, M)) return GemmPlan{PLAN_KERNEL_HALF, 1, 0, false};
+    return plan_f16x2(M, N, K, ws_floats, deferred, qkv_offered, vec);
 }
 
 // ---- launch sequence ---------------------------------------------------------------------------------------------------------------------------------------

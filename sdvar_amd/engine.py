@@ -32,6 +32,12 @@ ABI_VERSION = 5
 #   'f16x2' = two fp16 planes per operand (x ~ xh + xl to 2^-22), 3 fp16 MFMA products, fp32 accumulate: half the matrix work of bf16x3 at the same
 #             measured accuracy while activations stay inside the fp16 range (csrc/gemm_f16x2.hip).
 GEMM_MODES = ("f32", "bf16x3", "f16x2")
+#   'f16'   = engine only (ModelCtx, SDVAR_GEMM_MODE, VAR.gemm_mode / tf_gemm_mode): an f16x2 model whose block and head GEMMs run as ONE fp16 product on the high
+#             planes (csrc/gemm_half.hip) in calls of at least `h16_min_m` rows (default 2704, measured: tools/f16_mode_bench.py; sdvar_debug_set_variant / SDVAR_H16_MIN_M); smaller calls are f16x2's,
+#             bit for bit.  fp16-autocast accuracy, NOT the fp32 modes' 1e-3 logit bar: sampled ids differ from the reference's.  See DESIGN.md section 4.
+ENGINE_GEMM_MODES = GEMM_MODES + ("f16",)
+HALF_KERNEL_CODE = 1128                     # last_gemm_cfg()["bm"] / sdvar_debug_plan_gemm's kernel code of the 128 x 128 half kernel
+PLAN_FLAG_F16 = 8                           # sdvar_debug_plan_gemm: mode 2 with this flag bit = the plan of a gemm_mode 'f16' model
 DEFAULT_GEMM_MODE = "f16x2"
 PROF_CLASSES = ("gemm", "attention", "ln_modulate", "qk_norm_append", "sampler", "verify", "quant", "embed_misc", "attention_small", "gemm_small")
 
@@ -140,6 +146,7 @@ _SIGNATURES = {
     "sdvar_op_sdpa_h_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _P, _I, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _D,
                                  _P]),
     "sdvar_op_gemm_h": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "sdvar_op_gemm_h_ex": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sdvar_op_half_operand": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sdvar_op_gelu_bwd_h": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "sdvar_op_grad_operands": (_I, [_P, _I, _I, _I, _I, _P, _P, _U64, _P, _U64, _P, _P]),
@@ -236,9 +243,9 @@ class ModelCtx:
         d.max_batch, d.max_chunk_stages, d.kv_dtype = max_batch, max_chunk, (1 if kv_fp16 else 0)
         self.kv_fp16 = bool(kv_fp16)
         self.gemm_mode = gemm_mode or os.environ.get("SDVAR_GEMM_MODE", DEFAULT_GEMM_MODE)
-        if self.gemm_mode not in GEMM_MODES:
-            raise SdvarError(f"gemm_mode {self.gemm_mode!r}: expected one of {GEMM_MODES}")
-        d.gemm_mode = GEMM_MODES.index(self.gemm_mode)
+        if self.gemm_mode not in ENGINE_GEMM_MODES:
+            raise SdvarError(f"gemm_mode {self.gemm_mode!r}: expected one of {ENGINE_GEMM_MODES}")
+        d.gemm_mode = ENGINE_GEMM_MODES.index(self.gemm_mode)
         for i, p in enumerate(self.lad.patch_nums):
             d.patch_nums[i] = p
         self.h = C.c_void_p()
@@ -1399,9 +1406,43 @@ def img_err_stats(a: torch.Tensor, b: torch.Tensor, sums: torch.Tensor, accumula
     _check(_lib.sdvar_img_err_stats(_ptr(a), _ptr(b), a.numel(), _ptr(sums), int(bool(accumulate)), _stream()))
 
 
+def gemm_h_ex(x: torch.Tensor, w: torch.Tensor, M: int, N: int, K: int, epilogue: int, w_scale: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, ldo: int = 0, h_out: Optional[torch.Tensor] = None, pre_out: Optional[torch.Tensor] = None,
+              res: Optional[torch.Tensor] = None, ldres: int = 0, gate: Optional[torch.Tensor] = None, rows_per_gate: int = 1, gate_stride: int = 0) -> None:
+    """sdvar_op_gemm_h_ex: the half kernel as GEMM mode 'f16' launches it.  x, w: fp16 K-blocked operands (M x K), (N x K) (the high plane of an f16x2 operand);
+    w_scale: one float32 on the device or None; bias (N,) float32 or None.  epilogue 0: out fp32 rows of ldo; 1: h_out = the fp16 operand (M x N) of gelu(.), pre_out
+    (M, N) fp16 or None; 2: out = res + (.) * gate[(m // rows_per_gate) * gate_stride + n], res / out fp32 rows of ldres / ldo (res may be out).  Buffers may be larger
+    than the kernel writes (guard strips); sizes are checked as minimums here, the arithmetic's own constraints by the library.  No host synchronisation."""
+    who = "gemm_h_ex"
+    dev = x.device
+
+    def chk(name, t, dtype, numel):
+        if t is None:
+            return
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_cuda or not t.is_contiguous() or t.numel() < numel:
+            raise SdvarError(f"{who}: {name} must be a contiguous {dtype} tensor of at least {numel} elements on {dev}")
+    if min(M, N, K) < 1:
+        raise SdvarError(f"{who}: M={M} N={N} K={K}")
+    chk("x", x, torch.float16, M * K); chk("w", w, torch.float16, N * K)
+    chk("w_scale", w_scale, torch.float32, 1); chk("bias", bias, torch.float32, N)
+    chk("out", out, torch.float32, (M - 1) * ldo + N); chk("res", res, torch.float32, (M - 1) * ldres + N)
+    chk("h_out", h_out, torch.float16, M * N); chk("pre_out", pre_out, torch.float16, M * N)
+    if gate is not None:
+        chk("gate", gate, torch.float32, ((M - 1) // max(rows_per_gate, 1)) * gate_stride + N)
+    lib = load_library()
+    with _on_device(dev):
+        _check(lib.sdvar_op_gemm_h_ex(_addr(x), _addr(w), 1, _addr(w_scale), _addr(bias), _addr(out), ldo, _addr(h_out), _addr(pre_out), _addr(res), ldres, _addr(gate),
+                                      rows_per_gate, gate_stride, M, N, K, epilogue, _stream()))
+
+
+def set_variant(name: str, value: int) -> None:
+    """sdvar_debug_set_variant: a process-wide kernel switch by name (csrc/gemm_plan.h), e.g. 'h16_min_m'; value < 0 = back to the environment / default."""
+    _check(load_library().sdvar_debug_set_variant(name.encode(), int(value)))
+
+
 def last_gemm_cfg() -> Dict[str, int]:
     """Test aid: row tile and K split of the last f16x2 GEMM call of this thread, and how many launches since the last read took the hybrid tail split /
-    finished q and k in the QKV epilogue (reading resets the two counters)."""
+    finished q and k in the QKV epilogue (reading resets the two counters).  bm == HALF_KERNEL_CODE: the last launch was mode f16's half kernel."""
     v = (_I * 4)()
     _check(load_library().sdvar_debug_get_gemm_cfg(v))
     return dict(bm=v[0], split=v[1], tail_launches=v[2], fused_qkv_launches=v[3])
@@ -1508,6 +1549,14 @@ class Sampler:
         qz.next_h(si, h, f_hat, None if last else nxt, B)
         return masked
 
+    def _f16_stats(self, stats: Dict[str, object]):
+        """GEMM mode f16 only: stats['gemm_mode'] = (target's, draft's) and stats['last_gemm_half'] = whether the call's last GEMM launch (the head of its last forward)
+        ran on the half kernel, i.e. whether that forward had at least h16_min_m rows."""
+        modes = (self.t.gemm_mode, self.d.gemm_mode if self.d is not None else None)
+        if "f16" in modes:
+            stats["gemm_mode"] = modes
+            stats["last_gemm_half"] = last_gemm_cfg()["bm"] == HALF_KERNEL_CODE
+
     @property
     def f_snap(self):
         return self._fs[self._slot]
@@ -1538,6 +1587,7 @@ class Sampler:
                     m.embed_next(self.nxt[0], si + 1, self.x_t, lad.lens[si + 1], 0)
             m.kv_set_len(0)
         res.stats = dict(target_calls=S, draft_stage_calls=0, forced_accepts=0, accepted_tokens=0)
+        self._f16_stats(res.stats)
         if _GUARD_ON:
             res.stats["f16x2_guard"] = f16x2_guard_collect()
         return res
@@ -1818,6 +1868,7 @@ class Sampler:
             optimistic = n_acc == g and not forced
             self.spec_commit(st, n_acc, forced, acc_tok)
         self.spec_end(st)
+        self._f16_stats(res.stats)
         if _GUARD_ON:
             res.stats["f16x2_guard"] = f16x2_guard_collect()
         return res

@@ -111,7 +111,9 @@ class VAR(nn.Module):
         self._quant: Optional[E.QuantCtx] = None
         self._tf_ctx: Optional[E.ModelCtx] = None   # VAR.forward's own model object (teacher forcing): the sampler's context stays untouched
         self.tf_pass_images = TF_PASS_IMAGES
-        self.tf_gemm_mode: Optional[str] = None     # GEMM arithmetic of VAR.forward (engine.GEMM_MODES; None = the engine default)
+        self.tf_gemm_mode: Optional[str] = None     # GEMM arithmetic of VAR.forward (engine.ENGINE_GEMM_MODES; None = the engine default)
+        self.gemm_mode: Optional[str] = None        # GEMM arithmetic of the sampler's model object (engine.ENGINE_GEMM_MODES; None = the engine default); 'f16' = the opt-in
+                                                    # fp16 tier for the large stages: not fp32-accurate, sampled ids differ from the reference's
         self.noise_kind = "device"                  # 'device' | 'host' | 'torch' (sdvar_amd.engine.Noise)
         self.last_result: Optional[E.SampleResult] = None
 
@@ -141,10 +143,10 @@ class VAR(nn.Module):
         if dev.type != "cuda":
             raise E.SdvarError("the sampler runs on an MI355X: move the model to a cuda (HIP) device; there is no CPU path")
         c = self._ctx
-        if c is None or c.max_batch < max_batch or c.max_chunk < max_chunk or c.device != dev:
+        if c is None or c.max_batch < max_batch or c.max_chunk < max_chunk or c.device != dev or c.gemm_mode != (self.gemm_mode or c.gemm_mode):
             if c is not None:
                 c.close()
-            self._ctx = E.ModelCtx(self.state_dict(), self.depth, self.patch_nums, max_batch, max_chunk, dev, self.num_classes)
+            self._ctx = E.ModelCtx(self.state_dict(), self.depth, self.patch_nums, max_batch, max_chunk, dev, self.num_classes, gemm_mode=self.gemm_mode)
             self._sampler = None
         return self._ctx
 
