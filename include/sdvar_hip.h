@@ -173,7 +173,9 @@ typedef struct {
     int32_t num_res_blocks;                 /* 2: every decoder level has num_res_blocks + 1 ResnetBlocks (basic_vae.py:196) */
     int32_t max_batch;
     int32_t latent_hw;                      /* side of f_hat: 16 for 256^2 images, 32 for 512^2 */
-    int32_t plane_format;                   /* operands of the convolutions: 0 or 2 = f16x2 (two fp16 planes, three MFMA products), 3 = bf16x3 */
+    int32_t plane_format;                   /* operands of the convolutions: 0 or 2 = f16x2 (two fp16 planes, three MFMA products), 3 = bf16x3;
+                                               sdvar_vae_create only: 6 = an f16x2 decoder whose conv_planes launches multiply plane 0 with plane 0 and nothing else
+                                               (opt-in: NOT fp32-accurate; conv_out, GroupNorm and attention are unchanged).  sdvar_vae_enc_create rejects 6 */
 } sdvar_vae_desc;
 int sdvar_vae_create(const sdvar_vae_desc* desc /*host*/, sdvar_vae_t** out /*host*/);
 int sdvar_vae_destroy(sdvar_vae_t* v);
@@ -391,7 +393,11 @@ int sdvar_op_vae_s2d_weights(const float* w, float* w_s2d, int32_t Cout, int32_t
 /* nearest code of z (N, cvae = 32) in codebook (V, cvae): ids (N) int64, ties to the lowest index; e2 (V floats) receives |e_v|^2 */
 int sdvar_op_quant_nearest(const float* z, int32_t N, const float* codebook, int32_t V, int32_t cvae, float* e2, int64_t* ids, void* stream);
 /* out[B H W][N] = conv(x planes of a (B,Cin,H,W) tensor, w planes) + bias (+ res[B H W][N]); taps = 9: 3x3 pad 1, taps = 1: 1x1.  x_row0 =
- * guard rows (>= W+3).  workspace: split-K slabs (may be NULL: no split); force_split > 0 overrides the heuristic. */
+ * guard rows (>= W+3).  workspace: split-K slabs (may be NULL: no split); force_split > 0 overrides the heuristic.
+ * plane_format: 3 = bf16x3, 2 = f16x2 (three fp16 products), 6 = f16x2 planes multiplied as ONE product, x plane 0 times w plane 0 (plane 1 of either operand is never
+ * read; fp32 accumulation, same epilogues; N % 4 == 0 or SDVAR_ERR_ARG).  The operands of format 6 are format-2 planes: pack and produce them with plane_format 2.
+ * Format 6 runs the one-product instances of the "conv_pp" 2 loop and of the tap-reuse loop (same eligibility rule) whatever "conv_pp" says; "conv_tap_reuse" 0 still
+ * forces the per-tap loop. */
 int sdvar_op_conv_planes(const uint16_t* x_planes, uint64_t x_plane_stride, uint64_t x_rows, int32_t x_row0, const uint16_t* w_planes, uint64_t w_plane_stride,
                          int32_t plane_format, const float* w_scale, const float* bias, const float* res, float* out, int32_t B, int32_t H, int32_t W, int32_t N,
                          int32_t Cin, int32_t taps, float* workspace, uint64_t workspace_floats, int32_t force_split, void* stream);
@@ -453,8 +459,8 @@ int sdvar_debug_get_gemm_cfg(int32_t* out4);
 /* test aid: out1[0] = 1 if the LAST convolution launch (sdvar_op_conv_planes / _ex, the decoder's convolutions) of this host thread took the tap-reuse K loop
  * (f16x2 planes, "conv_pp" 2, "conv_tap_reuse" 1, 3x3 or fused up-sampling taps, no split-K, H W % 256 == 0, W % 256 == 0 or 256 % W == 0 with W >= 64), else 0. */
 int sdvar_debug_get_conv_cfg(int32_t* out1);
-/* test aid: out4 = what the LAST convolution launch of this host thread ran: {kernel: 0 bf16x3 | 1 f16x2 | 2 f16x2 tap-reuse; the "conv_pp" loop actually used (2 falls
- * back to 1 when N % 4 != 0; 0 for bf16x3, which has one loop); the K split actually used (1 = none; a forced split is rounded to the number of non-empty slices);
+/* test aid: out4 = what the LAST convolution launch of this host thread ran: {kernel: 0 bf16x3 | 1 f16x2 | 2 f16x2 tap-reuse | 3 one-product per-tap | 4 one-product
+ * tap-reuse (plane_format 6); the "conv_pp" loop actually used (2 falls back to 1 when N % 4 != 0; 0 for bf16x3, which has one loop; always 2 for plane_format 6); the K split actually used (1 = none; a forced split is rounded to the number of non-empty slices);
  * 1 if the GroupNorm statistics were fused into the epilogue}.  All four are -1 before the first launch.  Thread-local, like sdvar_debug_get_conv_cfg. */
 int sdvar_debug_get_conv_plan(int32_t* out4);
 /* The GEMM planner (csrc/gemm_plan.h) on its own: what a GEMM of this shape would launch.  Pure host code - no HIP call, no GPU needed; a pure function of the

@@ -187,6 +187,8 @@ __device__ __forceinline__ void gelu_val_grad(float x, int kind, float& g, float
 
 // Output-plane format of the producers of GEMM operands (ln_modulate, attention, GELU epilogues): none, three bf16 planes, two fp16 planes
 enum { PLANES_NONE = 0, PLANES_F16X2 = 2, PLANES_BF16X3 = 3 };
+// conv_planes only: operands are PLANES_F16X2 planes (written by the producers under that code), multiplied as ONE product, X plane 0 x W plane 0
+enum { PLANES_F16X2_HH = 6 };
 // four consecutive values of one row -> the packed 8-byte words of each plane, written at the K-blocked position
 __device__ __forceinline__ void store_planes4(uint16_t* outp, size_t ops, size_t o, const float* v, int fmt) {
     if (fmt == PLANES_F16X2) {

@@ -16,6 +16,8 @@
 // 78 KB, XOR-swizzled 64-byte rows (conflict-free ds_read_b128), hand-placed fragment reads with counted lgkmcnt, the
 // DMA instructions of the next K-step spread between the MFMA groups (as gemm_bf16x3_v3_kernel).
 // conv_f16x2_reuse_kernel (f16x2 planes, the decoder's 64^2 .. 256^2 levels): the X rows are staged once per row of taps instead of once per tap.
+// PLANES_F16X2_HH (the decoder's opt-in conv mode "f16"): the NP = 1 instances of conv_f16x2_kernel<EPI, 2> and conv_f16x2_reuse_kernel multiply plane 0 of X with
+// plane 0 of W and nothing else - one MFMA per (row tile, column tile) and K-step where there are three; not fp32-accurate.
 #include <stdlib.h>
 
 #include "common.h"
@@ -354,8 +356,11 @@ __global__ __launch_bounds__(512, 2) void conv_bf16x3_kernel(ConvArgs a) {
 //     waves 4-7:  M1(t-1) L0(t)  M0(t)   L1(t)        Ms = its 15 MFMAs (5 column tiles x 3 plane products)
 // with an s_barrier between slots.  K-step t + 1 is read from slot 4t + 4 on: every wave waits for its own share (counted vmcnt) at the end of slot 4t + 3.
 // PP = 0: the round-2 loop (one barrier per K-step, every wave reads, then multiplies).
-template <int EPI, int PP>
+// NP = 1 (PP = 2 only; PLANES_F16X2_HH): one product, X plane 0 x W plane 0.  Same stage layout, but plane 1 of X and W is neither brought into LDS nor read:
+// 4 DMA instructions per K-step on waves 0-1 and 3 on the others (8 / 6 with NP = 3), 10 fragment reads and 20 MFMAs per wave (24 / 60).
+template <int EPI, int PP, int NP = 3>
 __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
+    static_assert(NP == 3 || (NP == 1 && PP == 2), "one-product form: PP = 2 only");
     extern __shared__ __attribute__((aligned(16))) uint16_t csm[];
     const int tiles_m = (a.M + CBM - 1) / CBM, tiles_n = (a.N + CBN - 1) / CBN, ntile = tiles_m * tiles_n;
     const int ks = blockIdx.x / ntile;
@@ -400,11 +405,12 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
     auto issue_one = [&](uint16_t* st, int q) {
         if (q < 6) {
             const int p = q / 3, kind = q % 3;
+            if (NP == 1 && p) return;
             if (kind < 2 && skx) return;
             if (kind == 0) SDVAR_DMA16(lx0, ux + p * a.xps * 2, SDVAR_LDS_ADDR(st + p * 8192 + swave * 1024));
             else if (kind == 1) SDVAR_DMA16(lx1, ux + p * a.xps * 2, SDVAR_LDS_ADDR(st + p * 8192 + swave * 1024 + 512));
             else SDVAR_DMA16(lw0, uw + p * a.wps * 2, SDVAR_LDS_ADDR(st + 2 * 8192 + p * 5120 + swave * 512));
-        } else if (two_w) {
+        } else if (two_w && (NP == 3 || q == 6)) {
             const int p = q - 6;
             SDVAR_DMA16(lw1, uw + p * a.wps * 2, SDVAR_LDS_ADDR(st + 2 * 8192 + p * 5120 + 4096 + swave * 512));
         }
@@ -434,18 +440,27 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
         // + DMA slots 0-3, M0 = 2 x 5 x 3 = 30 MFMAs (480 matrix-pipe cycles), L1 = W tiles 5-9 (10 reads) + DMA slots 4-7, M1 = 30 MFMAs.
         const int late = __builtin_amdgcn_readfirstlane(wave >> 2);
         const int l15 = lane & 15, lq = lane >> 4;
-        auto wait_next = [&](int t) {
+        auto wait_next = [&](int t) {          // K-step t + 1 landed: the instructions of K-step t + 2 of THIS wave, if requested, may stay in flight
+            if (NP == 1) {                     // X group 0, X group 1, W group 0 (+ W group 1 on waves 0-1) of plane 0
+                if (t + 2 < nk && skx) { if (two_w) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); }
+                else if (t + 2 < nk) { if (two_w) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                return;
+            }
             if (t + 2 < nk && skx) { if (two_w) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }     // the newest step has W only
             else if (t + 2 < nk) { if (two_w) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         };
 #define SDVAR_C_SLOT() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define SDVAR_LDS_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
+#define SDVAR_LDS_RD1(dst, addr, off) do { if constexpr (NP == 3) SDVAR_LDS_RD(dst, addr, off); } while (0)          // plane 1: not read by the one-product form
 #define SDVAR_C_MFMA16(J0)                                                                                      \
         _Pragma("unroll") for (int j = 0; j < 5; ++j)                                                           \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                     \
+                if constexpr (NP == 3) {                                                                        \
                 acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][0], fx[i][1], acc16[i][(J0) + j], 0, 0, 0);   \
                 acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][1], fx[i][0], acc16[i][(J0) + j], 0, 0, 0);   \
+                }                                                                                               \
                 acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][0], fx[i][0], acc16[i][(J0) + j], 0, 0, 0);   \
             }
         cf32x4 acc16[2][10];
@@ -469,10 +484,10 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
             const uint32_t sb = (uint32_t)(uintptr_t)(lds_ptr_t)(csm + (t % 3) * CSTAGE_H);
             const uint32_t xa = sb + fxo, wa = sb + fwo;
             // ---- L0(t)
-            SDVAR_LDS_RD(fx[0][0], xa, 0); SDVAR_LDS_RD(fx[0][1], xa, 16384); SDVAR_LDS_RD(fx[1][0], xa, 1024); SDVAR_LDS_RD(fx[1][1], xa, 17408);
-            SDVAR_LDS_RD(fw[0][0], wa, 0);    SDVAR_LDS_RD(fw[0][1], wa, 10240); SDVAR_LDS_RD(fw[1][0], wa, 1024); SDVAR_LDS_RD(fw[1][1], wa, 11264);
-            SDVAR_LDS_RD(fw[2][0], wa, 2048); SDVAR_LDS_RD(fw[2][1], wa, 12288); SDVAR_LDS_RD(fw[3][0], wa, 3072); SDVAR_LDS_RD(fw[3][1], wa, 13312);
-            SDVAR_LDS_RD(fw[4][0], wa, 4096); SDVAR_LDS_RD(fw[4][1], wa, 14336);
+            SDVAR_LDS_RD(fx[0][0], xa, 0); SDVAR_LDS_RD1(fx[0][1], xa, 16384); SDVAR_LDS_RD(fx[1][0], xa, 1024); SDVAR_LDS_RD1(fx[1][1], xa, 17408);
+            SDVAR_LDS_RD(fw[0][0], wa, 0);    SDVAR_LDS_RD1(fw[0][1], wa, 10240); SDVAR_LDS_RD(fw[1][0], wa, 1024); SDVAR_LDS_RD1(fw[1][1], wa, 11264);
+            SDVAR_LDS_RD(fw[2][0], wa, 2048); SDVAR_LDS_RD1(fw[2][1], wa, 12288); SDVAR_LDS_RD(fw[3][0], wa, 3072); SDVAR_LDS_RD1(fw[3][1], wa, 13312);
+            SDVAR_LDS_RD(fw[4][0], wa, 4096); SDVAR_LDS_RD1(fw[4][1], wa, 14336);
             if (pf) {
                 set_next();
 #pragma unroll
@@ -483,9 +498,9 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
             SDVAR_C_MFMA16(0);                   // M0(t): column tiles 0-4
             SDVAR_C_SLOT();
             // ---- L1(t)
-            SDVAR_LDS_RD(fw[0][0], wa, 5120); SDVAR_LDS_RD(fw[0][1], wa, 15360); SDVAR_LDS_RD(fw[1][0], wa, 6144); SDVAR_LDS_RD(fw[1][1], wa, 16384);
-            SDVAR_LDS_RD(fw[2][0], wa, 7168); SDVAR_LDS_RD(fw[2][1], wa, 17408); SDVAR_LDS_RD(fw[3][0], wa, 8192); SDVAR_LDS_RD(fw[3][1], wa, 18432);
-            SDVAR_LDS_RD(fw[4][0], wa, 9216); SDVAR_LDS_RD(fw[4][1], wa, 19456);
+            SDVAR_LDS_RD(fw[0][0], wa, 5120); SDVAR_LDS_RD1(fw[0][1], wa, 15360); SDVAR_LDS_RD(fw[1][0], wa, 6144); SDVAR_LDS_RD1(fw[1][1], wa, 16384);
+            SDVAR_LDS_RD(fw[2][0], wa, 7168); SDVAR_LDS_RD1(fw[2][1], wa, 17408); SDVAR_LDS_RD(fw[3][0], wa, 8192); SDVAR_LDS_RD1(fw[3][1], wa, 18432);
+            SDVAR_LDS_RD(fw[4][0], wa, 9216); SDVAR_LDS_RD1(fw[4][1], wa, 19456);
             if (pf) {
 #pragma unroll
                 for (int q = 4; q < 8; ++q) issue_one(nst, q);
@@ -499,6 +514,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(ConvArgs a) {
         }
         if (!late) SDVAR_C_SLOT();
 #undef SDVAR_C_MFMA16
+#undef SDVAR_LDS_RD1
 #undef SDVAR_LDS_RD
 #undef SDVAR_C_SLOT
         if (SDVAR_CDBG(a, 1)) return;
@@ -651,7 +667,21 @@ __device__ __forceinline__ void conv_vm_wait(int n) {          // s_waitcnt vmcn
     }
 }
 
-template <int EPI, int TW>
+// the one-product form's counts (1 .. 5: per K-step at most 2 X + 1 X row group 16 + 2 W instructions); a function of its own keeps conv_vm_wait's code as it is
+__device__ __forceinline__ void conv_vm_wait_hh(int n) {
+    switch (n) {
+        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+}
+
+// NP = 1 (PLANES_F16X2_HH): one product, X plane 0 x W plane 0.  Same rings, plane 1 of either operand neither staged nor read.  DMA instructions per wave:
+// X part 0: 1 (+ 1 on wave 2: row group 16), part 1: 1; a W block: 2 on waves 0-1, 1 on the others - the waits count those.
+template <int EPI, int TW, int NP = 3>
 __global__ __launch_bounds__(512, 2) void conv_f16x2_reuse_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t csm[];
     const int tiles_n = (a.N + CBN - 1) / CBN, ntile = (a.M / CBM) * tiles_n;
@@ -680,8 +710,8 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_reuse_kernel(ConvArgs a) {
     const int wr0 = 16 * wave + r16, wr1 = 128 + wr0;
     const int cw0 = (lane & 3) ^ ((wr0 >> 2) & 3), cw1 = (lane & 3) ^ ((wr1 >> 2) & 3);
     const uint32_t lw0 = (uint32_t)(min(n0 + wr0, a.N - 1) * 32 + 8 * cw0) * 2u, lw1 = (uint32_t)(min(n0 + wr1, a.N - 1) * 32 + 8 * cw1) * 2u;
-    const bool two_w = swave < 2, x17 = swave == 2 || swave == 3;
-    const int nw = two_w ? 4 : 2;                                         // DMA instructions of this wave per W block
+    const bool two_w = swave < 2, x17 = swave == 2 || (NP == 3 && swave == 3);
+    const int nw = (two_w ? 4 : 2) / (NP == 3 ? 1 : 2);                                       // DMA instructions of this wave per W block
     const int ng = TW * a.cb, nk = TW * ng;                               // X groups (dy, c); K-steps
 
     uint16_t* const wring = csm + 2 * CXSTAGE_R;
@@ -692,23 +722,23 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_reuse_kernel(ConvArgs a) {
         const char* ux = reinterpret_cast<const char*>(a.X) + ((long long)xc * (long long)a.x_rows + shift) * 64;
         if (part == 0) {
             SDVAR_DMA16(lxa, ux, SDVAR_LDS_ADDR(xs + swave * 512));
-            SDVAR_DMA16(lxa, ux + a.xps * 2, SDVAR_LDS_ADDR(xs + CXR * 32 + swave * 512));
+            if (NP == 3) SDVAR_DMA16(lxa, ux + a.xps * 2, SDVAR_LDS_ADDR(xs + CXR * 32 + swave * 512));
             if (x17) SDVAR_DMA16(lxc, ux + (swave - 2) * a.xps * 2, SDVAR_LDS_ADDR(xs + (swave - 2) * CXR * 32 + 16 * 512));
         } else {
             SDVAR_DMA16(lxb, ux, SDVAR_LDS_ADDR(xs + (swave + 8) * 512));
-            SDVAR_DMA16(lxb, ux + a.xps * 2, SDVAR_LDS_ADDR(xs + CXR * 32 + (swave + 8) * 512));
+            if (NP == 3) SDVAR_DMA16(lxb, ux + a.xps * 2, SDVAR_LDS_ADDR(xs + CXR * 32 + (swave + 8) * 512));
         }
     };
     auto x_adv = [&]() { if (++xc == a.cb) { xc = 0; ++xy; } };
-    const int nx0 = x17 ? 3 : 2;                                          // DMA instructions of part 0 (part 1: 2)
+    const int nx1 = NP == 3 ? 2 : 1, nx0 = NP == 3 ? (x17 ? 3 : 2) : (x17 ? 2 : 1);          // DMA instructions of part 1 and of part 0
     int wy = 0, wc = 0, wx = 0;                                           // the next W block to issue: tap (wy, wx), channel block wc
     auto issue_w = [&](uint16_t* ws) {
         const char* uw = reinterpret_cast<const char*>(Wp) + (size_t)((wy * TW + wx) * a.cb + wc) * a.N * 64;
         SDVAR_DMA16(lw0, uw, SDVAR_LDS_ADDR(ws + swave * 512));
-        SDVAR_DMA16(lw0, uw + a.wps * 2, SDVAR_LDS_ADDR(ws + 5120 + swave * 512));
+        if (NP == 3) SDVAR_DMA16(lw0, uw + a.wps * 2, SDVAR_LDS_ADDR(ws + 5120 + swave * 512));
         if (two_w) {
             SDVAR_DMA16(lw1, uw, SDVAR_LDS_ADDR(ws + 4096 + swave * 512));
-            SDVAR_DMA16(lw1, uw + a.wps * 2, SDVAR_LDS_ADDR(ws + 5120 + 4096 + swave * 512));
+            if (NP == 3) SDVAR_DMA16(lw1, uw + a.wps * 2, SDVAR_LDS_ADDR(ws + 5120 + 4096 + swave * 512));
         }
         if (++wx == TW) { wx = 0; if (++wc == a.cb) { wc = 0; ++wy; } }
     };
@@ -741,14 +771,18 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_reuse_kernel(ConvArgs a) {
 
 #define SDVAR_C_SLOT() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define SDVAR_LDS_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
+#define SDVAR_LDS_RD1(dst, addr, off) do { if constexpr (NP == 3) SDVAR_LDS_RD(dst, addr, off); } while (0)          // plane 1: not read by the one-product form
 #define SDVAR_C_MFMA16(J0)                                                                                      \
     _Pragma("unroll") for (int j = 0; j < 5; ++j)                                                               \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
+            if constexpr (NP == 3) {                                                                        \
             acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][0], fx[i][1], acc16[i][(J0) + j], 0, 0, 0);   \
             acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][1], fx[i][0], acc16[i][(J0) + j], 0, 0, 0);   \
+            }                                                                                               \
             acc16[i][(J0) + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[j][0], fx[i][0], acc16[i][(J0) + j], 0, 0, 0);   \
         }
-    conv_vm_wait(nw);                                    // X group 0 and W block 0 landed; W block 1 may be in flight
+    auto vm_wait = [&](int n) { if (NP == 3) conv_vm_wait(n); else conv_vm_wait_hh(n); };
+    vm_wait(nw);                                         // X group 0 and W block 0 landed; W block 1 may be in flight
     SDVAR_C_SLOT();
     if (late) SDVAR_C_SLOT();
     f16x8 fx[2][2], fw[5][2];                            // [row tile][plane], [column tile of the half][plane]
@@ -765,34 +799,35 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_reuse_kernel(ConvArgs a) {
             const uint32_t wa = wb0 + (uint32_t)(t & 3) * (uint32_t)(CWSTAGE_R * 2);
             int issued = 0;
             // ---- L0(t)
-            SDVAR_LDS_RD(fx[0][0], xa0, 0); SDVAR_LDS_RD(fx[0][1], xa0, 17408); SDVAR_LDS_RD(fx[1][0], xa1, 0); SDVAR_LDS_RD(fx[1][1], xa1, 17408);
-            SDVAR_LDS_RD(fw[0][0], wa, 0);    SDVAR_LDS_RD(fw[0][1], wa, 10240); SDVAR_LDS_RD(fw[1][0], wa, 1024); SDVAR_LDS_RD(fw[1][1], wa, 11264);
-            SDVAR_LDS_RD(fw[2][0], wa, 2048); SDVAR_LDS_RD(fw[2][1], wa, 12288); SDVAR_LDS_RD(fw[3][0], wa, 3072); SDVAR_LDS_RD(fw[3][1], wa, 13312);
-            SDVAR_LDS_RD(fw[4][0], wa, 4096); SDVAR_LDS_RD(fw[4][1], wa, 14336);
+            SDVAR_LDS_RD(fx[0][0], xa0, 0); SDVAR_LDS_RD1(fx[0][1], xa0, 17408); SDVAR_LDS_RD(fx[1][0], xa1, 0); SDVAR_LDS_RD1(fx[1][1], xa1, 17408);
+            SDVAR_LDS_RD(fw[0][0], wa, 0);    SDVAR_LDS_RD1(fw[0][1], wa, 10240); SDVAR_LDS_RD(fw[1][0], wa, 1024); SDVAR_LDS_RD1(fw[1][1], wa, 11264);
+            SDVAR_LDS_RD(fw[2][0], wa, 2048); SDVAR_LDS_RD1(fw[2][1], wa, 12288); SDVAR_LDS_RD(fw[3][0], wa, 3072); SDVAR_LDS_RD1(fw[3][1], wa, 13312);
+            SDVAR_LDS_RD(fw[4][0], wa, 4096); SDVAR_LDS_RD1(fw[4][1], wa, 14336);
             if (xpf) {
                 if (dx == 0) { issue_x(xn, 0); issued += nx0; }
-                if (dx == TW - 2) { issue_x(xn, 1); issued += 2; }
+                if (dx == TW - 2) { issue_x(xn, 1); issued += nx1; }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             SDVAR_C_SLOT();
             SDVAR_C_MFMA16(0);                           // M0(t): column tiles 0-4
             SDVAR_C_SLOT();
             // ---- L1(t)
-            SDVAR_LDS_RD(fw[0][0], wa, 5120); SDVAR_LDS_RD(fw[0][1], wa, 15360); SDVAR_LDS_RD(fw[1][0], wa, 6144); SDVAR_LDS_RD(fw[1][1], wa, 16384);
-            SDVAR_LDS_RD(fw[2][0], wa, 7168); SDVAR_LDS_RD(fw[2][1], wa, 17408); SDVAR_LDS_RD(fw[3][0], wa, 8192); SDVAR_LDS_RD(fw[3][1], wa, 18432);
-            SDVAR_LDS_RD(fw[4][0], wa, 9216); SDVAR_LDS_RD(fw[4][1], wa, 19456);
+            SDVAR_LDS_RD(fw[0][0], wa, 5120); SDVAR_LDS_RD1(fw[0][1], wa, 15360); SDVAR_LDS_RD(fw[1][0], wa, 6144); SDVAR_LDS_RD1(fw[1][1], wa, 16384);
+            SDVAR_LDS_RD(fw[2][0], wa, 7168); SDVAR_LDS_RD1(fw[2][1], wa, 17408); SDVAR_LDS_RD(fw[3][0], wa, 8192); SDVAR_LDS_RD1(fw[3][1], wa, 18432);
+            SDVAR_LDS_RD(fw[4][0], wa, 9216); SDVAR_LDS_RD1(fw[4][1], wa, 19456);
             if (wpf) { issue_w(wring + ((t + 2) & 3) * CWSTAGE_R); issued += nw; }
-            if (late) conv_vm_wait(issued);
+            if (late) vm_wait(issued);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             SDVAR_C_SLOT();
             SDVAR_C_MFMA16(5);                           // M1(t): column tiles 5-9
-            if (!late) conv_vm_wait(issued);
+            if (!late) vm_wait(issued);
             SDVAR_C_SLOT();
         }
         if (xpf) x_adv();
     }
     if (!late) SDVAR_C_SLOT();
 #undef SDVAR_C_MFMA16
+#undef SDVAR_LDS_RD1
 #undef SDVAR_LDS_RD
 #undef SDVAR_C_SLOT
     if (SDVAR_CDBG(a, 1)) return;
@@ -875,9 +910,13 @@ int upconv_weights(const float* w, float* weff, int Cout, int Cin, hipStream_t s
 
 static thread_local int g_conv_last_reuse = 0;      // 1: the last conv_planes launch of this host thread took conv_f16x2_reuse_kernel (test aid)
 int debug_get_conv_tap_reuse() { return g_conv_last_reuse; }
-static thread_local int g_conv_last_plan[4] = {-1, -1, -1, -1};      // {kernel 0 bf16x3 | 1 f16x2 | 2 f16x2 tap-reuse, conv_pp used, K split used, statistics fused} of that launch (test aid)
+static thread_local int g_conv_last_plan[4] = {-1, -1, -1, -1};      // {kernel 0 bf16x3 | 1 f16x2 | 2 f16x2 tap-reuse | 3 one-product per-tap | 4 one-product tap-reuse, conv_pp used, K split used, statistics fused} of that launch (test aid)
 void debug_get_conv_plan(int* out4) { for (int i = 0; i < 4; ++i) out4[i] = g_conv_last_plan[i]; }
 
+// K-step cost of the one-product per-tap loop in conv_choose_split's units.  Not a cycle count: the value at which the heuristic's choices cost least in MEASURED time
+// over the split shapes of the ch = 160 decoder at B = 8 (the 16^2 and 32^2 levels, every K split timed: tools/f16_conv_bench.py section f):
+// 1800 -> 1.008 of the best split per shape; 1400 - 2800 stay within 1.025, 800 - 1200 (f16x2's value) 1.04, 500 - 700 1.1.
+constexpr double CONV_KSTEP_HH = 1800.0;
 // split heuristic: fill the 256 CUs (one resident workgroup each) without leaving a mostly empty last round
 static int conv_choose_split(int M, int N, int nkt, size_t ws_floats, double kstep_cycles) {
     const long tiles = (long)((M + CBM - 1) / CBM) * ((N + CBN - 1) / CBN);
@@ -900,6 +939,8 @@ static int conv_choose_split(int M, int N, int nkt, size_t ws_floats, double kst
 // gn_part (optional): receives the GroupNorm partial sums of the output, [B H W / 256][32][2] doubles, when the shape allows the fused
 // epilogue (no split-K, H W a multiple of 256, 32 groups that tile the 160-column workgroup tile); *gn_done tells whether it was written.
 // pfmt: PLANES_BF16X3 (six bf16 products) or PLANES_F16X2 (three fp16 products; wsi -> 2^-S of the weight scale, or null)
+// or PLANES_F16X2_HH: PLANES_F16X2 operands, one product (X plane 0 x W plane 0; plane 1 of either is never read).  Runs the one-product instances of the
+// conv_pp = 2 loop and of the tap-reuse loop whatever conv_pp says (there are no others), conv_tap_reuse = 0 still forces the per-tap loop; N % 4 == 0 required.
 int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const uint16_t* W, size_t wps, int pfmt, const float* wsi, const float* bias, const float* res,
                 float* out, int B, int H, int Wd, int N, int Cin, int taps, float* ws, size_t ws_floats, int force_split, double* gn_part, int* gn_done, int up_phase,
                 size_t w_phase_stride, hipStream_t stream) {
@@ -912,8 +953,9 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
     SDVAR_CHECK_ARG(up_phase < 0 || !res, "conv: no residual with the fused up-sampling");
     SDVAR_CHECK_ARG(x_rows >= (size_t)x_row0 + Mp + w2 + 1, "conv: plane rows %zu too few", x_rows);
     SDVAR_CHECK_ARG(((uintptr_t)X % 16) == 0 && ((uintptr_t)W % 16) == 0 && xps % 8 == 0 && wps % 8 == 0, "conv: planes must be 16-byte aligned");
-    SDVAR_CHECK_ARG(pfmt == PLANES_BF16X3 || pfmt == PLANES_F16X2, "conv: plane format %d", pfmt);
-    const bool F16 = pfmt == PLANES_F16X2;
+    SDVAR_CHECK_ARG(pfmt == PLANES_BF16X3 || pfmt == PLANES_F16X2 || pfmt == PLANES_F16X2_HH, "conv: plane format %d", pfmt);
+    const bool HH = pfmt == PLANES_F16X2_HH, F16 = pfmt == PLANES_F16X2 || HH;
+    SDVAR_CHECK_ARG(!HH || N % 4 == 0, "conv: the one-product format needs N %% 4 == 0 (N=%d)", N);
     ConvArgs a{X, W, xps, wps, x_rows, x_row0, F16 ? wsi : nullptr, bias, res, out, M, N, Cin / 32, taps, H, Wd, N, 1, taps * (Cin / 32), nullptr, 1, up_phase, w_phase_stride, 0};
 #ifdef SDVAR_TIMING_EXPERIMENTS
     static const int conv_dbg = getenv("SDVAR_CONV_DBG") ? atoi(getenv("SDVAR_CONV_DBG")) : 0;
@@ -923,7 +965,7 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
 #endif
     const int nkt = taps * (Cin / 32);
     const int tiles = ((M + CBM - 1) / CBM) * ((N + CBN - 1) / CBN);
-    int split = up_phase >= 0 ? 1 : force_split > 0 ? force_split : conv_choose_split(M, N, nkt, ws ? ws_floats : 0, F16 ? 1200.0 : 2100.0);
+    int split = up_phase >= 0 ? 1 : force_split > 0 ? force_split : conv_choose_split(M, N, nkt, ws ? ws_floats : 0, HH ? CONV_KSTEP_HH : F16 ? 1200.0 : 2100.0);
     if (split > nkt) split = nkt;
     if (split > 1) {
         SDVAR_CHECK_ARG(ws && (size_t)split * M * N <= ws_floats && N % 4 == 0, "conv: split-K workspace too small");
@@ -934,17 +976,46 @@ int conv_planes(const uint16_t* X, size_t xps, size_t x_rows, int x_row0, const 
     const size_t lds = F16 ? 3 * (size_t)CSTAGE_H * sizeof(uint16_t) : 2 * (size_t)CSTAGE * sizeof(uint16_t);      // 156 KB either way
     // SDVAR_CONV_PP is read per call; sdvar_debug_set_variant("conv_pp", v) overrides it (tests): 0 = the round-2 loop, 1 = ping-pong on 32x32x16, 2 (default) = ping-pong on 16x16x32
     const int pp_env = variant(VAR_CONV_PP);
-    const int pp = (pp_env == 2 && N % 4 != 0) ? 1 : pp_env;                                         // the 16-byte epilogue needs whole groups of four columns
+    const int pp = HH ? 2 : (pp_env == 2 && N % 4 != 0) ? 1 : pp_env;                                       // the 16-byte epilogue needs whole groups of four columns
     // SDVAR_CONV_TAP_REUSE (read per call; sdvar_debug_set_variant("conv_tap_reuse", v)): 1 (default) = conv_f16x2_reuse_kernel where the shape allows it, 0 = never.
     // A tile must be part of one image row or whole rows of one image (the staged span is contiguous and <= 264 rows), and the DMA lane offsets are 32-bit.
     const bool reuse = F16 && pp == 2 && variant(VAR_CONV_TAP_REUSE) == 1 && (taps == 9 || taps == 4) && split == 1 && (H * Wd) % CBM == 0 &&
                        (Wd % CBM == 0 || (CBM % Wd == 0 && Wd >= 64)) && x_rows * 64 <= 0xFFFFFFFFull;
     g_conv_last_reuse = reuse ? 1 : 0;
-    g_conv_last_plan[0] = reuse ? 2 : F16 ? 1 : 0;
+    g_conv_last_plan[0] = HH ? (reuse ? 4 : 3) : reuse ? 2 : F16 ? 1 : 0;
     g_conv_last_plan[1] = F16 ? pp : 0;
     g_conv_last_plan[2] = split;
     g_conv_last_plan[3] = 0;
-    static LdsOptIn opt_in, opt_in_h, opt_in_r;
+    static LdsOptIn opt_in, opt_in_h, opt_in_r, opt_in_hh, opt_in_rhh;
+    if (HH) {          // the one-product instances: the launch rules of the f16x2 branches below
+        if (reuse) {
+            SDVAR_LDS_OPT_IN(opt_in_rhh, CLDS_R, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 3, 1>, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3, 1>,
+                             (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 2, 1>);
+            if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; g_conv_last_plan[3] = 1; }
+            if (taps == 4) hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS, 2, 1>), dim3(tiles, 4), dim3(512), CLDS_R, stream, a);
+            else if (res) hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3, 1>), dim3(tiles), dim3(512), CLDS_R, stream, a);
+            else hipLaunchKernelGGL((conv_f16x2_reuse_kernel<CEPI_BIAS, 3, 1>), dim3(tiles), dim3(512), CLDS_R, stream, a);
+            SDVAR_LAUNCH_CHECK();
+            return SDVAR_OK;
+        }
+        SDVAR_LDS_OPT_IN(opt_in_hh, lds, (const void*)conv_f16x2_kernel<CEPI_BIAS, 2, 1>, (const void*)conv_f16x2_kernel<CEPI_BIAS_RES, 2, 1>, (const void*)conv_f16x2_kernel<CEPI_PARTIAL, 2, 1>);
+        if (split > 1) {
+            ConvArgs p = a;
+            p.out = ws;
+            hipLaunchKernelGGL((conv_f16x2_kernel<CEPI_PARTIAL, 2, 1>), dim3(tiles * split), dim3(512), lds, stream, p);
+            SDVAR_LAUNCH_CHECK();
+            const size_t total = (size_t)M * (N / 4);
+            const int rgrid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+            hipLaunchKernelGGL(conv_reduce_kernel, dim3(rgrid), dim3(256), 0, stream, ws, split, bias, res, out, M, N);
+            SDVAR_LAUNCH_CHECK();
+            return SDVAR_OK;
+        }
+        if (gn_part && N % 32 == 0 && CBN % (N / 32) == 0 && (H * Wd) % CBM == 0) { a.gn_part = gn_part; a.cpg = N / 32; if (gn_done) *gn_done = 1; g_conv_last_plan[3] = 1; }
+        if (res) hipLaunchKernelGGL((conv_f16x2_kernel<CEPI_BIAS_RES, 2, 1>), dim3(tiles), dim3(512), lds, stream, a);
+        else hipLaunchKernelGGL((conv_f16x2_kernel<CEPI_BIAS, 2, 1>), dim3(tiles, up_phase >= 0 ? 4 : 1), dim3(512), lds, stream, a);
+        SDVAR_LAUNCH_CHECK();
+        return SDVAR_OK;
+    }
     if (reuse) {
         SDVAR_LDS_OPT_IN(opt_in_r, CLDS_R, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 3>, (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS_RES, 3>,
                          (const void*)conv_f16x2_reuse_kernel<CEPI_BIAS, 2>);

@@ -587,6 +587,7 @@ struct sdvar_vae {
     uint16_t *p1 = nullptr, *p2 = nullptr;
     size_t f_floats = 0, p1_elems = 0, p2_elems = 0, ws_floats = 0;
     int pfmt = PLANES_F16X2, npl = 2;     // operand plane format of the convolutions (desc.plane_format: 0 / 2 = f16x2, 3 = bf16x3)
+    int cfmt = PLANES_F16X2;              // what conv_planes is told: pfmt, or PLANES_F16X2_HH (desc.plane_format 6: f16x2 planes from every producer, one product)
     std::vector<void*> owned;
 };
 
@@ -605,10 +606,12 @@ int sdvar_vae_create(const sdvar_vae_desc* desc, sdvar_vae_t** out) {
         const int c = desc->ch * desc->ch_mult[i];
         SDVAR_CHECK_ARG(c <= 640 * 2 && 320 % (c / 4) == 0, "vae_create: width %d unsupported by the GroupNorm kernel ((C/4) must divide 320)", c);
     }
-    SDVAR_CHECK_ARG(desc->plane_format == 0 || desc->plane_format == PLANES_F16X2 || desc->plane_format == PLANES_BF16X3, "vae_create: plane_format %d (0 / 2 = f16x2, 3 = bf16x3)", desc->plane_format);
+    SDVAR_CHECK_ARG(desc->plane_format == 0 || desc->plane_format == PLANES_F16X2 || desc->plane_format == PLANES_BF16X3 || desc->plane_format == PLANES_F16X2_HH,
+                    "vae_create: plane_format %d (0 / 2 = f16x2, 3 = bf16x3, 6 = f16x2 planes, one product)", desc->plane_format);
     sdvar_vae* v = new sdvar_vae();
     v->d = *desc; v->nlev = desc->n_mult; v->H0 = desc->latent_hw;
     v->pfmt = desc->plane_format == PLANES_BF16X3 ? PLANES_BF16X3 : PLANES_F16X2; v->npl = v->pfmt == PLANES_BF16X3 ? 3 : 2;
+    v->cfmt = desc->plane_format == PLANES_F16X2_HH ? PLANES_F16X2_HH : v->pfmt;
     const int B = desc->max_batch;
     // largest fp32 activation / plane tensors over the levels (level lv runs at H0 << (nlev-1-lv) with width ch*mult[lv]; the
     // first block of a level and the up-sampling conv see the previous level's width)
@@ -782,7 +785,7 @@ struct Runner {
     int conv(const ConvW& c, const uint16_t* xp, size_t ops, size_t rows, int G, const float* res, float* out) {
         SDVAR_CHECK_ARG(M() * c.cout <= v->f_floats, "vae: activation buffer too small");
         int done = 0;
-        VAE_TRY(conv_planes(xp, ops, rows, G, c.wp, c.wps, v->pfmt, c.wsc ? c.wsc + 1 : nullptr, c.bias, res, out, B, H, H, c.cout, c.cin, c.taps, v->ws, v->ws_floats, 0,
+        VAE_TRY(conv_planes(xp, ops, rows, G, c.wp, c.wps, v->cfmt, c.wsc ? c.wsc + 1 : nullptr, c.bias, res, out, B, H, H, c.cout, c.cin, c.taps, v->ws, v->ws_floats, 0,
                             v->part, &done, -1, 0, s));
         stats_src = done ? out : nullptr; stats_up = false;
         return SDVAR_OK;
@@ -846,7 +849,7 @@ static int vae_decode_impl(sdvar_vae_t* v, const float* f_hat, int32_t B, float*
                 VAE_TRY(r.prep(r.x, L.up.cin, nullptr, 0, 0, v->p1, v->p1_elems, &ops, &rows, &G));
                 SDVAR_CHECK_ARG(4 * r.M() * L.up.cout <= v->f_floats, "vae: activation buffer too small");
                 int done = 0;
-                VAE_TRY(conv_planes(v->p1, ops, rows, G, L.up.wp, L.up.wps, v->pfmt, L.up.wsc ? L.up.wsc + 1 : nullptr, L.up.bias, nullptr, r.h, B, r.H, r.H, L.up.cout,
+                VAE_TRY(conv_planes(v->p1, ops, rows, G, L.up.wp, L.up.wps, v->cfmt, L.up.wsc ? L.up.wsc + 1 : nullptr, L.up.bias, nullptr, r.h, B, r.H, r.H, L.up.cout,
                                     L.up.cin, 4, nullptr, 0, 0, v->part, &done, 0, v->npl * L.up.wps, s));
                 r.stats_src = done ? r.h : nullptr; r.stats_up = true;
                 r.H <<= 1;
@@ -1076,6 +1079,7 @@ int sdvar_vae_enc_create(const sdvar_vae_desc* desc, sdvar_vae_enc_t** out) {
     sdvar_vae* v = e->w = new sdvar_vae();
     v->d = *desc; v->nlev = desc->n_mult; v->H0 = desc->latent_hw;
     v->pfmt = desc->plane_format == PLANES_BF16X3 ? PLANES_BF16X3 : PLANES_F16X2; v->npl = v->pfmt == PLANES_BF16X3 ? 3 : 2;
+    v->cfmt = v->pfmt;                    // the encoder has no one-product mode: its convolutions multiply what its producers wrote
     // largest fp32 activation / plane tensors: level lv runs at Himg >> lv with width ch*mult[lv]; its first block reads the previous width, its
     // downsample convolution reads the space-to-depth planes (4C channels at half the side); the deepest level holds the qkv rows (3C)
     size_t fmax_ = 0, pmax = (size_t)plane_rows(B, Himg, Himg) * 32;

@@ -437,21 +437,37 @@ class QuantCtx:
             pass
 
 
+CONV_MODES = ("bf16x3", "f16x2", "f16")
+_CONV_PLANE_FORMAT = {"bf16x3": 3, "f16x2": 2, "f16": 6}          # sdvar_vae_desc.plane_format (include/sdvar_hip.h)
+
+
+def resolve_conv_mode(conv_mode: Optional[str], encoder: bool = False) -> str:
+    """The operand mode of a VQVAE context's convolutions: the argument, else SDVAR_CONV_MODE, else the default.  "f16" (decoders only, opt-in) is an f16x2
+    decoder whose convolutions multiply the high fp16 planes alone - not fp32-accurate.  An encoder feeds a nearest-code search whose ids
+    would move, so it reads the environment's "f16" as "f16x2" and refuses an explicit one.  Decided before any device call."""
+    if encoder and conv_mode == "f16":
+        raise SdvarError("conv_mode 'f16' is a decoder mode: the encoder feeds the nearest-code search and stays fp32-accurate; expected 'bf16x3' or 'f16x2'")
+    mode = conv_mode or os.environ.get("SDVAR_CONV_MODE", DEFAULT_GEMM_MODE if DEFAULT_GEMM_MODE != "f32" else "f16x2")
+    if encoder and not conv_mode and mode == "f16":
+        mode = "f16x2"
+    if mode not in (CONV_MODES[:2] if encoder else CONV_MODES):
+        raise SdvarError(f"conv_mode {mode!r}: expected " + ("'bf16x3' or 'f16x2'" if encoder else "'bf16x3', 'f16x2' or 'f16'"))
+    return mode
+
+
 class VaeCtx:
     """sdvar_vae_t from the VQVAE state_dict: `fhat_to_img` (vqvae.py:62-63) as hand-written HIP (csrc/conv.hip, csrc/vae.hip)."""
 
     def __init__(self, vae_sd: Dict[str, torch.Tensor], max_batch: int, device, latent_hw: int = 16, ch: Optional[int] = None,
                  ch_mult: Sequence[int] = (1, 1, 2, 2, 4), num_res_blocks: int = 2, conv_mode: Optional[str] = None):
+        self.conv_mode = resolve_conv_mode(conv_mode)       # operands of the convolutions; "f16": one fp16 product per convolution (opt-in)
         self.lib = load_library()
         self.device = torch.device(device)
         z = vae_sd["post_quant_conv.weight"].shape[0]
         ch = ch if ch is not None else vae_sd["decoder.norm_out.weight"].shape[0] // ch_mult[0]
         d = _VaeDesc()
         d.ch, d.z_channels, d.n_mult, d.num_res_blocks, d.max_batch, d.latent_hw = ch, z, len(ch_mult), num_res_blocks, max_batch, latent_hw
-        self.conv_mode = conv_mode or os.environ.get("SDVAR_CONV_MODE", DEFAULT_GEMM_MODE if DEFAULT_GEMM_MODE != "f32" else "f16x2")   # operands of the convolutions
-        if self.conv_mode not in ("bf16x3", "f16x2"):
-            raise SdvarError(f"conv_mode {self.conv_mode!r}: expected 'bf16x3' or 'f16x2'")
-        d.plane_format = 3 if self.conv_mode == "bf16x3" else 2
+        d.plane_format = _CONV_PLANE_FORMAT[self.conv_mode]
         for i, m in enumerate(ch_mult):
             d.ch_mult[i] = m
         self.desc, self.max_batch, self.latent_hw, self.z = d, max_batch, latent_hw, z
@@ -518,6 +534,7 @@ class VaeEncCtx:
 
     def __init__(self, vae_sd: Dict[str, torch.Tensor], max_batch: int, device, latent_hw: int = 16, ch: Optional[int] = None,
                  ch_mult: Sequence[int] = (1, 1, 2, 2, 4), num_res_blocks: int = 2, conv_mode: Optional[str] = None):
+        self.conv_mode = resolve_conv_mode(conv_mode, encoder=True)          # as VaeCtx, without the decoder-only "f16"
         self.lib = load_library()
         self.device = torch.device(device)
         if "encoder.conv_in.weight" not in vae_sd:
@@ -526,10 +543,7 @@ class VaeEncCtx:
         ch = ch if ch is not None else vae_sd["encoder.conv_in.weight"].shape[0]
         d = _VaeDesc()
         d.ch, d.z_channels, d.n_mult, d.num_res_blocks, d.max_batch, d.latent_hw = ch, z, len(ch_mult), num_res_blocks, max_batch, latent_hw
-        self.conv_mode = conv_mode or os.environ.get("SDVAR_CONV_MODE", DEFAULT_GEMM_MODE if DEFAULT_GEMM_MODE != "f32" else "f16x2")   # as VaeCtx
-        if self.conv_mode not in ("bf16x3", "f16x2"):
-            raise SdvarError(f"conv_mode {self.conv_mode!r}: expected 'bf16x3' or 'f16x2'")
-        d.plane_format = 3 if self.conv_mode == "bf16x3" else 2
+        d.plane_format = _CONV_PLANE_FORMAT[self.conv_mode]
         for i, m in enumerate(ch_mult):
             d.ch_mult[i] = m
         self.desc, self.max_batch, self.latent_hw, self.z = d, max_batch, latent_hw, z

@@ -305,6 +305,8 @@ class VQVAE(_VaeForward, nn.Module):
         self.Cvae = z_channels
         ch_mult, nrb = (1, 1, 2, 2, 4), 2
         self._ch_mult, self._nrb, self._hip_ctx, self._hip_enc = ch_mult, nrb, None, None
+        self.conv_mode: Optional[str] = None        # arithmetic of the decoder's convolutions (engine.CONV_MODES; None = SDVAR_CONV_MODE / the engine default); 'f16' = the
+                                                    # opt-in one-product fp16 tier: not fp32-accurate.  The encoder never takes it
         self.with_encoder = bool(with_encoder)
         if with_encoder:
             self.encoder = Encoder(ch, ch_mult, nrb, z_channels)
@@ -328,12 +330,12 @@ class VQVAE(_VaeForward, nn.Module):
         if not f_hat.is_cuda:
             raise E.SdvarError("VQVAE: decoding (fhat_to_img, forward) runs on the HIP decoder and needs a GPU tensor (tests/torch_ref.py holds the PyTorch test reference)")
         B, hw = f_hat.shape[0], f_hat.shape[-1]
-        ctx = self._hip_ctx
-        if ctx is None or ctx.device != f_hat.device or ctx.max_batch < B or ctx.latent_hw != hw:
+        ctx, mode = self._hip_ctx, E.resolve_conv_mode(self.conv_mode)
+        if ctx is None or ctx.device != f_hat.device or ctx.max_batch < B or ctx.latent_hw != hw or ctx.conv_mode != mode:
             if ctx is not None:
                 ctx.close()
             sd = {k: v for k, v in self.state_dict().items() if k.startswith(("decoder.", "post_quant_conv."))}
-            ctx = self._hip_ctx = E.VaeCtx(sd, B, f_hat.device, latent_hw=hw, ch_mult=self._ch_mult, num_res_blocks=self._nrb)
+            ctx = self._hip_ctx = E.VaeCtx(sd, B, f_hat.device, latent_hw=hw, ch_mult=self._ch_mult, num_res_blocks=self._nrb, conv_mode=mode)
         return ctx.decode(f_hat, clamp=clamp)
 
     @torch.no_grad()
