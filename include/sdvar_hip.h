@@ -237,6 +237,41 @@ int sdvar_verify_accept_ex(const float* logits, int32_t B, int32_t lsum, int32_t
  * scalar ops): the per-stage CFG logits SDVAR.target_verify_batch returns to a caller that drives the reference's step functions itself. */
 int sdvar_cfg_combine(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n_stages, const int32_t* stage_lens /*host*/, const double* t /*host*/,
                       float* out, void* stream);
+/* ---- per-image sampling parameters (an extension: the reference's arguments are scalars) ------------------------------------------
+ * Image b of a batch is sampled with its own (cfg_b, top_k_b, top_p_b, seed_b, index_b).  The *_rows entry points below take them from two
+ * tables in DEVICE memory, which the caller builds on the host and uploads once per sampler call; the kernels only read them, one row per
+ * workgroup (a workgroup serves one image).  Nothing is copied or synchronised per launch.
+ *   image table   sdvar_row_image[n_rows]: 32-byte rows, one per image
+ *   factor table  float[n_stages][n_rows][2]: { float32(1 + t), float32(t) } with t = cfg_b * s / (S - 1) of (stage s, image b) - the two
+ *                 roundings sdvar_cfg_sample / sdvar_verify_accept_ex / sdvar_cfg_combine apply to their scalar t, done by the caller.
+ *                 A one-stage call takes the (n_rows, 2) slice of its stage, a chunk call the slices of its n_stages consecutive stages.
+ * n_rows is the number of images the tables were built for and must equal B (the factor table is strided by it).
+ * With equal values in every row the *_rows entry points produce the bits of their scalar twins. */
+typedef struct {
+    int32_t  top_k;                         /* 0 = off; < 0 is rejected */
+    int32_t  use_top_p;                     /* top_p_b > 0 */
+    float    top_p_thr;                     /* float32(1 - top_p_b) */
+    uint32_t seed_lo, seed_hi;              /* Philox key of image b: seed_b (the kernels apply the key xor of sdvar_amd/noise.py) */
+    uint32_t index;                         /* Philox image counter of image b (the scalar entry points use image_offset + b) */
+    uint32_t reserved[2];                   /* 0 */
+} sdvar_row_image;
+/* sdvar_cfg_sample with per-image parameters.  fac (B,2) and img (B) are DEVICE tables; img_host is the host copy of img the caller built
+ * (checked here: a negative top_k gives SDVAR_ERR_ARG; never handed to the GPU). */
+int sdvar_cfg_sample_rows(const float* logits, int32_t B, int32_t l, int32_t V, const float* fac, const sdvar_row_image* img,
+                          const sdvar_row_image* img_host /*host*/, int32_t n_rows, const float* q, uint32_t draw, int64_t* ids_out, int32_t ids_stride,
+                          float* dbg_masked, void* stream);
+/* sdvar_verify_accept_ex with the CFG factors of (stage j of the chunk, image b) from fac (n_stages, B, 2), DEVICE.  The acceptance decision is
+ * unchanged: per-stage batch match rate against thr. */
+int sdvar_verify_accept_rows(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n_stages, const int32_t* stage_lens /*host*/, const float* fac,
+                             int32_t n_rows, const int64_t* draft_ids, int32_t ids_stride, double thr, int32_t rule, int32_t match_top_k, double kl_thr,
+                             const float* draft_logits, int32_t* counts, int64_t* argmax_out, uint8_t* match_out, int64_t* corrected_out, void* stream);
+/* sdvar_cfg_combine with fac (n_stages, B, 2), DEVICE */
+int sdvar_cfg_combine_rows(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n_stages, const int32_t* stage_lens /*host*/, const float* fac,
+                           int32_t n_rows, float* out, void* stream);
+/* sdvar_gumbel_mix with the Philox key and image counter of image b from img (B), DEVICE; ratio and tau belong to the stage */
+int sdvar_gumbel_mix_rows(sdvar_quant_t* q, const float* masked_logits, int32_t B, int32_t l, double ratio, double tau, const float* e_noise,
+                          const sdvar_row_image* img, int32_t n_rows, uint32_t draw, float* h_out, void* stream);
+
 /* Validation statistics of VARTrainer.eval_ep (trainer.py:66-75) on logits (B, L, V) fp32 against targets (B, L) int64, one wave64 per token:
  * nll = lse - logit[target] (fp32; a target outside [0, V) gives NaN and is never read), argmax with the lowest index on ties.  nll_out (B*L) fp32 and
  * argmax_out (B*L) int64 may be NULL.  sums (4 doubles) = {sum nll, sum nll of the last `tail` tokens of each image, #argmax == target, #tail

@@ -113,11 +113,16 @@ void debug_get_conv_plan(int* out4);
 int planes_guard(const uint16_t* h_plane, size_t n, unsigned long long* cnt, hipStream_t stream);
 int cfg_sample(const float* logits, int B, int l, int V, float one_plus_t, float t, int top_k, int use_top_p, float top_p_thr, const float* q, uint64_t seed,
                uint32_t draw, uint32_t image_offset, long long* ids, int ids_stride, float* dbg_masked, hipStream_t stream);
+int cfg_sample_rows(const float* logits, int B, int l, int V, const float* fac, const sdvar_row_image* img, const float* q, uint32_t draw, long long* ids,
+                    int ids_stride, float* dbg_masked, hipStream_t stream);
 int noise_fill(float* q, int B, int l, int V, uint64_t seed, uint32_t draw, uint32_t image_offset, hipStream_t stream);
-int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const long long* draft_ids,
-                  int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits, const long long* dl_off, int* counts,
+int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
+                  const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits, const long long* dl_off, int* counts,
                   long long* argmax_out, unsigned char* match_out, long long* corrected_out, hipStream_t stream);
-int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, float* out, hipStream_t stream);
+int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac, float* out,
+                hipStream_t stream);
+int gumbel_mix_rows(const float* masked, int B, int l, int V, float scale, float tau, const float* e, const sdvar_row_image* img, uint32_t draw,
+                    const float* codebook, int Cv, float* h, hipStream_t stream);
 int gumbel_mix(const float* masked, int B, int l, int V, float scale, float tau, const float* e, uint64_t seed, uint32_t draw, uint32_t image_offset,
                const float* codebook, int Cv, float* h, hipStream_t stream);
 int quant_code_norms(const float* codebook, float* e2, int V, int Cv, hipStream_t stream);
@@ -1090,6 +1095,16 @@ int sdvar_gumbel_mix(sdvar_quant_t* q, const float* masked_logits, int32_t B, in
     return gumbel_mix(masked_logits, B, l, q->V, (float)(1.0 + ratio), (float)tau, e_noise, seed, draw, image_offset, q->codebook, q->Cv, h_out, (hipStream_t)stream);
 }
 
+int sdvar_gumbel_mix_rows(sdvar_quant_t* q, const float* masked_logits, int32_t B, int32_t l, double ratio, double tau, const float* e_noise,
+                          const sdvar_row_image* img, int32_t n_rows, uint32_t draw, float* h_out, void* stream) {
+    SDVAR_CHECK_ARG(q && q->bound && masked_logits && h_out, "gumbel_mix_rows: quantizer not bound or null operand");
+    SDVAR_CHECK_ARG(tau > 0.0, "gumbel_mix_rows: tau %g", tau);
+    SDVAR_CHECK_ARG(img, "gumbel_mix_rows: null parameter table");
+    SDVAR_CHECK_ARG(B >= 1 && n_rows == B, "gumbel_mix_rows: B = %d but the table holds %d images", B, n_rows);
+    ProfScope ps(4, 2.0 * B * l * q->V * q->Cv, 4.0 * B * l * q->V * (e_noise ? 2.0 : 1.0), (hipStream_t)stream);
+    return gumbel_mix_rows(masked_logits, B, l, q->V, (float)(1.0 + ratio), (float)tau, e_noise, img, draw, q->codebook, q->Cv, h_out, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------------- sampling
 int sdvar_cfg_sample(const float* logits, int32_t B, int32_t l, int32_t V, double t, int32_t top_k, double top_p, const float* q, uint64_t seed,
                      uint32_t draw, uint32_t image_offset, int64_t* ids_out, int32_t ids_stride, float* dbg_masked, void* stream) {
@@ -1107,7 +1122,7 @@ int sdvar_verify_accept_ex(const float* logits, int32_t B, int32_t lsum, int32_t
     for (int j = 0; j < n; ++j) { qbeg[j] = acc; dl[j] = (long long)2 * B * V * acc; acc += stage_lens[j]; opt[j] = (float)(1.0 + t[j]); tf[j] = (float)t[j]; }
     SDVAR_CHECK_ARG(acc == lsum, "verify_accept: stage lens sum %d != lsum %d", acc, lsum);
     ProfScope ps(5, 0, 4.0 * 2.0 * B * lsum * V * (rule == 2 ? 2.0 : 1.0), (hipStream_t)stream);
-    return verify_accept(logits, B, lsum, V, n, qbeg, opt, tf, (const long long*)draft_ids, ids_stride, thr, rule, match_top_k, (float)kl_thr, draft_logits, dl, counts,
+    return verify_accept(logits, B, lsum, V, n, qbeg, opt, tf, nullptr, (const long long*)draft_ids, ids_stride, thr, rule, match_top_k, (float)kl_thr, draft_logits, dl, counts,
                          (long long*)argmax_out, match_out, (long long*)corrected_out, (hipStream_t)stream);
 }
 
@@ -1122,7 +1137,43 @@ int sdvar_cfg_combine(const float* logits, int32_t B, int32_t lsum, int32_t V, i
     for (int j = 0; j < n; ++j) { qbeg[j] = acc; acc += stage_lens[j]; opt[j] = (float)(1.0 + t[j]); tf[j] = (float)t[j]; }
     SDVAR_CHECK_ARG(acc == lsum, "cfg_combine: stage lens sum %d != lsum %d", acc, lsum);
     ProfScope ps(5, 0, 4.0 * 3.0 * B * lsum * V, (hipStream_t)stream);
-    return cfg_combine(logits, B, lsum, V, n, qbeg, opt, tf, out, (hipStream_t)stream);
+    return cfg_combine(logits, B, lsum, V, n, qbeg, opt, tf, nullptr, out, (hipStream_t)stream);
+}
+
+// ---- per-image parameter tables (include/sdvar_hip.h): the same launches with the scalars read from device rows
+int sdvar_cfg_sample_rows(const float* logits, int32_t B, int32_t l, int32_t V, const float* fac, const sdvar_row_image* img, const sdvar_row_image* img_host,
+                          int32_t n_rows, const float* q, uint32_t draw, int64_t* ids_out, int32_t ids_stride, float* dbg_masked, void* stream) {
+    SDVAR_CHECK_ARG(fac && img && img_host, "cfg_sample_rows: null parameter table");
+    SDVAR_CHECK_ARG(B >= 1 && n_rows == B, "cfg_sample_rows: B = %d but the tables hold %d images", B, n_rows);
+    for (int b = 0; b < B; ++b) SDVAR_CHECK_ARG(img_host[b].top_k >= 0, "cfg_sample_rows: top_k[%d] = %d", b, img_host[b].top_k);
+    ProfScope ps(4, 0, 4.0 * B * l * V * (q ? 3.0 : 2.0), (hipStream_t)stream);
+    return cfg_sample_rows(logits, B, l, V, fac, img, q, draw, (long long*)ids_out, ids_stride, dbg_masked, (hipStream_t)stream);
+}
+
+int sdvar_verify_accept_rows(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n, const int32_t* stage_lens, const float* fac, int32_t n_rows,
+                             const int64_t* draft_ids, int32_t ids_stride, double thr, int32_t rule, int32_t match_top_k, double kl_thr,
+                             const float* draft_logits, int32_t* counts, int64_t* argmax_out, uint8_t* match_out, int64_t* corrected_out, void* stream) {
+    SDVAR_CHECK_ARG(stage_lens && n >= 1 && n <= SDVAR_MAX_STAGES, "verify_accept_rows: bad stage table");
+    SDVAR_CHECK_ARG(fac, "verify_accept_rows: null parameter table");
+    SDVAR_CHECK_ARG(B >= 1 && n_rows == B, "verify_accept_rows: B = %d but the table holds %d images", B, n_rows);
+    int qbeg[SDVAR_MAX_STAGES]; long long dl[SDVAR_MAX_STAGES]; int acc = 0;
+    for (int j = 0; j < n; ++j) { qbeg[j] = acc; dl[j] = (long long)2 * B * V * acc; acc += stage_lens[j]; }
+    SDVAR_CHECK_ARG(acc == lsum, "verify_accept_rows: stage lens sum %d != lsum %d", acc, lsum);
+    ProfScope ps(5, 0, 4.0 * 2.0 * B * lsum * V * (rule == 2 ? 2.0 : 1.0), (hipStream_t)stream);
+    return verify_accept(logits, B, lsum, V, n, qbeg, nullptr, nullptr, fac, (const long long*)draft_ids, ids_stride, thr, rule, match_top_k, (float)kl_thr, draft_logits,
+                         dl, counts, (long long*)argmax_out, match_out, (long long*)corrected_out, (hipStream_t)stream);
+}
+
+int sdvar_cfg_combine_rows(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n, const int32_t* stage_lens, const float* fac, int32_t n_rows,
+                           float* out, void* stream) {
+    SDVAR_CHECK_ARG(stage_lens && n >= 1 && n <= SDVAR_MAX_STAGES, "cfg_combine_rows: bad stage table");
+    SDVAR_CHECK_ARG(fac, "cfg_combine_rows: null parameter table");
+    SDVAR_CHECK_ARG(B >= 1 && n_rows == B, "cfg_combine_rows: B = %d but the table holds %d images", B, n_rows);
+    int qbeg[SDVAR_MAX_STAGES]; int acc = 0;
+    for (int j = 0; j < n; ++j) { qbeg[j] = acc; acc += stage_lens[j]; }
+    SDVAR_CHECK_ARG(acc == lsum, "cfg_combine_rows: stage lens sum %d != lsum %d", acc, lsum);
+    ProfScope ps(5, 0, 4.0 * 3.0 * B * lsum * V, (hipStream_t)stream);
+    return cfg_combine(logits, B, lsum, V, n, qbeg, nullptr, nullptr, fac, out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------- single ops

@@ -16,6 +16,7 @@
 //   * the draw is argmax(p / q), q ~ Exp(1): torch.multinomial's own formulation; q is either an explicit
 //     (B*l, V) input (parity mode) or generated in-kernel from Philox4x32-10 (device mode).
 #include "common.h"
+#include "../../include/sdvar_hip.h"
 
 namespace sdvar {
 
@@ -49,7 +50,15 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Per-image parameter tables (include/sdvar_hip.h "per-image sampling parameters"): device memory, read-only to every kernel here.  A workgroup serves one
+// image, so its row index (blockIdx.y) is block-uniform and the row is read once, into scalar registers.
+//   fac  float (n_stages, B, 2): { float32(1 + t), float32(t) } of (stage, image)
+//   img  sdvar_row_image[B] (8 dwords): top_k, use_top_p, top_p_thr, seed_lo, seed_hi, index, 0, 0
+constexpr int ROW_IMG_DWORDS = 8;
+static_assert(sizeof(sdvar_row_image) == 4 * ROW_IMG_DWORDS, "sdvar_row_image is 8 dwords");
+
 struct SampleArgs {
+    static constexpr bool rows = false;
     const float* logits;      // (2B, l, V)
     const float* q;           // (B*l, V) or null -> philox
     long long* ids;           // ids[b * ids_stride + tok]
@@ -59,8 +68,16 @@ struct SampleArgs {
     uint32_t k0, k1, draw, image_offset;
     float* dbg_masked;        // optional (B, l, V): masked logits for tests
 };
+struct SampleRowArgs : SampleArgs {       // the scalar fields one_plus_t .. k1 and image_offset are unused: image b takes them from its rows
+    static constexpr bool rows = true;
+    const float* fac;                     // (B, 2) of this stage
+    const uint32_t* img;                  // (B, 8)
+};
 
-__global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
+// One body, two kernels: the scalar instance reads its parameters from the launch constants exactly as before (same registers, same LDS), the
+// per-image instance from row blockIdx.y of the tables.  Every branch on them (top-k off, compact / full sort, top-p off) is uniform per workgroup either way.
+template <class Args>
+__device__ __forceinline__ void cfg_sample_body(const Args& a) {
     __shared__ unsigned long long sbuf[NV];        // sort buffer (32 KB); also histogram scratch
     __shared__ unsigned char rm[NV];
     __shared__ double redd[8];
@@ -72,6 +89,16 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
     const int V = a.V;
     const float* pc = a.logits + ((size_t)b * a.l + tok) * V;
     const float* pu = a.logits + ((size_t)(a.B + b) * a.l + tok) * V;
+    float p_opt, p_t, p_thr; int p_top_k, p_use_top_p; uint32_t p_k0, p_k1, p_img;
+    if constexpr (Args::rows) {
+        const uint32_t* r = a.img + (size_t)ROW_IMG_DWORDS * b;
+        p_opt = a.fac[2 * b]; p_t = a.fac[2 * b + 1];
+        p_top_k = (int)r[0]; p_use_top_p = (int)r[1]; p_thr = __uint_as_float(r[2]);
+        p_k0 = r[3]; p_k1 = r[4] ^ 0x5D5A17ABu; p_img = r[5];
+    } else {
+        p_opt = a.one_plus_t; p_t = a.t; p_top_k = a.top_k; p_use_top_p = a.use_top_p; p_thr = a.top_p_thr;
+        p_k0 = a.k0; p_k1 = a.k1; p_img = a.image_offset + (uint32_t)b;
+    }
 
     // ---- CFG combine; thread owns chunks v4 = tid + 256*j (4 consecutive vocab entries each)
     float x[VPT];
@@ -81,7 +108,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
         if (v0 < V) {
             const f32x4 c = *reinterpret_cast<const f32x4*>(pc + v0), u = *reinterpret_cast<const f32x4*>(pu + v0);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) x[4 * j + e] = __fsub_rn(__fmul_rn(a.one_plus_t, c[e]), __fmul_rn(a.t, u[e]));
+            for (int e = 0; e < 4; ++e) x[4 * j + e] = __fsub_rn(__fmul_rn(p_opt, c[e]), __fmul_rn(p_t, u[e]));
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[4 * j + e] = -INFINITY;
@@ -89,11 +116,11 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
     }
 
     // ---- top-k: exact radix select of the k-th largest key, 4 passes of 8 bits
-    if (a.top_k > 0 && a.top_k < V) {
+    if (p_top_k > 0 && p_top_k < V) {
         unsigned int* hist = reinterpret_cast<unsigned int*>(sbuf);
         unsigned int* wsum = hist + 256;
         uint32_t prefix = 0, pmask = 0;
-        int k = a.top_k;                               // rank from the top, 1-based
+        int k = p_top_k;                               // rank from the top, 1-based
         for (int pass = 0; pass < 4; ++pass) {
             const int shift = 24 - 8 * pass;
             hist[tid] = 0;
@@ -129,7 +156,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
     }
 
     // ---- top-p
-    if (a.use_top_p) {
+    if (p_use_top_p) {
         // Survivors of the top-k filter (finite entries).  At most 1024 of them (top_k = 900 + ties at the k-th value): only they are sorted - compacted into
         // sbuf[0, 1024), padded with keys below every finite key - a quarter of the rows and 55 instead of 78 compare-exchange rounds.  The filtered-out
         // entries are -inf: probability 0, first in the ascending order, removed or not they stay -inf, so dropping them changes neither the sorted
@@ -200,7 +227,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
 #pragma unroll
             for (int i = 0; i < CPT; ++i) {
                 run += (double)ev[i];
-                const bool remove = ((float)run <= a.top_p_thr) && (CPT * tid + i != NC - 1);
+                const bool remove = ((float)run <= p_thr) && (CPT * tid + i != NC - 1);
                 if (si[i] < NV) rm[si[i]] = remove ? 1 : 0;              // pads carry indices >= NV
             }
             __syncthreads();
@@ -260,7 +287,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
             run += (double)ev[i];
-            const bool remove = ((float)run <= a.top_p_thr) && (VPT * tid + i != NV - 1);
+            const bool remove = ((float)run <= p_thr) && (VPT * tid + i != NV - 1);
             rm[si[i]] = remove ? 1 : 0;
         }
         __syncthreads();
@@ -301,7 +328,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
             for (int e = 0; e < 4; ++e) qv[e] = t4[e];
         } else {
             uint32_t r4[4];
-            philox4x32_10((uint32_t)(v0 >> 2), (uint32_t)tok, a.image_offset + (uint32_t)b, a.draw, a.k0, a.k1, r4);
+            philox4x32_10((uint32_t)(v0 >> 2), (uint32_t)tok, p_img, a.draw, p_k0, p_k1, r4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) qv[e] = -logf(((float)(r4[e] >> 9) + 0.5f) * 1.1920928955078125e-07f);
         }
@@ -327,6 +354,9 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void cfg_sample_kernel(SampleArgs a) { cfg_sample_body(a); }
+__global__ __launch_bounds__(256) void cfg_sample_rows_kernel(SampleRowArgs a) { cfg_sample_body(a); }
+
 int cfg_sample(const float* logits, int B, int l, int V, float one_plus_t, float t, int top_k, int use_top_p, float top_p_thr,
                const float* q, uint64_t seed, uint32_t draw, uint32_t image_offset, long long* ids, int ids_stride, float* dbg_masked,
                hipStream_t stream) {
@@ -338,6 +368,19 @@ int cfg_sample(const float* logits, int B, int l, int V, float one_plus_t, float
     a.k0 = (uint32_t)(seed & 0xFFFFFFFFull); a.k1 = (uint32_t)(seed >> 32) ^ 0x5D5A17ABu; a.draw = draw; a.image_offset = image_offset;
     a.dbg_masked = dbg_masked;
     hipLaunchKernelGGL(cfg_sample_kernel, dim3(l, B), dim3(256), 0, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+int cfg_sample_rows(const float* logits, int B, int l, int V, const float* fac, const sdvar_row_image* img, const float* q, uint32_t draw, long long* ids,
+                    int ids_stride, float* dbg_masked, hipStream_t stream) {
+    SDVAR_CHECK_ARG(logits && ids && B > 0 && l > 0, "cfg_sample_rows: null/empty");
+    SDVAR_CHECK_ARG(fac && img, "cfg_sample_rows: null parameter table");
+    SDVAR_CHECK_ARG(V > 0 && V <= NV && V % 4 == 0, "cfg_sample_rows: V=%d unsupported (<= %d, multiple of 4)", V, NV);
+    SampleRowArgs a{};
+    a.logits = logits; a.q = q; a.ids = ids; a.B = B; a.l = l; a.V = V; a.ids_stride = ids_stride; a.draw = draw; a.dbg_masked = dbg_masked;
+    a.fac = fac; a.img = reinterpret_cast<const uint32_t*>(img);
+    hipLaunchKernelGGL(cfg_sample_rows_kernel, dim3(l, B), dim3(256), 0, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
@@ -369,6 +412,7 @@ int noise_fill(float* q, int B, int l, int V, uint64_t seed, uint32_t draw, uint
 // at draw | 0x40000000).  `masked` are the CFG logits as the sampler left them (top-k / top-p entries at -inf: the reference's
 // sampler masks its argument in place, helpers.py:10,15).  One workgroup per token; fp32 like the reference.
 struct GumbelArgs {
+    static constexpr bool rows = false;
     const float* masked;      // (B, l, V)
     const float* e;           // (B, l, V) Exp(1) noise or null
     const float* codebook;    // (V, Cv)
@@ -377,14 +421,26 @@ struct GumbelArgs {
     float scale, tau;         // float32(1 + ratio), float32(tau)
     uint32_t k0, k1, draw, image_offset;
 };
+struct GumbelRowArgs : GumbelArgs {       // k0, k1 and image_offset unused: image b takes its Philox key and counter from its row
+    static constexpr bool rows = true;
+    const uint32_t* img;                  // (B, 8)
+};
 
-__global__ __launch_bounds__(256) void gumbel_mix_kernel(GumbelArgs a) {
+template <class Args>
+__device__ __forceinline__ void gumbel_mix_body(const Args& a) {
     __shared__ float pv[NV];
     __shared__ float redf[8];
     __shared__ double redd[8];
     __shared__ float part[8][32];
     const int tid = threadIdx.x, tok = blockIdx.x, b = blockIdx.y, V = a.V;
     const size_t row = ((size_t)b * a.l + tok) * V;
+    uint32_t p_k0, p_k1, p_img;
+    if constexpr (Args::rows) {
+        const uint32_t* r = a.img + (size_t)ROW_IMG_DWORDS * b;
+        p_k0 = r[3]; p_k1 = r[4] ^ 0x5D5A17ABu; p_img = r[5];
+    } else {
+        p_k0 = a.k0; p_k1 = a.k1; p_img = a.image_offset + (uint32_t)b;
+    }
     float y[VPT];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -398,7 +454,7 @@ __global__ __launch_bounds__(256) void gumbel_mix_kernel(GumbelArgs a) {
                 for (int e = 0; e < 4; ++e) ev[e] = t4[e];
             } else {
                 uint32_t r4[4];
-                philox4x32_10((uint32_t)(v0 >> 2), (uint32_t)tok, a.image_offset + (uint32_t)b, a.draw, a.k0, a.k1, r4);
+                philox4x32_10((uint32_t)(v0 >> 2), (uint32_t)tok, p_img, a.draw, p_k0, p_k1, r4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ev[e] = -logf(((float)(r4[e] >> 9) + 0.5f) * 1.1920928955078125e-07f);
             }
@@ -438,6 +494,9 @@ __global__ __launch_bounds__(256) void gumbel_mix_kernel(GumbelArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void gumbel_mix_kernel(GumbelArgs a) { gumbel_mix_body(a); }
+__global__ __launch_bounds__(256) void gumbel_mix_rows_kernel(GumbelRowArgs a) { gumbel_mix_body(a); }
+
 int gumbel_mix(const float* masked, int B, int l, int V, float scale, float tau, const float* e, uint64_t seed, uint32_t draw, uint32_t image_offset,
                const float* codebook, int Cv, float* h, hipStream_t stream) {
     SDVAR_CHECK_ARG(masked && codebook && h && B > 0 && l > 0, "gumbel_mix: null/empty");
@@ -446,6 +505,19 @@ int gumbel_mix(const float* masked, int B, int l, int V, float scale, float tau,
     a.masked = masked; a.e = e; a.codebook = codebook; a.h = h; a.B = B; a.l = l; a.V = V; a.Cv = Cv; a.scale = scale; a.tau = tau;
     a.k0 = (uint32_t)(seed & 0xFFFFFFFFull); a.k1 = (uint32_t)(seed >> 32) ^ 0x5D5A17ABu; a.draw = draw; a.image_offset = image_offset;
     hipLaunchKernelGGL(gumbel_mix_kernel, dim3(l, B), dim3(256), 0, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+int gumbel_mix_rows(const float* masked, int B, int l, int V, float scale, float tau, const float* e, const sdvar_row_image* img, uint32_t draw,
+                    const float* codebook, int Cv, float* h, hipStream_t stream) {
+    SDVAR_CHECK_ARG(masked && codebook && h && B > 0 && l > 0, "gumbel_mix_rows: null/empty");
+    SDVAR_CHECK_ARG(img, "gumbel_mix_rows: null parameter table");
+    SDVAR_CHECK_ARG(V > 0 && V <= NV && V % 4 == 0 && Cv >= 1, "gumbel_mix_rows: V=%d Cv=%d unsupported", V, Cv);
+    GumbelRowArgs a{};
+    a.masked = masked; a.e = e; a.codebook = codebook; a.h = h; a.B = B; a.l = l; a.V = V; a.Cv = Cv; a.scale = scale; a.tau = tau; a.draw = draw;
+    a.img = reinterpret_cast<const uint32_t*>(img);
+    hipLaunchKernelGGL(gumbel_mix_rows_kernel, dim3(l, B), dim3(256), 0, stream, a);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
@@ -459,6 +531,7 @@ int gumbel_mix(const float* masked, int B, int l, int V, float scale, float tau,
 // (draft id where the rule holds, the target's argmax elsewhere) for token-level partial acceptance.
 constexpr int ACC_MAX_CHUNK = 16;
 struct AcceptArgs {
+    static constexpr bool rows = false;
     const float* logits;            // (2B, lsum, V) target logits of the chunk
     const long long* draft_ids;     // draft_ids[b * ids_stride + tok_in_chunk]
     int* counts;                    // [0..n) matched per stage, [16] n_accept, [17..17+n) totals
@@ -474,8 +547,18 @@ struct AcceptArgs {
     unsigned char* match_out;       // optional (B, lsum)
     long long* corrected_out;       // optional (B, lsum)
 };
+struct AcceptRowArgs : AcceptArgs {       // one_plus_t[] / t[] unused: the factors of (stage j of the chunk, image b) are fac[(j * B + b) * 2 + {0, 1}]
+    static constexpr bool rows = true;
+    const float* fac;                     // (n_chunk, B, 2)
+};
+template <class Args>
+__device__ __forceinline__ void stage_factors(const Args& a, int st, int b, float& opt, float& tt) {
+    if constexpr (Args::rows) { const float* f = a.fac + 2 * ((size_t)st * a.B + b); opt = f[0]; tt = f[1]; }
+    else { opt = a.one_plus_t[st]; tt = a.t[st]; }
+}
 
-__global__ __launch_bounds__(256) void verify_match_kernel(AcceptArgs a) {
+template <class Args>
+__device__ __forceinline__ void verify_match_body(const Args& a) {
     __shared__ float redf[8];
     __shared__ int redi[4];
     __shared__ double redd[8];
@@ -484,7 +567,8 @@ __global__ __launch_bounds__(256) void verify_match_kernel(AcceptArgs a) {
     int st = 0;
 #pragma unroll 1
     for (int j = 1; j < a.n_chunk; ++j) if (tok >= a.qbeg[j]) st = j;
-    const float opt = a.one_plus_t[st], tt = a.t[st];
+    float opt, tt;
+    stage_factors(a, st, b, opt, tt);
     const float* pc = a.logits + ((size_t)b * a.lsum + tok) * V;
     const float* pu = a.logits + ((size_t)(a.B + b) * a.lsum + tok) * V;
     float x[VPT];
@@ -572,6 +656,9 @@ __global__ __launch_bounds__(256) void verify_match_kernel(AcceptArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void verify_match_kernel(AcceptArgs a) { verify_match_body(a); }
+__global__ __launch_bounds__(256) void verify_match_rows_kernel(AcceptRowArgs a) { verify_match_body(a); }
+
 // n_accept = number of leading stages with float32(matched)/float32(total) >= thr (var.py:1203,1217), evaluated the
 // way the reference does: a float32 mean promoted to double against the double threshold.
 __global__ void accept_scan_kernel(AcceptArgs a) {
@@ -586,7 +673,8 @@ __global__ void accept_scan_kernel(AcceptArgs a) {
     a.counts[16] = n;
 }
 
-int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t,
+// `fac` non-null: the per-image launch (one_plus_t / t ignored, may be null)
+int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
                   const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits,
                   const long long* dl_off, int* counts, long long* argmax_out, unsigned char* match_out, long long* corrected_out, hipStream_t stream) {
     SDVAR_CHECK_ARG(logits && draft_ids && counts, "verify_accept: null operand");
@@ -594,16 +682,20 @@ int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, cons
     SDVAR_CHECK_ARG(mode >= 0 && mode <= 2, "verify_accept: mode %d (0 top-1, 1 top-k membership, 2 KL threshold)", mode);
     SDVAR_CHECK_ARG(mode != 1 || top_k >= 1, "verify_accept: top-k membership needs k >= 1");
     SDVAR_CHECK_ARG(mode != 2 || (draft_logits && dl_off), "verify_accept: the KL rule needs the draft logits of the chunk");
-    AcceptArgs a;
+    SDVAR_CHECK_ARG(fac || (one_plus_t && t), "verify_accept: no CFG factors");
+    AcceptRowArgs a{};
+    a.fac = fac;
     a.logits = logits; a.draft_ids = draft_ids; a.counts = counts; a.argmax_out = argmax_out;
     a.B = B; a.lsum = lsum; a.V = V; a.ids_stride = ids_stride; a.n_chunk = n_chunk; a.thr = thr;
     a.mode = mode; a.top_k = top_k; a.kl_thr = kl_thr; a.draft_logits = draft_logits; a.match_out = match_out; a.corrected_out = corrected_out;
-    for (int j = 0; j < n_chunk; ++j) { a.qbeg[j] = qbeg[j]; a.one_plus_t[j] = one_plus_t[j]; a.t[j] = t[j]; a.dl_off[j] = dl_off ? dl_off[j] : 0; }
+    for (int j = 0; j < n_chunk; ++j) { a.qbeg[j] = qbeg[j]; a.dl_off[j] = dl_off ? dl_off[j] : 0; if (!fac) { a.one_plus_t[j] = one_plus_t[j]; a.t[j] = t[j]; } }
     a.qbeg[n_chunk] = lsum;
+    const AcceptArgs& base = a;
     SDVAR_HIP(hipMemsetAsync(counts, 0, 40 * sizeof(int), stream));
-    hipLaunchKernelGGL(verify_match_kernel, dim3(lsum, B), dim3(256), 0, stream, a);
+    if (fac) hipLaunchKernelGGL(verify_match_rows_kernel, dim3(lsum, B), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(verify_match_kernel, dim3(lsum, B), dim3(256), 0, stream, base);
     SDVAR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(64), 0, stream, base);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }
@@ -611,12 +703,14 @@ int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, cons
 // ------------------------------------------------------------------------------------------------ cfg_combine
 // out (B, lsum, V) = (1 + t_j) * cond - t_j * uncond per stage j of a verified chunk, with torch's roundings (var.py:1062-1067): what
 // SDVAR.target_verify_batch hands back to a caller that drives the reference's step functions itself.
-__global__ __launch_bounds__(256) void cfg_combine_kernel(AcceptArgs a, float* __restrict__ out) {
+template <class Args>
+__device__ __forceinline__ void cfg_combine_body(const Args& a, float* __restrict__ out) {
     const int tok = blockIdx.x, b = blockIdx.y, V = a.V;
     int st = 0;
 #pragma unroll 1
     for (int j = 1; j < a.n_chunk; ++j) if (tok >= a.qbeg[j]) st = j;
-    const float opt = a.one_plus_t[st], tt = a.t[st];
+    float opt, tt;
+    stage_factors(a, st, b, opt, tt);
     const float* pc = a.logits + ((size_t)b * a.lsum + tok) * V;
     const float* pu = a.logits + ((size_t)(a.B + b) * a.lsum + tok) * V;
     float* po = out + ((size_t)b * a.lsum + tok) * V;
@@ -629,14 +723,21 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(AcceptArgs a, float* _
     }
 }
 
-int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, float* out, hipStream_t stream) {
+__global__ __launch_bounds__(256) void cfg_combine_kernel(AcceptArgs a, float* __restrict__ out) { cfg_combine_body(a, out); }
+__global__ __launch_bounds__(256) void cfg_combine_rows_kernel(AcceptRowArgs a, float* __restrict__ out) { cfg_combine_body(a, out); }
+
+int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac, float* out,
+                hipStream_t stream) {
     SDVAR_CHECK_ARG(logits && out, "cfg_combine: null operand");
+    SDVAR_CHECK_ARG(fac || (one_plus_t && t), "cfg_combine: no CFG factors");
     SDVAR_CHECK_ARG(n_chunk >= 1 && n_chunk <= ACC_MAX_CHUNK && V % 4 == 0 && B >= 1 && lsum >= 1, "cfg_combine: bad chunk/V");
-    AcceptArgs a{};
+    AcceptRowArgs a{};
+    a.fac = fac;
     a.logits = logits; a.B = B; a.lsum = lsum; a.V = V; a.n_chunk = n_chunk;
-    for (int j = 0; j < n_chunk; ++j) { a.qbeg[j] = qbeg[j]; a.one_plus_t[j] = one_plus_t[j]; a.t[j] = t[j]; }
+    for (int j = 0; j < n_chunk; ++j) { a.qbeg[j] = qbeg[j]; if (!fac) { a.one_plus_t[j] = one_plus_t[j]; a.t[j] = t[j]; } }
     a.qbeg[n_chunk] = lsum;
-    hipLaunchKernelGGL(cfg_combine_kernel, dim3(lsum, B), dim3(256), 0, stream, a, out);
+    if (fac) hipLaunchKernelGGL(cfg_combine_rows_kernel, dim3(lsum, B), dim3(256), 0, stream, a, out);
+    else hipLaunchKernelGGL(cfg_combine_kernel, dim3(lsum, B), dim3(256), 0, stream, static_cast<const AcceptArgs&>(a), out);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }

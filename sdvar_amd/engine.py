@@ -105,6 +105,10 @@ _SIGNATURES = {
     "sdvar_cfg_sample": (_I, [_P, _I, _I, _I, _D, _I, _D, _P, _U64, _U32, _U32, _P, _I, _P, _P]),
     "sdvar_verify_accept": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _P, _P, _P]),
     "sdvar_cfg_combine": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _P]),
+    "sdvar_cfg_sample_rows": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _U32, _P, _I, _P, _P]),
+    "sdvar_verify_accept_rows": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), _P, _I, _P, _I, _D, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "sdvar_cfg_combine_rows": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), _P, _I, _P, _P]),
+    "sdvar_gumbel_mix_rows": (_I, [_P, _P, _I, _I, _D, _D, _P, _P, _I, _U32, _P, _P]),
     "sdvar_xent_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "sdvar_img_err_stats": (_I, [_P, _P, C.c_int64, _P, _I, _P]),
     "sdvar_xent_train_fwd": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _D, C.c_int64, _P, _P, _P, _P, _P, _I, _P]),
@@ -426,6 +430,12 @@ class QuantCtx:
         _check(self.lib.sdvar_gumbel_mix(self.h, _ptr(masked), B, l, float(ratio), float(tau), _ptr(e) if e is not None else None, seed & (2**64 - 1), draw,
                                          image_offset, _ptr(h_out), _stream()))
 
+    def gumbel_mix_rows(self, masked: torch.Tensor, B: int, l: int, ratio: float, tau: float, e: Optional[torch.Tensor], rows: "RowParams", draw: int,
+                        h_out: torch.Tensor):
+        """gumbel_mix with image b's Philox key and image counter from the image table of `rows`."""
+        _check(self.lib.sdvar_gumbel_mix_rows(self.h, _ptr(masked), B, l, float(ratio), float(tau), _ptr(e) if e is not None else None, rows.img_ptr(), rows.B,
+                                              draw, _ptr(h_out), _stream()))
+
     def close(self):
         if self.h:
             self.lib.sdvar_quant_destroy(self.h); self.h = C.c_void_p()
@@ -601,23 +611,152 @@ class VaeEncCtx:
             pass
 
 
+# ------------------------------------------------------------------------------------------------------- per-image parameters
+def _as_rows(name: str, v, kind):
+    """A sampling argument as given: a python scalar stays one (-> `kind`); a sequence, numpy array or tensor becomes a list of `kind`."""
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist() if v.dim() else v.item()
+    elif isinstance(v, np.ndarray):
+        v = v.tolist()
+    if isinstance(v, (list, tuple)):
+        return [kind(x) for x in v]
+    try:
+        return kind(v)
+    except (TypeError, ValueError):
+        raise SdvarError(f"{name}: expected a number or a sequence of numbers, got {type(v).__name__}") from None
+
+
+def scalar_arg(who: str, **named):
+    """The paths without per-image tables: a sequence where they take one number is refused by name, before anything is launched."""
+    for name, v in named.items():
+        if isinstance(v, Noise):
+            if v.per_image:
+                raise SdvarError(f"{who}: per-image seeds / image offsets are not supported on this path (plain_ar and spec_decode take them)")
+        elif isinstance(v, (list, tuple, np.ndarray)) or (isinstance(v, torch.Tensor) and v.dim() > 0):
+            raise SdvarError(f"{who}: {name} must be one number on this path, not a sequence (plain_ar and spec_decode take per-image values)")
+
+
+class _RowImage(C.Structure):                  # sdvar_row_image of include/sdvar_hip.h
+    _fields_ = [("top_k", C.c_int32), ("use_top_p", C.c_int32), ("top_p_thr", C.c_float), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
+                ("index", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+ROW_IMAGE_DTYPE = np.dtype([("top_k", "<i4"), ("use_top_p", "<i4"), ("top_p_thr", "<f4"), ("seed_lo", "<u4"), ("seed_hi", "<u4"), ("index", "<u4"),
+                            ("reserved", "<u4", (2,))])
+assert ROW_IMAGE_DTYPE.itemsize == C.sizeof(_RowImage) == 32
+
+
+class RowParams:
+    """Per-image (cfg_b, top_k_b, top_p_b, seed_b, index_b) of one sampler call as the tables of include/sdvar_hip.h: `fac` (S, B, 2) float32
+    = float32(1 + t), float32(t) with t = cfg_b * s / (S - 1) (Ladder.cfg_t; the roundings the scalar entry points apply to their t), and `img`, one
+    sdvar_row_image per image.  Built on the host with numpy, uploaded ONCE (`dev`: one buffer, the factor table then the image table); the kernels
+    read the row of their image, nothing is copied per stage or per round."""
+
+    def __init__(self, B: int, lad: Ladder, cfg, top_k, top_p, seeds: Sequence[int], index: Sequence[int], device=None):
+        col = {}
+        for name, v, kind in (("cfg", cfg, float), ("top_k", top_k, int), ("top_p", top_p, float)):
+            v = _as_rows(name, v, kind)
+            if isinstance(v, list) and len(v) != B:
+                raise SdvarError(f"{name}: {len(v)} entries for a batch of {B} images")
+            col[name] = v if isinstance(v, list) else [v] * B
+        if len(seeds) != B or len(index) != B:
+            raise SdvarError(f"seed / image_offset: {len(seeds)} / {len(index)} entries for a batch of {B} images")
+        if min(col["top_k"]) < 0:
+            raise SdvarError(f"top_k: {col['top_k']}: a negative top_k (0 = off)")
+        self.B, self.S = B, lad.S
+        self.cfg, self.top_k, self.top_p = col["cfg"], col["top_k"], col["top_p"]
+        self.seeds, self.index = [int(x) & (2**64 - 1) for x in seeds], [int(x) & 0xFFFFFFFF for x in index]
+        self.fac = np.empty((lad.S, B, 2), np.float32)
+        for s in range(lad.S):
+            for b in range(B):
+                t = lad.cfg_t(self.cfg[b], s)
+                self.fac[s, b, 0], self.fac[s, b, 1] = np.float32(1.0 + t), np.float32(t)
+        self.img = np.zeros(B, ROW_IMAGE_DTYPE)
+        self.img["top_k"] = self.top_k
+        self.img["use_top_p"] = [1 if p > 0.0 else 0 for p in self.top_p]
+        self.img["top_p_thr"] = [np.float32(1.0 - p) for p in self.top_p]
+        self.img["seed_lo"] = [x & 0xFFFFFFFF for x in self.seeds]
+        self.img["seed_hi"] = [x >> 32 for x in self.seeds]
+        self.img["index"] = self.index
+        self.dev = None
+        self.upload(device)
+
+    def upload(self, device):
+        """One device buffer: the factor table, then the image table.  The one host-to-device copy of a sampler call."""
+        self.img_off = self.fac.nbytes
+        if device is not None:
+            host = np.concatenate([np.ascontiguousarray(self.fac).reshape(-1).view(np.uint8), np.ascontiguousarray(self.img).view(np.uint8).reshape(-1)])
+            self.dev = torch.from_numpy(host).to(device)
+
+    @classmethod
+    def from_tables(cls, fac: np.ndarray, img: np.ndarray, device=None) -> "RowParams":
+        """Tables built by the caller: fac (n_stages, B, 2) float32 holding float32(1 + t), float32(t) of any t, img (B,) ROW_IMAGE_DTYPE."""
+        self = cls.__new__(cls)
+        self.fac, self.img = np.ascontiguousarray(fac, np.float32), np.ascontiguousarray(img, ROW_IMAGE_DTYPE)
+        self.S, self.B = self.fac.shape[0], self.fac.shape[1]
+        if self.fac.ndim != 3 or self.fac.shape[2] != 2 or self.img.shape != (self.B,):
+            raise SdvarError(f"RowParams.from_tables: fac {self.fac.shape} / img {self.img.shape}: expected (n_stages, B, 2) and (B,)")
+        if self.B and int(self.img["top_k"].min()) < 0:
+            raise SdvarError("top_k: a negative top_k (0 = off)")
+        self.dev = None
+        self.upload(device)
+        return self
+
+    @staticmethod
+    def build(B: int, lad: Ladder, cfg, top_k, top_p, noise: "Noise", device=None) -> Optional["RowParams"]:
+        """None when every argument is a scalar: the scalar entry points then run, with the launches they always had."""
+        if not noise.per_image and all(not isinstance(_as_rows(n, v, k), list) for n, v, k in (("cfg", cfg, float), ("top_k", top_k, int), ("top_p", top_p, float))):
+            return None
+        seeds, index = noise.rows(B)
+        return RowParams(B, lad, cfg, top_k, top_p, seeds, index, device)
+
+    def fac_ptr(self, s: int):
+        return C.c_void_p(self.dev.data_ptr() + 8 * self.B * s)
+
+    def img_ptr(self):
+        return C.c_void_p(self.dev.data_ptr() + self.img_off)
+
+    def img_host_ptr(self):
+        return C.c_void_p(self.img.ctypes.data)
+
+
 # ------------------------------------------------------------------------------------------------------- noise
 class Noise:
     """Where the Exp(1) draw noise q comes from (sdvar_amd/noise.py explains why it is explicit).
     kind = 'device': Philox generated inside the sampler kernel (fast path, no host traffic);
            'host'  : the same Philox stream computed on the host in float64 and uploaded (portable parity mode);
            'torch' : torch.empty(B*l, V).exponential_(generator=cpu_gen), the reference's own CPU stream on this host;
-           callable: fn(draw, B, l, V) -> float32 array/tensor (B*l, V) or (B, l, V)."""
+           callable: fn(draw, B, l, V) -> float32 array/tensor (B*l, V) or (B, l, V).
+    `seed` and `image_offset` may be sequences (one entry per image of the call) for 'device' and 'host': image b then draws the Philox stream with
+    key seed[b] and image counter image_offset[b] - what a one-image call with that seed and offset draws.  With a sequence of seeds the counter defaults
+    to 0 for every image; with a scalar seed it stays image_offset + b.  'torch' and callable noise have one stream: a sequence raises SdvarError."""
 
-    def __init__(self, kind="device", seed: int = 0, image_offset: int = 0, fn: Optional[Callable] = None, generator: Optional[torch.Generator] = None):
-        self.kind, self.seed, self.image_offset, self.fn, self.gen = kind, int(seed), int(image_offset), fn, generator
+    def __init__(self, kind="device", seed=0, image_offset=0, fn: Optional[Callable] = None, generator: Optional[torch.Generator] = None):
+        seed, image_offset = _as_rows("seed", seed, int), _as_rows("image_offset", image_offset, int)
+        self.per_image = not (isinstance(seed, int) and isinstance(image_offset, int))
+        if self.per_image and kind not in ("device", "host"):
+            raise SdvarError(f"Noise: a sequence of seeds / image offsets needs the Philox stream (kind 'device' or 'host'), not {kind!r} noise: it has one generator")
+        self.kind, self.seed, self.image_offset, self.fn, self.gen = kind, seed, image_offset, fn, generator
         if kind == "torch" and generator is None:
             self.gen = torch.Generator(device="cpu"); self.gen.manual_seed(self.seed)
+
+    def rows(self, B: int):
+        """(seed_b, index_b) of the B images of a call: the Philox key and image counter of each."""
+        sd, io = self.seed, self.image_offset
+        for name, v in (("seed", sd), ("image_offset", io)):
+            if not isinstance(v, int) and len(v) != B:
+                raise SdvarError(f"{name}: {len(v)} entries for a batch of {B} images")
+        if isinstance(sd, int):
+            idx = [io + b for b in range(B)] if isinstance(io, int) else list(io)
+            return [sd] * B, idx
+        return list(sd), ([io] * B if isinstance(io, int) else list(io))
 
     def tensor(self, draw: int, B: int, l: int, V: int, device) -> Optional[torch.Tensor]:
         if self.kind == "device":
             return None
-        if self.kind == "host":
+        if self.kind == "host" and self.per_image:
+            q = torch.from_numpy(np.concatenate([exponential_noise(s_, draw, 1, l, V, i_) for s_, i_ in zip(*self.rows(B))], 0))
+        elif self.kind == "host":
             q = torch.from_numpy(exponential_noise(self.seed, draw, B, l, V, self.image_offset))
         elif self.kind == "torch":
             q = torch.empty(B * l, V).exponential_(1, generator=self.gen)
@@ -633,6 +772,14 @@ def cfg_sample(logits: torch.Tensor, B: int, l: int, V: int, t: float, top_k: in
     _check(lib.sdvar_cfg_sample(_ptr(logits), B, l, V, float(t), int(top_k), float(top_p), _ptr(q) if q is not None else None, seed & (2**64 - 1),
                                 draw, image_offset, C.c_void_p(ids_out.data_ptr() + 8 * ids_off), ids_stride,
                                 _ptr(dbg_masked) if dbg_masked is not None else None, _stream()))
+
+
+def cfg_sample_rows(logits: torch.Tensor, B: int, l: int, V: int, rows: RowParams, si: int, q: Optional[torch.Tensor], draw: int, ids_out: torch.Tensor,
+                    ids_off: int, ids_stride: int, dbg_masked: Optional[torch.Tensor] = None):
+    """cfg_sample with image b's own parameters: stage `si`'s factor slice and the image table of `rows` (device tables, uploaded when it was built)."""
+    _check(load_library().sdvar_cfg_sample_rows(_ptr(logits), B, l, V, rows.fac_ptr(si), rows.img_ptr(), rows.img_host_ptr(), rows.B,
+                                                _ptr(q) if q is not None else None, draw, C.c_void_p(ids_out.data_ptr() + 8 * ids_off), ids_stride,
+                                                _ptr(dbg_masked) if dbg_masked is not None else None, _stream()))
 
 
 def handoff_mask(lad: Ladder, entry_num: int, sd_mask: int) -> torch.Tensor:
@@ -679,20 +826,31 @@ class MatchRule:
 
 def verify_accept(logits: torch.Tensor, B: int, lens: Sequence[int], V: int, ts: Sequence[float], ids: torch.Tensor, ids_off: int, ids_stride: int,
                   thr: float, counts: torch.Tensor, argmax_out: Optional[torch.Tensor] = None, rule: Optional[MatchRule] = None,
-                  draft_logits: Optional[torch.Tensor] = None, match_out: Optional[torch.Tensor] = None, corrected_out: Optional[torch.Tensor] = None):
+                  draft_logits: Optional[torch.Tensor] = None, match_out: Optional[torch.Tensor] = None, corrected_out: Optional[torch.Tensor] = None,
+                  rows: Optional[RowParams] = None, s0: int = 0):
+    """`rows`: the CFG factors of (stage s0 + j, image b) come from its factor table and `ts` is ignored."""
     lib = load_library()
     n = len(lens)
     o = lambda t: _ptr(t) if t is not None else None
     r = rule or MatchRule()
+    if rows is not None:
+        _check(lib.sdvar_verify_accept_rows(_ptr(logits), B, int(sum(lens)), V, n, (_I * n)(*lens), rows.fac_ptr(s0), rows.B,
+                                            C.c_void_p(ids.data_ptr() + 8 * ids_off), ids_stride, float(thr), r.code, int(r.top_k), float(r.kl_thr),
+                                            o(draft_logits), _ptr(counts), o(argmax_out), o(match_out), o(corrected_out), _stream()))
+        return
     _check(lib.sdvar_verify_accept_ex(_ptr(logits), B, int(sum(lens)), V, n, (_I * n)(*lens), (_D * n)(*[float(t) for t in ts]),
                                       C.c_void_p(ids.data_ptr() + 8 * ids_off), ids_stride, float(thr), r.code, int(r.top_k), float(r.kl_thr),
                                       o(draft_logits), _ptr(counts), o(argmax_out), o(match_out), o(corrected_out), _stream()))
 
 
-def cfg_combine(logits: torch.Tensor, B: int, lens: Sequence[int], V: int, ts: Sequence[float]) -> List[torch.Tensor]:
-    """var.py:1062-1067 on a verified chunk's raw logits (2B, sum(lens), V): the per-stage CFG logits (B, l_j, V), one kernel (csrc/sampler.hip)."""
+def cfg_combine(logits: torch.Tensor, B: int, lens: Sequence[int], V: int, ts: Sequence[float], rows: Optional[RowParams] = None, s0: int = 0) -> List[torch.Tensor]:
+    """var.py:1062-1067 on a verified chunk's raw logits (2B, sum(lens), V): the per-stage CFG logits (B, l_j, V), one kernel (csrc/sampler.hip).
+    `rows`: per-image factors of stages s0 .. from its table (`ts` ignored)."""
     n, lsum = len(lens), int(sum(lens))
     out = torch.empty(B, lsum, V, dtype=torch.float32, device=logits.device)
+    if rows is not None:
+        _check(load_library().sdvar_cfg_combine_rows(_ptr(logits), B, lsum, V, n, (_I * n)(*lens), rows.fac_ptr(s0), rows.B, _ptr(out), _stream()))
+        return list(out.split([int(x) for x in lens], dim=1))
     _check(load_library().sdvar_cfg_combine(_ptr(logits), B, lsum, V, n, (_I * n)(*lens), (_D * n)(*[float(t) for t in ts]), _ptr(out), _stream()))
     return list(out.split([int(x) for x in lens], dim=1))
 
@@ -1542,14 +1700,18 @@ class Sampler:
         return t
 
     def _sample_stage(self, logits: torch.Tensor, B: int, si: int, cfg: float, top_k: int, top_p: float, noise: Noise, draw: int,
-                      more_smooth: bool, f_hat: torch.Tensor, nxt: Optional[torch.Tensor], f_in: Optional[torch.Tensor] = None, keep_masked: bool = False):
+                      more_smooth: bool, f_hat: torch.Tensor, nxt: Optional[torch.Tensor], f_in: Optional[torch.Tensor] = None, keep_masked: bool = False,
+                      rows: Optional[RowParams] = None):
         """CFG + top-k/top-p + multinomial (var.py:199-202), then the token -> feature step (var.py:205-211): codebook rows of the sampled ids,
-        or with more_smooth=True the gumbel-softmax mix of the masked logits (var.py:206-208)."""
+        or with more_smooth=True the gumbel-softmax mix of the masked logits (var.py:206-208).  `rows`: image b's own parameters (cfg, top_k, top_p ignored)."""
         lad, V, L, qz = self.lad, self.t.V, self.lad.L, self.q
         l = lad.lens[si]
         q = noise.tensor(draw, B, l, V, self.dev)
         masked = self._buf("masked", B * lad.lens[-1] * V) if (more_smooth or keep_masked) else None          # the CFG logits after top-k / top-p (-inf = removed)
-        cfg_sample(logits, B, l, V, lad.cfg_t(cfg, si), top_k, top_p, q, noise.seed, draw, noise.image_offset, self.ids, lad.begin(si), L, masked)
+        if rows is not None:
+            cfg_sample_rows(logits, B, l, V, rows, si, q, draw, self.ids, lad.begin(si), L, masked)
+        else:
+            cfg_sample(logits, B, l, V, lad.cfg_t(cfg, si), top_k, top_p, q, noise.seed, draw, noise.image_offset, self.ids, lad.begin(si), L, masked)
         last = si == lad.S - 1
         if not more_smooth:
             qz.next(si, self.ids[:, lad.begin(si):], L, f_hat, None if last else nxt, B, f_in=f_in)
@@ -1559,7 +1721,10 @@ class Sampler:
         tau = max(0.27 * (1 - ratio * 0.95), 0.005)                           # var.py:207
         e = noise.tensor(draw | GUMBEL_DRAW, B, l, V, self.dev)                # the generator's next (B, l, V) exponential draw (helpers.py:26)
         h = self._buf("h_soft", B * lad.lens[-1] * qz.Cv)
-        qz.gumbel_mix(masked, B, l, ratio, tau, e, noise.seed, draw | GUMBEL_DRAW, noise.image_offset, h)
+        if rows is not None:
+            qz.gumbel_mix_rows(masked, B, l, ratio, tau, e, rows, draw | GUMBEL_DRAW, h)
+        else:
+            qz.gumbel_mix(masked, B, l, ratio, tau, e, noise.seed, draw | GUMBEL_DRAW, noise.image_offset, h)
         qz.next_h(si, h, f_hat, None if last else nxt, B)
         return masked
 
@@ -1586,6 +1751,7 @@ class Sampler:
         B, V, S, L = labels.shape[0], m.V, lad.S, lad.L
         res = SampleResult(ids=self.ids[:B], f_hat=self.f_work[:B])
         with torch.cuda.device(self.dev):
+            rows = RowParams.build(B, lad, cfg, top_k, top_p, noise, self.dev)          # None for scalar arguments: the scalar launches
             m.begin(labels)
             f_hat = self.f_work[:B]; f_hat.zero_()
             for si in range(S):
@@ -1596,7 +1762,7 @@ class Sampler:
                     m.forward(self.x_t, si, 1, self.logits_t)
                 if trace:
                     res.trace.setdefault("logits", []).append(self.logits_t[:2 * B * l * V].view(2 * B, l, V).clone())
-                self._sample_stage(self.logits_t, B, si, cfg, top_k, top_p, noise, si, more_smooth, f_hat, self.nxt[0])
+                self._sample_stage(self.logits_t, B, si, cfg, top_k, top_p, noise, si, more_smooth, f_hat, self.nxt[0], rows=rows)
                 if si != S - 1:
                     m.embed_next(self.nxt[0], si + 1, self.x_t, lad.lens[si + 1], 0)
             m.kv_set_len(0)
@@ -1619,6 +1785,7 @@ class Sampler:
         (B, Cvae, pn', pn') after the last one (f_hat itself after the final stage); f_hat (the same tensor step + 1 times - the reference appends
         the object it then updates in place); CFG-combined logits (B, l, V) as the sampler left them (-inf at the entries top-k / top-p removed:
         helpers.py:10,15 mask the appended tensor in place); token ids (B, l)."""
+        scalar_arg("resume_ar", cfg=cfg, top_k=top_k, top_p=top_p, noise=noise)
         m, qz, lad = self.t, self.q, self.lad
         S, V, L, lens, Cv = lad.S, m.V, lad.L, lad.lens, qz.Cv
         B = cond.shape[0] // 2
@@ -1666,6 +1833,7 @@ class Sampler:
         mask (var.py:789, 802-804: this fills its cache), then - literally as the reference does - takes the entry stage's logits from
         the INPUT token map, not from the block output (var.py:809-811).  One noise stream: draw index = stage (var.py:642, 689, 831)."""
         assert self.d is not None, "the hand-off sampler needs a draft model"
+        scalar_arg("handoff", cfg=cfg, top_k=top_k, top_p=top_p, noise=noise)
         d, t, qz, lad = self.d, self.t, self.q, self.lad
         B, V, S, L, lens = labels.shape[0], t.V, lad.S, lad.L, lad.lens
         if not (0 <= entry_num <= S):
@@ -1725,11 +1893,12 @@ class Sampler:
         assert self.d is not None, "the speculative loop needs a draft model"
         assert 1 <= gamma <= self.t.max_chunk, f"gamma {gamma} exceeds the engine's max_chunk {self.t.max_chunk}"
         with torch.cuda.device(self.dev):
+            rows = RowParams.build(labels.shape[0], self.lad, cfg, top_k, top_p, noise, self.dev)        # per-image parameters: one table for the whole loop
             self.d.begin(labels); self.t.begin(labels)
             self.f_acc[:labels.shape[0]].zero_()
         self._row, self._slot = 0, 0
         return SpecState(sampler=self, labels=labels, B=labels.shape[0], cfg=cfg, gamma=gamma, top_k=top_k, top_p=top_p, noise=noise, thr=thr,
-                         total_stages=self.lad.S, patch_nums=self.lad.patch_nums, match=match or MatchRule())
+                         total_stages=self.lad.S, patch_nums=self.lad.patch_nums, match=match or MatchRule(), rows=rows)
 
     def spec_draft(self, st: "SpecState") -> int:
         """SDVAR.draft_generate_batch (var.py:949-1024): g = min(gamma, S - cur) draft stages (forward, CFG, sample, quant,
@@ -1760,8 +1929,11 @@ class Sampler:
                     d.forward(self.x_d, s, 1, lg)
                 st.stats["draft_stage_calls"] += 1
                 q = st.noise.tensor(st.draw, B, lens[s], V, self.dev)
-                cfg_sample(lg, B, lens[s], V, lad.cfg_t(st.cfg, s), st.top_k, st.top_p, q, st.noise.seed, st.draw, st.noise.image_offset,
-                           self.ids, lad.begin(s), L)
+                if st.rows is not None:
+                    cfg_sample_rows(lg, B, lens[s], V, st.rows, s, q, st.draw, self.ids, lad.begin(s), L)
+                else:
+                    cfg_sample(lg, B, lens[s], V, lad.cfg_t(st.cfg, s), st.top_k, st.top_p, q, st.noise.seed, st.draw, st.noise.image_offset,
+                               self.ids, lad.begin(s), L)
                 st.draw += 1
                 last = s == S - 1
                 # f_hat snapshot j = snapshot j-1 (the accepted prefix for j = 0) + this stage: written directly, nothing is copied
@@ -1794,8 +1966,8 @@ class Sampler:
         mr = st.match
         with torch.cuda.device(self.dev):
             corr = self._buf("ids_corr", self.t.max_batch * self.lmax_t, torch.int64) if mr.token_level else None
-            verify_accept(self.logits_t, st.B, st.glen, self.t.V, [lad.cfg_t(st.cfg, cur + j) for j in range(g)], self.ids, lad.begin(cur), lad.L, st.thr, self.counts,
-                          rule=mr, draft_logits=self._lazy.get("draft_logits") if mr.rule == "kl" else None, corrected_out=corr)
+            verify_accept(self.logits_t, st.B, st.glen, self.t.V, st.chunk_ts(cur, g), self.ids, lad.begin(cur), lad.L, st.thr, self.counts,
+                          rule=mr, draft_logits=self._lazy.get("draft_logits") if mr.rule == "kl" else None, corrected_out=corr, rows=st.rows, s0=cur)
             self.counts_host.copy_(self.counts, non_blocking=False)            # the one host sync of the round
         c = self.counts_host.tolist()
         if st.accept_scope == "global":            # batch-wide decision across ranks (reference-literal for one big batch)
@@ -1867,6 +2039,7 @@ class Sampler:
             lg = self.spec_verify_forward(st)
             if trace:
                 res.trace.setdefault("target_logits", []).append((cur, g, lg.clone()))
+                res.trace.setdefault("draft_ids", []).append(self.ids[:st.B, self.lad.begin(cur):self.lad.begin(cur) + sum(st.glen)].clone())      # the round's drafts (B, lsum)
             n_acc, matched = self.spec_accept(st)
             forced, acc_tok = False, None
             if n_acc < g and st.match.token_level:
@@ -1924,8 +2097,8 @@ class Sampler:
                 row = self._row; self._row += 1
                 with torch.cuda.stream(T):
                     self.t.forward(self._xt[slot], cur, g, self.logits_t)
-                    verify_accept(self.logits_t, B, st.glen, V, [lad.cfg_t(st.cfg, cur + j) for j in range(g)], self.ids, lad.begin(cur), lad.L, st.thr,
-                                  self.counts_ra[row])
+                    verify_accept(self.logits_t, B, st.glen, V, st.chunk_ts(cur, g), self.ids, lad.begin(cur), lad.L, st.thr,
+                                  self.counts_ra[row], rows=st.rows, s0=cur)
                     self._counts_pin[row].copy_(self.counts_ra[row], non_blocking=True)
                     ev = torch.cuda.Event(); ev.record(T); t_done.append(ev)
                 st.stats["target_calls"] += 1
@@ -1998,7 +2171,8 @@ class Sampler:
                         self.t.forward_first(self.logits_t)
                     else:
                         self.t.forward(self._xt[st.xt_idx], cur, 1, self.logits_t)
-                    verify_accept(self.logits_t, B, st.glen, V, [lad.cfg_t(st.cfg, cur)], self.ids, lad.begin(cur), lad.L, st.thr, self.counts_ra[row0 + r])
+                    verify_accept(self.logits_t, B, st.glen, V, st.chunk_ts(cur, 1), self.ids, lad.begin(cur), lad.L, st.thr, self.counts_ra[row0 + r],
+                                  rows=st.rows, s0=cur)
                     ev = torch.cuda.Event(); ev.record(T); t_done.append(ev)
                 st.stats["target_calls"] += 1
                 st.target_calls += 1
@@ -2047,6 +2221,11 @@ class SpecState:
     drafted: bool = False
     verified: bool = False
     stats: Dict[str, object] = field(default_factory=lambda: dict(target_calls=0, draft_stage_calls=0, forced_accepts=0, accepted_tokens=0, rounds=[], gamma_final=0))
+    rows: Optional["RowParams"] = None            # per-image (cfg, top_k, top_p, seed, index) tables; None = the scalar fields above
+
+    def chunk_ts(self, cur: int, g: int):
+        """The scalar CFG factors of stages cur .. cur + g - 1 (unused when `rows` carries them per image)."""
+        return [] if self.rows is not None else [self.sampler.lad.cfg_t(self.cfg, cur + j) for j in range(g)]
 
     @property
     def draft_f_hat(self) -> torch.Tensor:        # f_hat of the accepted prefix (after the last commit)

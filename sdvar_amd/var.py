@@ -172,7 +172,7 @@ class VAR(nn.Module):
         return label_B
 
     def _noise(self, g_seed, image_offset=0) -> E.Noise:
-        seed = int(torch.seed() & 0x7FFFFFFFFFFFFFFF) if g_seed is None else int(g_seed)
+        seed = int(torch.seed() & 0x7FFFFFFFFFFFFFFF) if g_seed is None else E._as_rows("g_seed", g_seed, int)
         if self.noise_kind == "torch":
             return E.Noise("torch", seed, generator=self.rng if g_seed is not None else None)
         return E.Noise(self.noise_kind, seed, image_offset)
@@ -181,10 +181,15 @@ class VAR(nn.Module):
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B: Optional[Union[int, torch.LongTensor]], g_seed: Optional[int] = None, cfg=1.5,
                                  top_k=0, top_p=0.0, more_smooth=False) -> torch.Tensor:
-        if g_seed is None:
+        """var.py:127-215.  An extension of the reference's call: `cfg`, `top_k`, `top_p` and `g_seed` each also take a length-B sequence, numpy array or
+        tensor - image b is then sampled with its own values, and with a sequence of seeds it draws what a B = 1 call with g_seed = g_seed[b] draws
+        (INTEGRATION.md section 3).  A wrong length, or a sequence of seeds with label_B=None (the label draw needs one generator), raises SdvarError."""
+        g_seed = _seed_arg(g_seed, B, label_B)
+        if g_seed is None or isinstance(g_seed, list):
             rng = None
         else:
             self.rng.manual_seed(g_seed); rng = self.rng
+        _row_lengths(B, cfg=cfg, top_k=top_k, top_p=top_p)
         labels = self._labels(B, label_B, rng)
         ctx = self.engine_ctx(B, 1)
         qc = self.quant_ctx(ctx.max_batch)
@@ -202,6 +207,7 @@ class VAR(nn.Module):
         is the model's own table (init_param hands it back unchanged, var.py:598): it is checked for shape and otherwise taken from the bound weights.
         `rng`: a CPU torch.Generator (the reference's stream on this host), an engine.Noise, or None (device Philox, fresh seed)."""
         S = len(self.patch_nums)
+        E.scalar_arg("autoregressive_infer_cfg_sd_helper1", cfg=cfg, top_k=top_k, top_p=top_p)
         assert 0 <= current_step < S and step >= 1
         assert sos.shape == (2 * B, self.C), tuple(sos.shape)
         assert lvl_pos is None or tuple(lvl_pos.shape[-2:]) == (self.L, self.C), tuple(lvl_pos.shape)
@@ -307,6 +313,26 @@ class VARHF(VAR, _HubMixin):
                          flash_if_available=flash_if_available, fused_if_available=fused_if_available)
 
 
+def _seed_arg(g_seed, B: int, label_B):
+    """g_seed as the samplers take it: None, one int, or a list of B ints (per-image seeds; they need explicit labels)."""
+    if g_seed is None:
+        return None
+    g_seed = E._as_rows("g_seed", g_seed, int)
+    if isinstance(g_seed, list):
+        if len(g_seed) != B:
+            raise E.SdvarError(f"g_seed: {len(g_seed)} entries for a batch of {B} images")
+        if label_B is None:
+            raise E.SdvarError("g_seed: a sequence of seeds needs label_B: the label draw of label_B=None takes one generator")
+    return g_seed
+
+
+def _row_lengths(B: int, **named):
+    for name, v in named.items():
+        v = E._as_rows(name, v, float)
+        if isinstance(v, list) and len(v) != B:
+            raise E.SdvarError(f"{name}: {len(v)} entries for a batch of {B} images")
+
+
 class SDVAR(nn.Module):
     """Speculative draft -> verify sampler over a (draft, target) VAR pair (models/var.py:535-1383)."""
 
@@ -346,17 +372,19 @@ class SDVAR(nn.Module):
     def _prepare(self, B: int, label_B, g_seed: Optional[int], chunk: int, rng: Optional[torch.Generator] = None):
         """Labels, sampler objects and the noise source of one call (var.py:641-656, 880-902)."""
         t = self.target_model
-        if g_seed is not None and rng is None:
+        g_seed = _seed_arg(g_seed, B, label_B)
+        if g_seed is not None and rng is None and not isinstance(g_seed, list):
             rng = torch.Generator(device="cpu"); rng.manual_seed(g_seed)      # var.py:882-887
         labels = t._labels(B, label_B, rng)
         smp = self._get_sampler(B, chunk)
-        seed = int(torch.seed() & 0x7FFFFFFFFFFFFFFF) if g_seed is None else int(g_seed)
+        seed = int(torch.seed() & 0x7FFFFFFFFFFFFFFF) if g_seed is None else g_seed
         noise = E.Noise("torch", seed, generator=rng) if self.noise_kind == "torch" else E.Noise(self.noise_kind, seed)
         return labels, smp, noise
 
     def _initialize_inference_state(self, B: int, label_B, g_seed: Optional[int], cfg: float, gamma: int) -> E.SpecState:
         """var.py:871-947.  The returned state carries the reference's field names (current_stage, gamma, total_stages,
         accept_count, target_calls, patch_nums, cfg, top_k, top_p, draft_f_hat, target_f_hat)."""
+        E.scalar_arg("_initialize_inference_state", g_seed=g_seed, cfg=cfg)
         labels, smp, noise = self._prepare(B, label_B, g_seed, gamma)
         st = smp.spec_begin(labels, cfg, gamma, 0, 0.0, noise, thr=self.match_threshold, match=self.match_rule)   # top_k / top_p set by the caller (var.py:937-938)
         st.accept_scope = self.accept_scope
@@ -365,6 +393,8 @@ class SDVAR(nn.Module):
     def draft_generate_batch(self, state: E.SpecState, B: int):
         """var.py:949-1024 -> list of g token tensors (B, pn^2) int64 for stages current_stage .. current_stage+g-1."""
         smp, lad = state.sampler, state.sampler.lad
+        if state.rows is None:                      # a state begun with scalars samples with the scalars it carries now (var.py:937-938 sets top_k / top_p on it)
+            E.scalar_arg("draft_generate_batch", cfg=state.cfg, top_k=state.top_k, top_p=state.top_p)
         g = smp.spec_draft(state)
         cur = state.current_stage
         return [smp.ids[:B, lad.begin(cur + j):lad.begin(cur + j) + lad.lens[cur + j]].clone() for j in range(g)]
@@ -375,11 +405,13 @@ class SDVAR(nn.Module):
         if not draft_tokens:
             return [], 0
         assert len(draft_tokens) == state.g, "target_verify_batch verifies the stages of the last draft_generate_batch"
+        if state.rows is None:
+            E.scalar_arg("target_verify_batch", cfg=state.cfg)
         smp, lad, cur = state.sampler, state.sampler.lad, state.current_stage
         lg = smp.spec_verify_forward(state)
         lens = [lad.lens[cur + j] for j in range(state.g)]
         with torch.cuda.device(lg.device):                                                           # var.py:1062-1067 (csrc/sampler.hip cfg_combine_kernel)
-            out = E.cfg_combine(lg, B, lens, lg.shape[-1], [lad.cfg_t(state.cfg, cur + j) for j in range(state.g)])
+            out = E.cfg_combine(lg, B, lens, lg.shape[-1], state.chunk_ts(cur, state.g), rows=state.rows, s0=cur)      # a state begun with per-image tables: every image's own factor
         return out, state.g
 
     def _match(self, draft_tokens, target_logits, B: int, rule: E.MatchRule, draft_logits=None):
@@ -426,6 +458,7 @@ class SDVAR(nn.Module):
         same counters: tests/test_gpu_e2e.py).  more_smooth is accepted and, exactly as in the reference, has no effect on this path
         (var.py:1315 stores it, draft_generate_batch var.py:949-1024 never reads it)."""
         t = self.target_model
+        _row_lengths(B, cfg=cfg, top_k=top_k, top_p=top_p)
         labels, smp, noise = self._prepare(B, label_B, g_seed, gamma)
         res = smp.spec_decode(labels, cfg, gamma, top_k, top_p, noise, thr=self.match_threshold, run_ahead=True, accept_scope=self.accept_scope,
                               match=self.match_rule)
@@ -439,6 +472,7 @@ class SDVAR(nn.Module):
         model's (var.py:641-642); labels as in var.py:647-656.  All six sd_mask values are built (engine.Sampler.handoff;
         1, 2, 4, 5 run the prefill under the explicit block-wise masks of var.py:557-578)."""
         t = self.target_model
+        E.scalar_arg("sdvar_autoregressive_infer_cfg_sd_test3", g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p)
         rng = None
         if g_seed is not None:
             t.rng.manual_seed(g_seed); rng = t.rng
