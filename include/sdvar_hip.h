@@ -272,6 +272,30 @@ int sdvar_cfg_combine_rows(const float* logits, int32_t B, int32_t lsum, int32_t
 int sdvar_gumbel_mix_rows(sdvar_quant_t* q, const float* masked_logits, int32_t B, int32_t l, double ratio, double tau, const float* e_noise,
                           const sdvar_row_image* img, int32_t n_rows, uint32_t draw, float* h_out, void* stream);
 
+/* ---- masked sampling (an extension: in-painting, out-painting, class editing; the reference has no such call) ---------------------------
+ * sdvar_cfg_sample with forced tokens.  gen (uint8) and force_ids (int64) are DEVICE tables read at [b * force_stride + tok], tok in [0, l).
+ * gen == 0: the token is not sampled; ids_out[b * ids_stride + tok] = force_ids[..] clamped into [0, V) (memory safety only: the next kernel
+ * gathers codebook rows by it; callers validate their ids), and the token's row of dbg_masked is NOT written.  gen != 0: the token is sampled
+ * exactly as sdvar_cfg_sample samples it - the Philox counter is (vocab chunk, token, image, draw), so it draws what an unmasked launch on the
+ * same logits draws.  With gen all ones the outputs carry the bits of sdvar_cfg_sample.  ids_out may alias force_ids. */
+int sdvar_cfg_sample_forced(const float* logits, int32_t B, int32_t l, int32_t V, double t, int32_t top_k, double top_p, const float* q,
+                            uint64_t seed, uint32_t draw, uint32_t image_offset, int64_t* ids_out, int32_t ids_stride, float* dbg_masked,
+                            const uint8_t* gen, const int64_t* force_ids, int32_t force_stride, void* stream);
+/* sdvar_cfg_sample_rows with forced tokens (gen, force_ids, force_stride as above) */
+int sdvar_cfg_sample_rows_forced(const float* logits, int32_t B, int32_t l, int32_t V, const float* fac, const sdvar_row_image* img,
+                                 const sdvar_row_image* img_host /*host*/, int32_t n_rows, const float* q, uint32_t draw, int64_t* ids_out,
+                                 int32_t ids_stride, float* dbg_masked, const uint8_t* gen, const int64_t* force_ids, int32_t force_stride, void* stream);
+/* Pixel mask -> token table.  mask_px (B, H, H) uint8, DEVICE: non-zero = regenerate this pixel.  gen (B, L) uint8, L = sum pn_s^2, stage s at
+ * columns [begin(s), begin(s) + pn_s^2), row-major (i, j).  Token (i, j) of a stage with side pn owns pixel rows [floor(i H / pn), ceil((i + 1) H / pn))
+ * and the same span of columns (the windows of area interpolation; they overlap where pn does not divide H); gen = 1 iff
+ * 2 * (non-zero pixels in the window) >= (pixels in the window) - a tie is sampled.  Integer arithmetic, one wave64 per token, no atomics:
+ * repeated calls are bit-identical.  1 <= n_stages <= SDVAR_MAX_STAGES, 1 <= pn_s <= H. */
+int sdvar_mask_tokens(const uint8_t* mask_px, int32_t B, int32_t H, int32_t n_stages, const int32_t* patch_nums /*host*/, uint8_t* gen, void* stream);
+/* out[b,c,y,x] = mask_px[b,y,x] ? fl(fl(gen_img + 1) * 0.5) : fl(fl(orig + 1) * 0.5): gen_img, orig, out (B, C, H, W) fp32, mask_px (B, H, W) uint8, hw = H * W.
+ * Two roundings each, as torch's x.add(1).mul(0.5).  16-byte accesses when hw % 4 == 0, the three float pointers are 16-byte aligned and mask_px is
+ * 4-byte aligned; one element per thread otherwise.  out may alias gen_img (or orig): every element is read before it is written, by the same thread. */
+int sdvar_img_composite(const float* gen_img, const float* orig, const uint8_t* mask_px, int32_t B, int32_t C, int64_t hw, float* out, void* stream);
+
 /* Validation statistics of VARTrainer.eval_ep (trainer.py:66-75) on logits (B, L, V) fp32 against targets (B, L) int64, one wave64 per token:
  * nll = lse - logit[target] (fp32; a target outside [0, V) gives NaN and is never read), argmax with the lowest index on ties.  nll_out (B*L) fp32 and
  * argmax_out (B*L) int64 may be NULL.  sums (4 doubles) = {sum nll, sum nll of the last `tail` tokens of each image, #argmax == target, #tail

@@ -115,6 +115,13 @@ int cfg_sample(const float* logits, int B, int l, int V, float one_plus_t, float
                uint32_t draw, uint32_t image_offset, long long* ids, int ids_stride, float* dbg_masked, hipStream_t stream);
 int cfg_sample_rows(const float* logits, int B, int l, int V, const float* fac, const sdvar_row_image* img, const float* q, uint32_t draw, long long* ids,
                     int ids_stride, float* dbg_masked, hipStream_t stream);
+int cfg_sample_forced(const float* logits, int B, int l, int V, float one_plus_t, float t, int top_k, int use_top_p, float top_p_thr, const float* q, uint64_t seed,
+                      uint32_t draw, uint32_t image_offset, long long* ids, int ids_stride, float* dbg_masked, const unsigned char* gen, const long long* force_ids,
+                      int force_stride, hipStream_t stream);
+int cfg_sample_rows_forced(const float* logits, int B, int l, int V, const float* fac, const sdvar_row_image* img, const float* q, uint32_t draw, long long* ids,
+                           int ids_stride, float* dbg_masked, const unsigned char* gen, const long long* force_ids, int force_stride, hipStream_t stream);
+int mask_tokens(const unsigned char* mask_px, int B, int H, int n_stages, const int* patch_nums, unsigned char* gen, hipStream_t stream);
+int img_composite(const float* gen_img, const float* orig, const unsigned char* mask_px, int B, int C, long long hw, float* out, hipStream_t stream);
 int noise_fill(float* q, int B, int l, int V, uint64_t seed, uint32_t draw, uint32_t image_offset, hipStream_t stream);
 int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
                   const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits, const long long* dl_off, int* counts,
@@ -1148,6 +1155,36 @@ int sdvar_cfg_sample_rows(const float* logits, int32_t B, int32_t l, int32_t V, 
     for (int b = 0; b < B; ++b) SDVAR_CHECK_ARG(img_host[b].top_k >= 0, "cfg_sample_rows: top_k[%d] = %d", b, img_host[b].top_k);
     ProfScope ps(4, 0, 4.0 * B * l * V * (q ? 3.0 : 2.0), (hipStream_t)stream);
     return cfg_sample_rows(logits, B, l, V, fac, img, q, draw, (long long*)ids_out, ids_stride, dbg_masked, (hipStream_t)stream);
+}
+
+// ---- masked sampling (include/sdvar_hip.h): the sampler launch with forced tokens, the pixel mask -> token table, the pixel composite
+int sdvar_cfg_sample_forced(const float* logits, int32_t B, int32_t l, int32_t V, double t, int32_t top_k, double top_p, const float* q, uint64_t seed,
+                            uint32_t draw, uint32_t image_offset, int64_t* ids_out, int32_t ids_stride, float* dbg_masked, const uint8_t* gen,
+                            const int64_t* force_ids, int32_t force_stride, void* stream) {
+    SDVAR_CHECK_ARG(gen && force_ids, "cfg_sample_forced: null gen / force_ids table");
+    ProfScope ps(4, 0, 4.0 * B * l * V * (q ? 3.0 : 2.0), (hipStream_t)stream);
+    return cfg_sample_forced(logits, B, l, V, (float)(1.0 + t), (float)t, top_k, top_p > 0.0 ? 1 : 0, (float)(1.0 - top_p), q, seed, draw, image_offset,
+                             (long long*)ids_out, ids_stride, dbg_masked, gen, (const long long*)force_ids, force_stride, (hipStream_t)stream);
+}
+
+int sdvar_cfg_sample_rows_forced(const float* logits, int32_t B, int32_t l, int32_t V, const float* fac, const sdvar_row_image* img, const sdvar_row_image* img_host,
+                                 int32_t n_rows, const float* q, uint32_t draw, int64_t* ids_out, int32_t ids_stride, float* dbg_masked, const uint8_t* gen,
+                                 const int64_t* force_ids, int32_t force_stride, void* stream) {
+    SDVAR_CHECK_ARG(fac && img && img_host, "cfg_sample_rows_forced: null parameter table");
+    SDVAR_CHECK_ARG(gen && force_ids, "cfg_sample_rows_forced: null gen / force_ids table");
+    SDVAR_CHECK_ARG(B >= 1 && n_rows == B, "cfg_sample_rows_forced: B = %d but the tables hold %d images", B, n_rows);
+    for (int b = 0; b < B; ++b) SDVAR_CHECK_ARG(img_host[b].top_k >= 0, "cfg_sample_rows_forced: top_k[%d] = %d", b, img_host[b].top_k);
+    ProfScope ps(4, 0, 4.0 * B * l * V * (q ? 3.0 : 2.0), (hipStream_t)stream);
+    return cfg_sample_rows_forced(logits, B, l, V, fac, img, q, draw, (long long*)ids_out, ids_stride, dbg_masked, gen, (const long long*)force_ids, force_stride,
+                                  (hipStream_t)stream);
+}
+
+int sdvar_mask_tokens(const uint8_t* mask_px, int32_t B, int32_t H, int32_t n_stages, const int32_t* patch_nums, uint8_t* gen, void* stream) {
+    return mask_tokens(mask_px, B, H, n_stages, patch_nums, gen, (hipStream_t)stream);
+}
+
+int sdvar_img_composite(const float* gen_img, const float* orig, const uint8_t* mask_px, int32_t B, int32_t C, int64_t hw, float* out, void* stream) {
+    return img_composite(gen_img, orig, mask_px, B, C, (long long)hw, out, (hipStream_t)stream);
 }
 
 int sdvar_verify_accept_rows(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n, const int32_t* stage_lens, const float* fac, int32_t n_rows,

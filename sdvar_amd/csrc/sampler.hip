@@ -5,6 +5,7 @@
 //   verify_accept   CFG combine + argmax_V + compare with the draft ids + per-stage match counts, then the
 //                   "leading stages with batch match rate >= thr" scan       models/var.py:1062-1067, 1199-1222
 //   noise_fill      the Philox Exp(1) stream of sdvar_amd/noise.py, for tests of the device-noise mode
+//   masked sampling (an extension, include/sdvar_hip.h): cfg_sample with forced tokens, mask_tokens (pixel mask -> token table), img_composite
 //
 // Exactness notes (the ids must equal the reference's):
 //   * CFG is (1+t)*cond - t*uncond with two roundings then a subtraction, as torch evaluates it: no fma contraction.
@@ -59,6 +60,7 @@ static_assert(sizeof(sdvar_row_image) == 4 * ROW_IMG_DWORDS, "sdvar_row_image is
 
 struct SampleArgs {
     static constexpr bool rows = false;
+    static constexpr bool forced = false;
     const float* logits;      // (2B, l, V)
     const float* q;           // (B*l, V) or null -> philox
     long long* ids;           // ids[b * ids_stride + tok]
@@ -73,11 +75,31 @@ struct SampleRowArgs : SampleArgs {       // the scalar fields one_plus_t .. k1 
     const float* fac;                     // (B, 2) of this stage
     const uint32_t* img;                  // (B, 8)
 };
+// Forced tokens (masked sampling, include/sdvar_hip.h): the two tables are read at [b * force_stride + tok].  Only the forced instances carry the fields.
+struct ForcedFields {
+    const unsigned char* gen;             // 1 = sample this token, 0 = take force_ids
+    const long long* force_ids;
+    int force_stride;
+};
+struct SampleForcedArgs : SampleArgs, ForcedFields { static constexpr bool forced = true; };
+struct SampleRowForcedArgs : SampleRowArgs, ForcedFields { static constexpr bool forced = true; };
 
-// One body, two kernels: the scalar instance reads its parameters from the launch constants exactly as before (same registers, same LDS), the
+// One body, four kernels: the scalar instance reads its parameters from the launch constants exactly as before (same registers, same LDS), the
 // per-image instance from row blockIdx.y of the tables.  Every branch on them (top-k off, compact / full sort, top-p off) is uniform per workgroup either way.
+// The forced instances first look up their token's `gen` byte - block-uniform - and a workgroup of a forced token stores the given id and leaves before
+// any barrier or LDS access; a workgroup of a sampled token runs the body below unchanged.
 template <class Args>
 __device__ __forceinline__ void cfg_sample_body(const Args& a) {
+    if constexpr (Args::forced) {
+        const size_t fo = (size_t)blockIdx.y * a.force_stride + blockIdx.x;
+        if (a.gen[fo] == 0) {
+            if (threadIdx.x == 0) {
+                const long long id = a.force_ids[fo];                  // clamped for memory safety only: the quantiser gathers codebook rows by it
+                a.ids[(size_t)blockIdx.y * a.ids_stride + blockIdx.x] = id < 0 ? 0 : (id >= (long long)a.V ? (long long)a.V - 1 : id);
+            }
+            return;
+        }
+    }
     __shared__ unsigned long long sbuf[NV];        // sort buffer (32 KB); also histogram scratch
     __shared__ unsigned char rm[NV];
     __shared__ double redd[8];
@@ -381,6 +403,141 @@ int cfg_sample_rows(const float* logits, int B, int l, int V, const float* fac, 
     a.logits = logits; a.q = q; a.ids = ids; a.B = B; a.l = l; a.V = V; a.ids_stride = ids_stride; a.draw = draw; a.dbg_masked = dbg_masked;
     a.fac = fac; a.img = reinterpret_cast<const uint32_t*>(img);
     hipLaunchKernelGGL(cfg_sample_rows_kernel, dim3(l, B), dim3(256), 0, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+__global__ __launch_bounds__(256) void cfg_sample_forced_kernel(SampleForcedArgs a) { cfg_sample_body(a); }
+__global__ __launch_bounds__(256) void cfg_sample_rows_forced_kernel(SampleRowForcedArgs a) { cfg_sample_body(a); }
+
+int cfg_sample_forced(const float* logits, int B, int l, int V, float one_plus_t, float t, int top_k, int use_top_p, float top_p_thr,
+                      const float* q, uint64_t seed, uint32_t draw, uint32_t image_offset, long long* ids, int ids_stride, float* dbg_masked,
+                      const unsigned char* gen, const long long* force_ids, int force_stride, hipStream_t stream) {
+    SDVAR_CHECK_ARG(logits && ids && B > 0 && l > 0, "cfg_sample_forced: null/empty");
+    SDVAR_CHECK_ARG(V > 0 && V <= NV && V % 4 == 0, "cfg_sample_forced: V=%d unsupported (<= %d, multiple of 4)", V, NV);
+    SDVAR_CHECK_ARG(gen && force_ids, "cfg_sample_forced: null gen / force_ids table");
+    SDVAR_CHECK_ARG(force_stride >= l && ids_stride >= l, "cfg_sample_forced: force_stride %d / ids_stride %d below l = %d", force_stride, ids_stride, l);
+    SampleForcedArgs a;
+    a.logits = logits; a.q = q; a.ids = ids; a.B = B; a.l = l; a.V = V; a.ids_stride = ids_stride;
+    a.one_plus_t = one_plus_t; a.t = t; a.top_k = top_k; a.top_p_thr = top_p_thr; a.use_top_p = use_top_p;
+    a.k0 = (uint32_t)(seed & 0xFFFFFFFFull); a.k1 = (uint32_t)(seed >> 32) ^ 0x5D5A17ABu; a.draw = draw; a.image_offset = image_offset;
+    a.dbg_masked = dbg_masked;
+    a.gen = gen; a.force_ids = force_ids; a.force_stride = force_stride;
+    hipLaunchKernelGGL(cfg_sample_forced_kernel, dim3(l, B), dim3(256), 0, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+int cfg_sample_rows_forced(const float* logits, int B, int l, int V, const float* fac, const sdvar_row_image* img, const float* q, uint32_t draw,
+                           long long* ids, int ids_stride, float* dbg_masked, const unsigned char* gen, const long long* force_ids, int force_stride,
+                           hipStream_t stream) {
+    SDVAR_CHECK_ARG(logits && ids && B > 0 && l > 0, "cfg_sample_rows_forced: null/empty");
+    SDVAR_CHECK_ARG(fac && img, "cfg_sample_rows_forced: null parameter table");
+    SDVAR_CHECK_ARG(V > 0 && V <= NV && V % 4 == 0, "cfg_sample_rows_forced: V=%d unsupported (<= %d, multiple of 4)", V, NV);
+    SDVAR_CHECK_ARG(gen && force_ids, "cfg_sample_rows_forced: null gen / force_ids table");
+    SDVAR_CHECK_ARG(force_stride >= l && ids_stride >= l, "cfg_sample_rows_forced: force_stride %d / ids_stride %d below l = %d", force_stride, ids_stride, l);
+    SampleRowForcedArgs a{};
+    a.logits = logits; a.q = q; a.ids = ids; a.B = B; a.l = l; a.V = V; a.ids_stride = ids_stride; a.draw = draw; a.dbg_masked = dbg_masked;
+    a.fac = fac; a.img = reinterpret_cast<const uint32_t*>(img);
+    a.gen = gen; a.force_ids = force_ids; a.force_stride = force_stride;
+    hipLaunchKernelGGL(cfg_sample_rows_forced_kernel, dim3(l, B), dim3(256), 0, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mask_tokens
+// Pixel mask (B, H, H) uint8 -> token table gen (B, L) uint8 (include/sdvar_hip.h): one wave64 per token.  Token (i, j) of a stage with side pn owns pixel
+// rows [i H / pn, ceil((i + 1) H / pn)) and the same span of columns; the wave walks its window row-major 64 pixels at a time, each lane tests one pixel,
+// and the set pixels are counted with a ballot and a popcount - integer and order-free, so repeated calls are bit-identical.
+constexpr int MASK_MAX_STAGES = 16;          // SDVAR_MAX_STAGES
+struct MaskTokArgs {
+    const unsigned char* mask;      // (B, H, H)
+    unsigned char* gen;             // (B, L)
+    int B, H, L, n_stages;
+    int pn[MASK_MAX_STAGES];
+    int beg[MASK_MAX_STAGES + 1];
+};
+
+__global__ __launch_bounds__(256) void mask_tokens_kernel(MaskTokArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);          // wave = (image, token): wave-uniform
+    if (w >= (long long)a.B * a.L) return;
+    const int b = (int)(w / a.L), tok = (int)(w % a.L);
+    int st = 0;
+#pragma unroll 1
+    for (int s = 1; s < a.n_stages; ++s) if (tok >= a.beg[s]) st = s;
+    const int pn = a.pn[st], H = a.H, t = tok - a.beg[st], i = t / pn, j = t % pn;
+    const int y0 = (int)(((long long)i * H) / pn), y1 = (int)(((long long)(i + 1) * H + pn - 1) / pn);
+    const int x0 = (int)(((long long)j * H) / pn), x1 = (int)(((long long)(j + 1) * H + pn - 1) / pn);
+    const int wd = x1 - x0, n = (y1 - y0) * wd;
+    const unsigned char* m = a.mask + (size_t)b * H * H;
+    int set = 0;
+    for (int p0 = 0; p0 < n; p0 += 64) {
+        const int p = p0 + lane;
+        bool on = false;
+        if (p < n) on = m[(size_t)(y0 + p / wd) * H + x0 + p % wd] != 0;
+        set += __popcll(__builtin_amdgcn_ballot_w64(on));
+    }
+    if (lane == 0) a.gen[(size_t)b * a.L + tok] = (2 * set >= n) ? 1 : 0;
+}
+
+int mask_tokens(const unsigned char* mask_px, int B, int H, int n_stages, const int* patch_nums, unsigned char* gen, hipStream_t stream) {
+    SDVAR_CHECK_ARG(mask_px && gen && patch_nums, "mask_tokens: null operand");
+    SDVAR_CHECK_ARG(B >= 1 && H >= 1 && H <= 32768, "mask_tokens: B = %d, H = %d", B, H);
+    SDVAR_CHECK_ARG(n_stages >= 1 && n_stages <= MASK_MAX_STAGES, "mask_tokens: %d stages (1 .. %d)", n_stages, MASK_MAX_STAGES);
+    MaskTokArgs a{};
+    a.mask = mask_px; a.gen = gen; a.B = B; a.H = H; a.n_stages = n_stages;
+    long long L = 0;
+    for (int s = 0; s < n_stages; ++s) {
+        SDVAR_CHECK_ARG(patch_nums[s] >= 1 && patch_nums[s] <= H, "mask_tokens: patch_nums[%d] = %d outside [1, H = %d]", s, patch_nums[s], H);
+        a.pn[s] = patch_nums[s]; a.beg[s] = (int)L; L += (long long)patch_nums[s] * patch_nums[s];
+        SDVAR_CHECK_ARG(L <= 0x7FFFFFFF, "mask_tokens: %lld tokens", L);
+    }
+    a.beg[n_stages] = (int)L; a.L = (int)L;
+    const long long waves = (long long)B * L, blocks = (waves + 3) / 4;
+    SDVAR_CHECK_ARG(blocks <= 0x7FFFFFFF, "mask_tokens: %lld tokens in the batch", waves);
+    hipLaunchKernelGGL(mask_tokens_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    SDVAR_LAUNCH_CHECK();
+    return SDVAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ img_composite
+// out = mask ? fl(fl(gen_img + 1) * 0.5) : fl(fl(orig + 1) * 0.5) per pixel, the mask shared by the C channels (include/sdvar_hip.h).  Both roundings are explicit
+// (__fadd_rn / __fmul_rn: no contraction), so the kept pixels carry the bits of torch's orig.add(1).mul(0.5) and the regenerated ones those of the plain
+// sampler's image.  Every thread reads its elements before it writes them: out may alias an input.
+__device__ __forceinline__ float to_unit(float x) { return __fmul_rn(__fadd_rn(x, 1.0f), 0.5f); }
+
+__global__ __launch_bounds__(256) void img_composite_vec_kernel(const float* g, const float* o, const unsigned char* m, int C, long long hw4, long long total4, float* out) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += stride) {          // e = ((b * C + c) * hw4 + p4)
+        const long long p4 = e % hw4, b = (e / hw4) / C;
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 4 * e), ov = *reinterpret_cast<const f32x4*>(o + 4 * e);
+        const uint32_t mv = *reinterpret_cast<const uint32_t*>(m + 4 * (b * hw4 + p4));
+        f32x4 r;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = to_unit(((mv >> (8 * k)) & 0xFFu) ? gv[k] : ov[k]);
+        *reinterpret_cast<f32x4*>(out + 4 * e) = r;
+    }
+}
+
+__global__ __launch_bounds__(256) void img_composite_kernel(const float* g, const float* o, const unsigned char* m, int C, long long hw, long long total, float* out) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const long long p = e % hw, b = (e / hw) / C;
+        const float gv = g[e], ov = o[e];
+        out[e] = to_unit(m[b * hw + p] ? gv : ov);
+    }
+}
+
+int img_composite(const float* gen_img, const float* orig, const unsigned char* mask_px, int B, int C, long long hw, float* out, hipStream_t stream) {
+    SDVAR_CHECK_ARG(gen_img && orig && mask_px && out, "img_composite: null operand");
+    SDVAR_CHECK_ARG(B >= 1 && C >= 1 && hw >= 1 && (double)B * C * (double)hw < 9.0e18, "img_composite: B = %d, C = %d, hw = %lld", B, C, hw);
+    const long long total = (long long)B * C * hw;
+    const bool vec = hw % 4 == 0 && (((uintptr_t)gen_img | (uintptr_t)orig | (uintptr_t)out) & 15) == 0 && ((uintptr_t)mask_px & 3) == 0;
+    const long long work = vec ? total / 4 : total;
+    const unsigned blocks = (unsigned)(work + 255 < 256LL * 4096 ? (work + 255) / 256 : 4096);
+    if (vec) hipLaunchKernelGGL(img_composite_vec_kernel, dim3(blocks), dim3(256), 0, stream, gen_img, orig, mask_px, C, hw / 4, work, out);
+    else hipLaunchKernelGGL(img_composite_kernel, dim3(blocks), dim3(256), 0, stream, gen_img, orig, mask_px, C, hw, total, out);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
 }

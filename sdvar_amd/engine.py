@@ -109,6 +109,10 @@ _SIGNATURES = {
     "sdvar_verify_accept_rows": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), _P, _I, _P, _I, _D, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "sdvar_cfg_combine_rows": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), _P, _I, _P, _P]),
     "sdvar_gumbel_mix_rows": (_I, [_P, _P, _I, _I, _D, _D, _P, _P, _I, _U32, _P, _P]),
+    "sdvar_cfg_sample_forced": (_I, [_P, _I, _I, _I, _D, _I, _D, _P, _U64, _U32, _U32, _P, _I, _P, _P, _P, _I, _P]),
+    "sdvar_cfg_sample_rows_forced": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _U32, _P, _I, _P, _P, _P, _I, _P]),
+    "sdvar_mask_tokens": (_I, [_P, _I, _I, _I, C.POINTER(_I), _P, _P]),
+    "sdvar_img_composite": (_I, [_P, _P, _P, _I, _I, C.c_int64, _P, _P]),
     "sdvar_xent_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "sdvar_img_err_stats": (_I, [_P, _P, C.c_int64, _P, _I, _P]),
     "sdvar_xent_train_fwd": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _D, C.c_int64, _P, _P, _P, _P, _P, _I, _P]),
@@ -780,6 +784,120 @@ def cfg_sample_rows(logits: torch.Tensor, B: int, l: int, V: int, rows: RowParam
     _check(load_library().sdvar_cfg_sample_rows(_ptr(logits), B, l, V, rows.fac_ptr(si), rows.img_ptr(), rows.img_host_ptr(), rows.B,
                                                 _ptr(q) if q is not None else None, draw, C.c_void_p(ids_out.data_ptr() + 8 * ids_off), ids_stride,
                                                 _ptr(dbg_masked) if dbg_masked is not None else None, _stream()))
+
+
+# ---- masked sampling (include/sdvar_hip.h "masked sampling"): forced tokens, the pixel mask -> token table, the pixel composite
+def _edit_tensor(who: str, name: str, t, dtype, numel: int, dev, align: int = 1, exact: bool = True) -> None:
+    """One dense operand of the masked-sampling calls, checked BEFORE its pointer is taken (as _xent_tensor / _embed_tensor do); exact=False: `numel` is the
+    least the kernel touches (a table or an output addressed at a stride inside a larger buffer)."""
+    if not isinstance(t, torch.Tensor):
+        raise SdvarError(f"{who}: {name} is not a tensor")
+    if not t.is_cuda or (dev is not None and t.device != dev):
+        raise SdvarError(f"{who}: {name} is on {t.device}; every operand must be on one GPU")
+    if t.dtype != dtype:
+        raise SdvarError(f"{who}: {name} is {t.dtype}, expected {dtype}")
+    if (t.numel() != numel) if exact else (t.numel() < numel):
+        raise SdvarError(f"{who}: {name} has {t.numel()} elements, expected {'' if exact else 'at least '}{numel}")
+    if not t.is_contiguous():
+        raise SdvarError(f"{who}: {name} with strides {tuple(t.stride())} is not dense (pass {name}.contiguous())")
+    if t.data_ptr() % align:
+        raise SdvarError(f"{who}: {name} is not {align}-byte aligned (pass {name}.clone())")
+
+
+def _forced_operands(who: str, logits, B: int, l: int, V: int, q, ids_out, ids_off: int, ids_stride: int, dbg_masked, gen, force_ids, force_off: int,
+                     force_stride: int):
+    """Everything the forced sampler kernels assume about their operands; returns the three offset pointers (ids, gen, force_ids)."""
+    if min(B, l) < 1 or V < 4 or V % 4 or V > 4096:
+        raise SdvarError(f"{who}: B = {B}, l = {l}, V = {V}: B and l must be positive and V a multiple of 4 up to 4096")
+    if min(ids_off, force_off) < 0 or ids_stride < ids_off + l or force_stride < force_off + l:
+        raise SdvarError(f"{who}: {l} tokens at offset {ids_off} / {force_off} do not fit rows of stride {ids_stride} (ids) / {force_stride} (gen, force_ids)")
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise SdvarError(f"{who}: logits must be a GPU tensor")
+    dev = logits.device
+    _edit_tensor(who, "logits", logits, torch.float32, 2 * B * l * V, dev, 16, exact=False)
+    if q is not None:
+        _edit_tensor(who, "q", q, torch.float32, B * l * V, dev, 16)
+    if dbg_masked is not None:
+        _edit_tensor(who, "dbg_masked", dbg_masked, torch.float32, B * l * V, dev, 4, exact=False)
+    _edit_tensor(who, "ids_out", ids_out, torch.int64, (B - 1) * ids_stride + ids_off + l, dev, 8, exact=False)
+    _edit_tensor(who, "gen", gen, torch.uint8, (B - 1) * force_stride + force_off + l, dev, 1, exact=False)
+    _edit_tensor(who, "force_ids", force_ids, torch.int64, (B - 1) * force_stride + force_off + l, dev, 8, exact=False)
+    return (C.c_void_p(ids_out.data_ptr() + 8 * ids_off), C.c_void_p(gen.data_ptr() + force_off), C.c_void_p(force_ids.data_ptr() + 8 * force_off))
+
+
+def cfg_sample_forced(logits: torch.Tensor, B: int, l: int, V: int, t: float, top_k: int, top_p: float, q: Optional[torch.Tensor], seed: int, draw: int,
+                      image_offset: int, ids_out: torch.Tensor, ids_off: int, ids_stride: int, gen: torch.Tensor, force_ids: torch.Tensor, force_off: int,
+                      force_stride: int, dbg_masked: Optional[torch.Tensor] = None):
+    """sdvar_cfg_sample_forced: cfg_sample, but token (b, tok) with gen[b * force_stride + force_off + tok] == 0 is not sampled: its id is
+    force_ids[b * force_stride + force_off + tok] (clamped into [0, V)) and its row of dbg_masked is left alone.  gen uint8, force_ids int64, dense device tensors."""
+    who = "cfg_sample_forced"
+    p_ids, p_gen, p_force = _forced_operands(who, logits, B, l, V, q, ids_out, ids_off, ids_stride, dbg_masked, gen, force_ids, force_off, force_stride)
+    lib = load_library()
+    with _on_device(logits.device):
+        _check(lib.sdvar_cfg_sample_forced(_ptr(logits), B, l, V, float(t), int(top_k), float(top_p), _ptr(q), seed & (2**64 - 1), draw, image_offset, p_ids, ids_stride,
+                                           _ptr(dbg_masked), p_gen, p_force, force_stride, _stream()))
+
+
+def cfg_sample_rows_forced(logits: torch.Tensor, B: int, l: int, V: int, rows: RowParams, si: int, q: Optional[torch.Tensor], draw: int, ids_out: torch.Tensor,
+                           ids_off: int, ids_stride: int, gen: torch.Tensor, force_ids: torch.Tensor, force_off: int, force_stride: int,
+                           dbg_masked: Optional[torch.Tensor] = None):
+    """sdvar_cfg_sample_rows_forced: cfg_sample_rows with the forced tokens of cfg_sample_forced."""
+    who = "cfg_sample_rows_forced"
+    p_ids, p_gen, p_force = _forced_operands(who, logits, B, l, V, q, ids_out, ids_off, ids_stride, dbg_masked, gen, force_ids, force_off, force_stride)
+    if not isinstance(rows, RowParams) or rows.dev is None or rows.dev.device != logits.device or rows.B != B or not 0 <= si < rows.S:
+        raise SdvarError(f"{who}: rows must be a RowParams uploaded to the logits' GPU for {B} images, and si = {si} one of its stages")
+    lib = load_library()
+    with _on_device(logits.device):
+        _check(lib.sdvar_cfg_sample_rows_forced(_ptr(logits), B, l, V, rows.fac_ptr(si), rows.img_ptr(), rows.img_host_ptr(), rows.B, _ptr(q), draw, p_ids, ids_stride,
+                                                _ptr(dbg_masked), p_gen, p_force, force_stride, _stream()))
+
+
+def mask_tokens(mask_px: torch.Tensor, patch_nums: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sdvar_mask_tokens: mask_px (B, H, H) uint8 on the GPU (non-zero = regenerate the pixel) -> gen (B, L) uint8, stage s at columns [begin(s), begin(s) + pn_s^2).
+    Token (i, j) of a stage with side pn owns pixel rows [floor(i H / pn), ceil((i + 1) H / pn)) and the same span of columns; it is sampled (1) iff
+    2 * (set pixels in its window) >= (pixels in its window).  Integer and exact; no host synchronisation."""
+    who = "mask_tokens"
+    pns = [int(p) for p in patch_nums]
+    if not isinstance(mask_px, torch.Tensor) or mask_px.dim() != 3 or mask_px.shape[1] != mask_px.shape[2] or mask_px.shape[0] < 1 or mask_px.shape[1] < 1:
+        raise SdvarError(f"{who}: mask_px must be a (B, H, H) uint8 GPU tensor, got {tuple(mask_px.shape) if isinstance(mask_px, torch.Tensor) else type(mask_px).__name__}")
+    B, H = int(mask_px.shape[0]), int(mask_px.shape[1])
+    if not 1 <= len(pns) <= MAX_STAGES or min(pns) < 1 or max(pns) > H:
+        raise SdvarError(f"{who}: patch_nums {tuple(pns)}: 1 to {MAX_STAGES} stages with sides in [1, H = {H}]")
+    _edit_tensor(who, "mask_px", mask_px, torch.uint8, B * H * H, None)
+    L = sum(p * p for p in pns)
+    if out is None:
+        out = torch.empty(B, L, dtype=torch.uint8, device=mask_px.device)
+    else:
+        _edit_tensor(who, "out", out, torch.uint8, B * L, mask_px.device)
+    lib = load_library()
+    with _on_device(mask_px.device):
+        _check(lib.sdvar_mask_tokens(_ptr(mask_px), B, H, len(pns), (_I * len(pns))(*pns), _ptr(out), _stream()))
+    return out
+
+
+def img_composite(gen_img: torch.Tensor, orig: torch.Tensor, mask_px: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sdvar_img_composite: out = mask_px ? (gen_img + 1) * 0.5 : (orig + 1) * 0.5 with the two roundings of torch's x.add(1).mul(0.5).  gen_img, orig (B, C, H, W) fp32,
+    mask_px (B, H, W) uint8, all dense on one GPU; out may be gen_img (or orig) itself.  16-byte accesses when the pointers allow, scalar ones otherwise."""
+    who = "img_composite"
+    if not isinstance(gen_img, torch.Tensor) or gen_img.dim() != 4 or gen_img.numel() == 0:
+        raise SdvarError(f"{who}: gen_img must be a non-empty (B, C, H, W) fp32 GPU tensor")
+    B, Cc, H, W = (int(x) for x in gen_img.shape)
+    _edit_tensor(who, "gen_img", gen_img, torch.float32, B * Cc * H * W, None, 4)
+    dev = gen_img.device
+    for name, t, shape, dtype in (("orig", orig, (B, Cc, H, W), torch.float32), ("mask_px", mask_px, (B, H, W), torch.uint8)):
+        if isinstance(t, torch.Tensor) and tuple(t.shape) != shape:
+            raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}, expected {shape}")
+        _edit_tensor(who, name, t, dtype, int(np.prod(shape)), dev, 4 if dtype == torch.float32 else 1)
+    if out is None:
+        out = torch.empty_like(gen_img)
+    else:
+        if isinstance(out, torch.Tensor) and tuple(out.shape) != (B, Cc, H, W):
+            raise SdvarError(f"{who}: out has shape {tuple(out.shape)}, expected {(B, Cc, H, W)}")
+        _edit_tensor(who, "out", out, torch.float32, B * Cc * H * W, dev, 4)
+    lib = load_library()
+    with _on_device(dev):
+        _check(lib.sdvar_img_composite(_ptr(gen_img), _ptr(orig), _ptr(mask_px), B, Cc, H * W, _ptr(out), _stream()))
+    return out
 
 
 def handoff_mask(lad: Ladder, entry_num: int, sd_mask: int) -> torch.Tensor:
@@ -1657,6 +1775,7 @@ class SampleResult:
     f_hat: torch.Tensor                    # (B, Cvae, HW, HW)
     stats: Dict[str, object] = field(default_factory=dict)
     trace: Dict[str, list] = field(default_factory=dict)
+    gen: Optional[torch.Tensor] = None     # masked sampling (VAR.autoregressive_infer_cfg_edit): the (B, L) uint8 token table, 1 = sampled, 0 = the image's own id
 
 
 class Sampler:
@@ -1701,14 +1820,22 @@ class Sampler:
 
     def _sample_stage(self, logits: torch.Tensor, B: int, si: int, cfg: float, top_k: int, top_p: float, noise: Noise, draw: int,
                       more_smooth: bool, f_hat: torch.Tensor, nxt: Optional[torch.Tensor], f_in: Optional[torch.Tensor] = None, keep_masked: bool = False,
-                      rows: Optional[RowParams] = None):
+                      rows: Optional[RowParams] = None, forced=None):
         """CFG + top-k/top-p + multinomial (var.py:199-202), then the token -> feature step (var.py:205-211): codebook rows of the sampled ids,
-        or with more_smooth=True the gumbel-softmax mix of the masked logits (var.py:206-208).  `rows`: image b's own parameters (cfg, top_k, top_p ignored)."""
+        or with more_smooth=True the gumbel-softmax mix of the masked logits (var.py:206-208).  `rows`: image b's own parameters (cfg, top_k, top_p ignored).
+        `forced`: (gen, force_ids), each (B, L): the forced entry points - a token with gen == 0 takes its id from force_ids instead of being sampled."""
         lad, V, L, qz = self.lad, self.t.V, self.lad.L, self.q
         l = lad.lens[si]
         q = noise.tensor(draw, B, l, V, self.dev)
         masked = self._buf("masked", B * lad.lens[-1] * V) if (more_smooth or keep_masked) else None          # the CFG logits after top-k / top-p (-inf = removed)
-        if rows is not None:
+        if forced is not None:
+            gen, force_ids = forced
+            if rows is not None:
+                cfg_sample_rows_forced(logits, B, l, V, rows, si, q, draw, self.ids, lad.begin(si), L, gen, force_ids, lad.begin(si), L, masked)
+            else:
+                cfg_sample_forced(logits, B, l, V, lad.cfg_t(cfg, si), top_k, top_p, q, noise.seed, draw, noise.image_offset, self.ids, lad.begin(si), L,
+                                  gen, force_ids, lad.begin(si), L, masked)
+        elif rows is not None:
             cfg_sample_rows(logits, B, l, V, rows, si, q, draw, self.ids, lad.begin(si), L, masked)
         else:
             cfg_sample(logits, B, l, V, lad.cfg_t(cfg, si), top_k, top_p, q, noise.seed, draw, noise.image_offset, self.ids, lad.begin(si), L, masked)
@@ -1746,9 +1873,27 @@ class Sampler:
 
     # ---- VAR.autoregressive_infer_cfg (var.py:127-215) up to the decode
     def plain_ar(self, labels: torch.Tensor, cfg: float, top_k: int, top_p: float, noise: Noise, trace: bool = False,
-                 more_smooth: bool = False) -> SampleResult:
+                 more_smooth: bool = False, force_ids: Optional[torch.Tensor] = None, gen: Optional[torch.Tensor] = None,
+                 trusted_ids: bool = False) -> SampleResult:
+        """`force_ids` (B, L) int64 and `gen` (B, L) uint8, both or neither: masked sampling - token (b, i) is sampled where gen[b, i] != 0 and takes force_ids[b, i]
+        elsewhere (in-painting: the image's own ids outside the edit region); a sampled token draws what the unmasked call would draw on the same logits.  Every
+        force_ids value must lie in [0, V): checked once before the first launch (one reduction, one synchronisation) unless trusted_ids=True."""
         m, qz, lad = self.t, self.q, self.lad
         B, V, S, L = labels.shape[0], m.V, lad.S, lad.L
+        forced = None
+        if force_ids is not None or gen is not None:
+            who = "plain_ar"
+            if force_ids is None or gen is None:
+                raise SdvarError(f"{who}: force_ids and gen go together (both (B, L)), got only {'gen' if force_ids is None else 'force_ids'}")
+            if more_smooth:
+                raise SdvarError(f"{who}: more_smooth=True with a mask (force_ids / gen) is not supported: the gumbel mix of a forced token is undefined")
+            for name, t, dtype in (("force_ids", force_ids, torch.int64), ("gen", gen, torch.uint8)):
+                if isinstance(t, torch.Tensor) and tuple(t.shape) != (B, L):
+                    raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}, expected (B, L) = {(B, L)}")
+                _edit_tensor(who, name, t, dtype, B * L, self.ids.device, 8 if dtype == torch.int64 else 1)
+            if not trusted_ids and bool(((force_ids < 0) | (force_ids >= V)).any()):
+                raise SdvarError(f"{who}: force_ids holds ids outside [0, V = {V})")
+            forced = (gen, force_ids)
         res = SampleResult(ids=self.ids[:B], f_hat=self.f_work[:B])
         with torch.cuda.device(self.dev):
             rows = RowParams.build(B, lad, cfg, top_k, top_p, noise, self.dev)          # None for scalar arguments: the scalar launches
@@ -1762,7 +1907,7 @@ class Sampler:
                     m.forward(self.x_t, si, 1, self.logits_t)
                 if trace:
                     res.trace.setdefault("logits", []).append(self.logits_t[:2 * B * l * V].view(2 * B, l, V).clone())
-                self._sample_stage(self.logits_t, B, si, cfg, top_k, top_p, noise, si, more_smooth, f_hat, self.nxt[0], rows=rows)
+                self._sample_stage(self.logits_t, B, si, cfg, top_k, top_p, noise, si, more_smooth, f_hat, self.nxt[0], rows=rows, forced=forced)
                 if si != S - 1:
                     m.embed_next(self.nxt[0], si + 1, self.x_t, lad.lens[si + 1], 0)
             m.kv_set_len(0)

@@ -22,6 +22,8 @@ from .vqvae import VQVAE
 # images per pass of VAR.forward (M = L * TF_PASS_IMAGES rows per GEMM), from tools/eval_bench.py: at 256^2 a d16 pass
 # runs 915 / 1012 / 1119 images/s at 8 / 16 / 32 images (f16x2), d30 195 / 201 / 203
 TF_PASS_IMAGES = 32
+# images per call of autoregressive_infer_cfg_edit: the sampler kernels put the image index on the grid's y axis (65535 at the most)
+MAX_EDIT_BATCH = 65535
 
 
 class _SelfAttention(nn.Module):                   # parameter names of basic_var.py:58-87
@@ -198,6 +200,71 @@ class VAR(nn.Module):
         res = self._sampler.plain_ar(labels, cfg, top_k, top_p, self._noise(g_seed), more_smooth=bool(more_smooth))   # more_smooth: var.py:206-208
         self.last_result = res
         return self.vae_proxy[0].fhat_to_img(res.f_hat.clone()).add_(1).mul_(0.5)
+
+    # ---- masked sampling: in-painting, out-painting, class-conditional editing (an extension; the reference has no such call) -------------
+    @torch.no_grad()
+    def autoregressive_infer_cfg_edit(self, image: torch.Tensor, mask: torch.Tensor, label_B: Optional[Union[int, torch.LongTensor]], g_seed: Optional[int] = None,
+                                      cfg=1.5, top_k=0, top_p=0.0, composite: bool = True, more_smooth: bool = False) -> torch.Tensor:
+        """Regenerate the masked region of `image` under `label_B` and keep the rest: (B, 3, H, H) in [0, 1].
+        image: (B, 3, H, H) fp32 GPU tensor in [-1, 1] (what VQVAE.img_to_idxBl takes), H = 16 * patch_nums[-1].  mask: (B, H, H), (B, 1, H, H) or (H, H) bool /
+        uint8 GPU tensor, non-zero = regenerate; a 2-D mask serves every image.  label_B, g_seed, cfg, top_k, top_p: as autoregressive_infer_cfg takes them,
+        per-image sequences included.  The image is encoded to its multi-scale ids; at every scale the tokens whose window (the pixels area interpolation
+        averages into them) is at least half masked are sampled and the others keep the image's own id (engine.mask_tokens, Sampler.plain_ar(force_ids, gen));
+        the result is decoded and, with composite=True, the pixels outside the mask are put back: they are then the bits of image.add(1).mul(0.5).  With
+        composite=False the decoder's output is returned as it is, and kept pixels move (the decoder's receptive field, the bicubic up-sampling of coarse
+        tokens).  more_smooth=True raises SdvarError (the gumbel mix of a forced token is undefined).  last_result additionally carries `gen`, the (B, L) table."""
+        who = "autoregressive_infer_cfg_edit"
+        if more_smooth:
+            raise E.SdvarError(f"{who}: more_smooth=True is not supported with a mask: the gumbel mix of a forced token is undefined")
+        vae = self.vae_proxy[0]
+        if not getattr(vae, "with_encoder", False):
+            raise E.SdvarError(f"{who}: image: the VQVAE was built with with_encoder=False, so it cannot encode the image to edit")
+        H = vae.downsample * self.patch_nums[-1]
+        if not isinstance(image, torch.Tensor) or image.dim() != 4 or image.shape[0] < 1 or image.shape[1] != 3 or image.dtype != torch.float32:
+            what = f"{tuple(image.shape)} {image.dtype}" if isinstance(image, torch.Tensor) else type(image).__name__
+            raise E.SdvarError(f"{who}: image must be a (B, 3, H, H) float32 tensor in [-1, 1], got {what}")
+        B = int(image.shape[0])
+        if tuple(image.shape[2:]) != (H, H):
+            raise E.SdvarError(f"{who}: image is {image.shape[2]} x {image.shape[3]}, but the ladder {self.patch_nums} generates {H} x {H} images")
+        if B > MAX_EDIT_BATCH:
+            raise E.SdvarError(f"{who}: image: a batch of {B} images is more than the sampler contexts can be built for ({MAX_EDIT_BATCH})")
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+            what = f"{mask.dtype}" if isinstance(mask, torch.Tensor) else type(mask).__name__
+            raise E.SdvarError(f"{who}: mask must be a bool or uint8 tensor (non-zero = regenerate), got {what}")
+        if tuple(mask.shape) not in ((B, H, H), (B, 1, H, H), (H, H)):
+            raise E.SdvarError(f"{who}: mask has shape {tuple(mask.shape)}, expected {(B, H, H)}, {(B, 1, H, H)} or {(H, H)}")
+        dev = self._device()
+        for name, t in (("image", image), ("mask", mask)):
+            if not t.is_cuda or t.device != dev:
+                raise E.SdvarError(f"{who}: {name} is on {t.device}, the model on {dev}: masked sampling runs on the GPU and there is no CPU path")
+        g_seed = _seed_arg(g_seed, B, label_B)
+        if g_seed is None or isinstance(g_seed, list):
+            rng = None
+        else:
+            self.rng.manual_seed(g_seed); rng = self.rng
+        _row_lengths(B, cfg=cfg, top_k=top_k, top_p=top_p)
+        labels = self._labels(B, label_B, rng)
+        image = image.contiguous()
+        mask_px = (mask.expand(B, H, H) if mask.dim() == 2 else mask.reshape(B, H, H)).contiguous()
+        if mask_px.dtype == torch.bool:
+            mask_px = mask_px.view(torch.uint8)                      # a bool tensor is one byte per element, 0 / 1
+        try:
+            ctx = self.engine_ctx(B, 1)
+            qc = self.quant_ctx(ctx.max_batch)
+            if self._sampler is None or self._sampler.t is not ctx or self._sampler.q is not qc:
+                self._sampler = E.Sampler(ctx, qc)
+        except torch.cuda.OutOfMemoryError as e:
+            self.invalidate_engine()
+            raise E.SdvarError(f"{who}: image: the sampler contexts cannot be built for a batch of {B} images: {e}") from None
+        force_ids = torch.cat(vae.img_to_idxBl(image, v_patch_nums=self.patch_nums), dim=1).contiguous()                     # (B, L): the image's own ids, stage s at [begin(s), begin(s) + pn_s^2)
+        gen = E.mask_tokens(mask_px, self.patch_nums)
+        res = self._sampler.plain_ar(labels, cfg, top_k, top_p, self._noise(g_seed), force_ids=force_ids, gen=gen, trusted_ids=True)
+        res.gen = gen
+        self.last_result = res
+        out = vae.fhat_to_img(res.f_hat.clone())
+        if composite:
+            return E.img_composite(out, image, mask_px, out=out)
+        return out.add_(1).mul_(0.5)
 
     @torch.no_grad()
     def autoregressive_infer_cfg_sd_helper1(self, B: int, current_step: int, step: int, next_token_map, f_hat, rng, sos, lvl_pos, cfg=1.5, top_k=0, top_p=0.0,
