@@ -285,6 +285,21 @@ int sdvar_cfg_sample_forced(const float* logits, int32_t B, int32_t l, int32_t V
 int sdvar_cfg_sample_rows_forced(const float* logits, int32_t B, int32_t l, int32_t V, const float* fac, const sdvar_row_image* img,
                                  const sdvar_row_image* img_host /*host*/, int32_t n_rows, const float* q, uint32_t draw, int64_t* ids_out,
                                  int32_t ids_stride, float* dbg_masked, const uint8_t* gen, const int64_t* force_ids, int32_t force_stride, void* stream);
+/* sdvar_verify_accept_ex / sdvar_verify_accept_rows over a chunk that holds forced tokens (the speculative sampler under a mask).  gen (uint8, DEVICE) is read at
+ * [b * gen_stride + tok_in_chunk], tok_in_chunk in [0, lsum): the pointer is already advanced to the chunk's first token, exactly as draft_ids is; gen_stride >= lsum.
+ * gen == 0, a forced token: it is no draft prediction, so it is verified by nobody - its workgroup reads no logit, adds nothing to counts[j], and writes (where given)
+ * match_out = 1, corrected_out = the draft id, argmax_out = -1.  gen != 0, a sampled token: everything as in the unforced entry points, for all three rules.
+ * counts[17 + j] = the number of SAMPLED tokens of stage j over the batch (not B * l_j); the scan accepts a stage with none, and otherwise applies
+ * float32(matched) / float32(sampled) promoted to double >= thr, stopping at the first failure.  Integer counters: repeated calls are bit-identical.  With gen all ones
+ * every counter and output carries the bits of the unforced entry point.  No host synchronisation. */
+int sdvar_verify_accept_forced(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n_stages, const int32_t* stage_lens /*host*/,
+                               const double* t /*host*/, const int64_t* draft_ids, int32_t ids_stride, double thr, int32_t rule, int32_t match_top_k,
+                               double kl_thr, const float* draft_logits, int32_t* counts, int64_t* argmax_out, uint8_t* match_out,
+                               int64_t* corrected_out, const uint8_t* gen, int32_t gen_stride, void* stream);
+int sdvar_verify_accept_rows_forced(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n_stages, const int32_t* stage_lens /*host*/, const float* fac,
+                                    int32_t n_rows, const int64_t* draft_ids, int32_t ids_stride, double thr, int32_t rule, int32_t match_top_k, double kl_thr,
+                                    const float* draft_logits, int32_t* counts, int64_t* argmax_out, uint8_t* match_out, int64_t* corrected_out,
+                                    const uint8_t* gen, int32_t gen_stride, void* stream);
 /* Pixel mask -> token table.  mask_px (B, H, H) uint8, DEVICE: non-zero = regenerate this pixel.  gen (B, L) uint8, L = sum pn_s^2, stage s at
  * columns [begin(s), begin(s) + pn_s^2), row-major (i, j).  Token (i, j) of a stage with side pn owns pixel rows [floor(i H / pn), ceil((i + 1) H / pn))
  * and the same span of columns (the windows of area interpolation; they overlap where pn does not divide H); gen = 1 iff

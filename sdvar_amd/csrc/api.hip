@@ -126,6 +126,10 @@ int noise_fill(float* q, int B, int l, int V, uint64_t seed, uint32_t draw, uint
 int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
                   const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits, const long long* dl_off, int* counts,
                   long long* argmax_out, unsigned char* match_out, long long* corrected_out, hipStream_t stream);
+int verify_accept_forced(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
+                         const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits, const long long* dl_off,
+                         int* counts, long long* argmax_out, unsigned char* match_out, long long* corrected_out, const unsigned char* gen, int gen_stride,
+                         hipStream_t stream);
 int cfg_combine(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac, float* out,
                 hipStream_t stream);
 int gumbel_mix_rows(const float* masked, int B, int l, int V, float scale, float tau, const float* e, const sdvar_row_image* img, uint32_t draw,
@@ -1199,6 +1203,37 @@ int sdvar_verify_accept_rows(const float* logits, int32_t B, int32_t lsum, int32
     ProfScope ps(5, 0, 4.0 * 2.0 * B * lsum * V * (rule == 2 ? 2.0 : 1.0), (hipStream_t)stream);
     return verify_accept(logits, B, lsum, V, n, qbeg, nullptr, nullptr, fac, (const long long*)draft_ids, ids_stride, thr, rule, match_top_k, (float)kl_thr, draft_logits,
                          dl, counts, (long long*)argmax_out, match_out, (long long*)corrected_out, (hipStream_t)stream);
+}
+
+// ---- the acceptance launches over a chunk with forced tokens (include/sdvar_hip.h "masked sampling")
+int sdvar_verify_accept_forced(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n, const int32_t* stage_lens, const double* t,
+                               const int64_t* draft_ids, int32_t ids_stride, double thr, int32_t rule, int32_t match_top_k, double kl_thr,
+                               const float* draft_logits, int32_t* counts, int64_t* argmax_out, uint8_t* match_out, int64_t* corrected_out, const uint8_t* gen,
+                               int32_t gen_stride, void* stream) {
+    SDVAR_CHECK_ARG(stage_lens && t && n >= 1 && n <= SDVAR_MAX_STAGES, "verify_accept_forced: bad stage table");
+    SDVAR_CHECK_ARG(gen, "verify_accept_forced: null gen table");
+    int qbeg[SDVAR_MAX_STAGES]; float opt[SDVAR_MAX_STAGES], tf[SDVAR_MAX_STAGES]; long long dl[SDVAR_MAX_STAGES]; int acc = 0;
+    for (int j = 0; j < n; ++j) { qbeg[j] = acc; dl[j] = (long long)2 * B * V * acc; acc += stage_lens[j]; opt[j] = (float)(1.0 + t[j]); tf[j] = (float)t[j]; }
+    SDVAR_CHECK_ARG(acc == lsum, "verify_accept_forced: stage lens sum %d != lsum %d", acc, lsum);
+    ProfScope ps(5, 0, 4.0 * 2.0 * B * lsum * V * (rule == 2 ? 2.0 : 1.0), (hipStream_t)stream);
+    return verify_accept_forced(logits, B, lsum, V, n, qbeg, opt, tf, nullptr, (const long long*)draft_ids, ids_stride, thr, rule, match_top_k, (float)kl_thr, draft_logits, dl,
+                                counts, (long long*)argmax_out, match_out, (long long*)corrected_out, gen, gen_stride, (hipStream_t)stream);
+}
+
+int sdvar_verify_accept_rows_forced(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n, const int32_t* stage_lens, const float* fac, int32_t n_rows,
+                                    const int64_t* draft_ids, int32_t ids_stride, double thr, int32_t rule, int32_t match_top_k, double kl_thr,
+                                    const float* draft_logits, int32_t* counts, int64_t* argmax_out, uint8_t* match_out, int64_t* corrected_out, const uint8_t* gen,
+                                    int32_t gen_stride, void* stream) {
+    SDVAR_CHECK_ARG(stage_lens && n >= 1 && n <= SDVAR_MAX_STAGES, "verify_accept_rows_forced: bad stage table");
+    SDVAR_CHECK_ARG(fac, "verify_accept_rows_forced: null parameter table");
+    SDVAR_CHECK_ARG(gen, "verify_accept_rows_forced: null gen table");
+    SDVAR_CHECK_ARG(B >= 1 && n_rows == B, "verify_accept_rows_forced: B = %d but the table holds %d images", B, n_rows);
+    int qbeg[SDVAR_MAX_STAGES]; long long dl[SDVAR_MAX_STAGES]; int acc = 0;
+    for (int j = 0; j < n; ++j) { qbeg[j] = acc; dl[j] = (long long)2 * B * V * acc; acc += stage_lens[j]; }
+    SDVAR_CHECK_ARG(acc == lsum, "verify_accept_rows_forced: stage lens sum %d != lsum %d", acc, lsum);
+    ProfScope ps(5, 0, 4.0 * 2.0 * B * lsum * V * (rule == 2 ? 2.0 : 1.0), (hipStream_t)stream);
+    return verify_accept_forced(logits, B, lsum, V, n, qbeg, nullptr, nullptr, fac, (const long long*)draft_ids, ids_stride, thr, rule, match_top_k, (float)kl_thr,
+                                draft_logits, dl, counts, (long long*)argmax_out, match_out, (long long*)corrected_out, gen, gen_stride, (hipStream_t)stream);
 }
 
 int sdvar_cfg_combine_rows(const float* logits, int32_t B, int32_t lsum, int32_t V, int32_t n, const int32_t* stage_lens, const float* fac, int32_t n_rows,

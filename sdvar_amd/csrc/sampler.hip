@@ -689,6 +689,7 @@ int gumbel_mix_rows(const float* masked, int B, int l, int V, float scale, float
 constexpr int ACC_MAX_CHUNK = 16;
 struct AcceptArgs {
     static constexpr bool rows = false;
+    static constexpr bool forced = false;
     const float* logits;            // (2B, lsum, V) target logits of the chunk
     const long long* draft_ids;     // draft_ids[b * ids_stride + tok_in_chunk]
     int* counts;                    // [0..n) matched per stage, [16] n_accept, [17..17+n) totals
@@ -708,14 +709,52 @@ struct AcceptRowArgs : AcceptArgs {       // one_plus_t[] / t[] unused: the fact
     static constexpr bool rows = true;
     const float* fac;                     // (n_chunk, B, 2)
 };
+// Forced tokens in a verified chunk (masked sampling, include/sdvar_hip.h): gen is read at [b * gen_stride + tok_in_chunk].  Only the forced instances carry the fields.
+struct AcceptForcedFields {
+    const unsigned char* gen;             // 1 = a sampled token (verified as ever), 0 = a forced one (no draft prediction: left out of every count)
+    int gen_stride;
+};
+struct AcceptForcedArgs : AcceptArgs, AcceptForcedFields { static constexpr bool forced = true; };
+struct AcceptRowForcedArgs : AcceptRowArgs, AcceptForcedFields { static constexpr bool forced = true; };
 template <class Args>
 __device__ __forceinline__ void stage_factors(const Args& a, int st, int b, float& opt, float& tt) {
     if constexpr (Args::rows) { const float* f = a.fac + 2 * ((size_t)st * a.B + b); opt = f[0]; tt = f[1]; }
     else { opt = a.one_plus_t[st]; tt = a.t[st]; }
 }
 
+// One body, four kernels, as cfg_sample_body: the forced instances first look up their token's `gen` byte - block-uniform - and a workgroup of a forced token
+// writes the optional outputs (match 1, corrected = the draft id, argmax -1) and leaves before it reads a logit or reaches a barrier, adding nothing to the match
+// counters; a workgroup of a sampled token runs the body unchanged.  The number of sampled tokens the scan divides by, counts[17 + stage], is counted from gen by
+// the workgroup of each stage's FIRST token, for its image, before that decision: ballots and popcounts, one atomic per wave that found any - B * n_chunk * 4 atomics
+// at the most.  (Reasoning, not a measurement: one atomic per sampled token, all on one address, would queue up in the L2.)
 template <class Args>
 __device__ __forceinline__ void verify_match_body(const Args& a) {
+    if constexpr (Args::forced) {
+        const int tok0 = blockIdx.x;
+        int st0 = 0;
+#pragma unroll 1
+        for (int j = 1; j < a.n_chunk; ++j) if (tok0 >= a.qbeg[j]) st0 = j;
+        const unsigned char* grow = a.gen + (size_t)blockIdx.y * a.gen_stride;
+        if (tok0 == a.qbeg[st0]) {                                   // block-uniform
+            const int l = a.qbeg[st0 + 1] - a.qbeg[st0];
+            int cnt = 0;
+            for (int i0 = 0; i0 < l; i0 += 256) {
+                const int i = i0 + (int)threadIdx.x;
+                const bool on = i < l && grow[tok0 + i] != 0;        // tok0 + i < qbeg[st0 + 1] <= lsum <= gen_stride
+                cnt += __popcll(__builtin_amdgcn_ballot_w64(on));
+            }
+            if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&a.counts[17 + st0], cnt);
+        }
+        if (grow[tok0] == 0) {
+            if (threadIdx.x == 0) {
+                const size_t o = (size_t)blockIdx.y * a.lsum + blockIdx.x;
+                if (a.argmax_out) a.argmax_out[o] = -1;
+                if (a.match_out) a.match_out[o] = 1;
+                if (a.corrected_out) a.corrected_out[o] = a.draft_ids[(size_t)blockIdx.y * a.ids_stride + blockIdx.x];
+            }
+            return;
+        }
+    }
     __shared__ float redf[8];
     __shared__ int redi[4];
     __shared__ double redd[8];
@@ -815,6 +854,8 @@ __device__ __forceinline__ void verify_match_body(const Args& a) {
 
 __global__ __launch_bounds__(256) void verify_match_kernel(AcceptArgs a) { verify_match_body(a); }
 __global__ __launch_bounds__(256) void verify_match_rows_kernel(AcceptRowArgs a) { verify_match_body(a); }
+__global__ __launch_bounds__(256) void verify_match_forced_kernel(AcceptForcedArgs a) { verify_match_body(a); }
+__global__ __launch_bounds__(256) void verify_match_rows_forced_kernel(AcceptRowForcedArgs a) { verify_match_body(a); }
 
 // n_accept = number of leading stages with float32(matched)/float32(total) >= thr (var.py:1203,1217), evaluated the
 // way the reference does: a float32 mean promoted to double against the double threshold.
@@ -830,18 +871,32 @@ __global__ void accept_scan_kernel(AcceptArgs a) {
     a.counts[16] = n;
 }
 
-// `fac` non-null: the per-image launch (one_plus_t / t ignored, may be null)
-int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
+// The scan of the forced launches: counts[17 + j] already holds the number of SAMPLED tokens of stage j (integer atomics of the match kernel: order-free).  A stage
+// with none is accepted - there is nothing the draft could have got wrong; otherwise the rule above over the sampled tokens.
+__global__ void accept_scan_forced_kernel(AcceptArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int n = 0; bool alive = true;
+    for (int j = 0; j < a.n_chunk; ++j) {
+        const int total = a.counts[17 + j];
+        const bool ok = total == 0 || (double)((float)a.counts[j] / (float)total) >= a.thr;
+        if (alive && ok) ++n; else alive = false;
+    }
+    a.counts[16] = n;
+}
+
+// `fac` non-null: the per-image launch (one_plus_t / t ignored, may be null).  `gen` non-null: the forced launches (verify_accept_forced below).
+static int verify_accept_impl(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
                   const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits,
-                  const long long* dl_off, int* counts, long long* argmax_out, unsigned char* match_out, long long* corrected_out, hipStream_t stream) {
+                  const long long* dl_off, int* counts, long long* argmax_out, unsigned char* match_out, long long* corrected_out, const unsigned char* gen,
+                  int gen_stride, hipStream_t stream) {
     SDVAR_CHECK_ARG(logits && draft_ids && counts, "verify_accept: null operand");
     SDVAR_CHECK_ARG(n_chunk >= 1 && n_chunk <= ACC_MAX_CHUNK && V % 4 == 0 && V <= NV, "verify_accept: bad chunk/V");
     SDVAR_CHECK_ARG(mode >= 0 && mode <= 2, "verify_accept: mode %d (0 top-1, 1 top-k membership, 2 KL threshold)", mode);
     SDVAR_CHECK_ARG(mode != 1 || top_k >= 1, "verify_accept: top-k membership needs k >= 1");
     SDVAR_CHECK_ARG(mode != 2 || (draft_logits && dl_off), "verify_accept: the KL rule needs the draft logits of the chunk");
     SDVAR_CHECK_ARG(fac || (one_plus_t && t), "verify_accept: no CFG factors");
-    AcceptRowArgs a{};
-    a.fac = fac;
+    AcceptRowForcedArgs a{};
+    a.fac = fac; a.gen = gen; a.gen_stride = gen_stride;
     a.logits = logits; a.draft_ids = draft_ids; a.counts = counts; a.argmax_out = argmax_out;
     a.B = B; a.lsum = lsum; a.V = V; a.ids_stride = ids_stride; a.n_chunk = n_chunk; a.thr = thr;
     a.mode = mode; a.top_k = top_k; a.kl_thr = kl_thr; a.draft_logits = draft_logits; a.match_out = match_out; a.corrected_out = corrected_out;
@@ -849,12 +904,40 @@ int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, cons
     a.qbeg[n_chunk] = lsum;
     const AcceptArgs& base = a;
     SDVAR_HIP(hipMemsetAsync(counts, 0, 40 * sizeof(int), stream));
-    if (fac) hipLaunchKernelGGL(verify_match_rows_kernel, dim3(lsum, B), dim3(256), 0, stream, a);
+    if (gen) {
+        AcceptForcedArgs f{};
+        static_cast<AcceptArgs&>(f) = base; static_cast<AcceptForcedFields&>(f) = a;
+        if (fac) hipLaunchKernelGGL(verify_match_rows_forced_kernel, dim3(lsum, B), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(verify_match_forced_kernel, dim3(lsum, B), dim3(256), 0, stream, f);
+        SDVAR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(accept_scan_forced_kernel, dim3(1), dim3(64), 0, stream, base);
+        SDVAR_LAUNCH_CHECK();
+        return SDVAR_OK;
+    }
+    if (fac) hipLaunchKernelGGL(verify_match_rows_kernel, dim3(lsum, B), dim3(256), 0, stream, static_cast<const AcceptRowArgs&>(a));
     else hipLaunchKernelGGL(verify_match_kernel, dim3(lsum, B), dim3(256), 0, stream, base);
     SDVAR_LAUNCH_CHECK();
     hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(64), 0, stream, base);
     SDVAR_LAUNCH_CHECK();
     return SDVAR_OK;
+}
+
+int verify_accept(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
+                  const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits,
+                  const long long* dl_off, int* counts, long long* argmax_out, unsigned char* match_out, long long* corrected_out, hipStream_t stream) {
+    return verify_accept_impl(logits, B, lsum, V, n_chunk, qbeg, one_plus_t, t, fac, draft_ids, ids_stride, thr, mode, top_k, kl_thr, draft_logits, dl_off, counts, argmax_out,
+                              match_out, corrected_out, nullptr, 0, stream);
+}
+
+// verify_accept over a chunk with forced tokens: gen (uint8, device) read at [b * gen_stride + tok_in_chunk]
+int verify_accept_forced(const float* logits, int B, int lsum, int V, int n_chunk, const int* qbeg, const float* one_plus_t, const float* t, const float* fac,
+                         const long long* draft_ids, int ids_stride, double thr, int mode, int top_k, float kl_thr, const float* draft_logits,
+                         const long long* dl_off, int* counts, long long* argmax_out, unsigned char* match_out, long long* corrected_out, const unsigned char* gen,
+                         int gen_stride, hipStream_t stream) {
+    SDVAR_CHECK_ARG(gen, "verify_accept_forced: null gen table");
+    SDVAR_CHECK_ARG(B >= 1 && lsum >= 1 && gen_stride >= lsum && ids_stride >= lsum, "verify_accept_forced: gen_stride %d / ids_stride %d below lsum = %d", gen_stride, ids_stride, lsum);
+    return verify_accept_impl(logits, B, lsum, V, n_chunk, qbeg, one_plus_t, t, fac, draft_ids, ids_stride, thr, mode, top_k, kl_thr, draft_logits, dl_off, counts, argmax_out,
+                              match_out, corrected_out, gen, gen_stride, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ cfg_combine

@@ -65,12 +65,12 @@ def gather_counters(stats: Dict[str, int], device) -> Dict[str, object]:
 
 def leading_accepted(matched: Sequence[int], totals: Sequence[int], thr: float) -> int:
     """Number of leading stages whose match rate is >= thr, with the reference's arithmetic: float32 mean compared as a
-    python float (models/var.py:1203, 1217)."""
+    python float (models/var.py:1203, 1217).  A stage with total 0 - under a mask, one whose tokens are all forced (totals count the sampled tokens) - is
+    accepted: there is nothing the draft could have got wrong (the rule of sdvar_verify_accept_forced)."""
     import numpy as np
     n = 0
     for m, t in zip(matched, totals):
-        rate = float(np.float32(m) / np.float32(t))
-        if rate >= thr:
+        if t == 0 or float(np.float32(m) / np.float32(t)) >= thr:
             n += 1
         else:
             break

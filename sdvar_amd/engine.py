@@ -111,6 +111,8 @@ _SIGNATURES = {
     "sdvar_gumbel_mix_rows": (_I, [_P, _P, _I, _I, _D, _D, _P, _P, _I, _U32, _P, _P]),
     "sdvar_cfg_sample_forced": (_I, [_P, _I, _I, _I, _D, _I, _D, _P, _U64, _U32, _U32, _P, _I, _P, _P, _P, _I, _P]),
     "sdvar_cfg_sample_rows_forced": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _U32, _P, _I, _P, _P, _P, _I, _P]),
+    "sdvar_verify_accept_forced": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_D), _P, _I, _D, _I, _I, _D, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "sdvar_verify_accept_rows_forced": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), _P, _I, _P, _I, _D, _I, _I, _D, _P, _P, _P, _P, _P, _P, _I, _P]),
     "sdvar_mask_tokens": (_I, [_P, _I, _I, _I, C.POINTER(_I), _P, _P]),
     "sdvar_img_composite": (_I, [_P, _P, _P, _I, _I, C.c_int64, _P, _P]),
     "sdvar_xent_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
@@ -945,12 +947,31 @@ class MatchRule:
 def verify_accept(logits: torch.Tensor, B: int, lens: Sequence[int], V: int, ts: Sequence[float], ids: torch.Tensor, ids_off: int, ids_stride: int,
                   thr: float, counts: torch.Tensor, argmax_out: Optional[torch.Tensor] = None, rule: Optional[MatchRule] = None,
                   draft_logits: Optional[torch.Tensor] = None, match_out: Optional[torch.Tensor] = None, corrected_out: Optional[torch.Tensor] = None,
-                  rows: Optional[RowParams] = None, s0: int = 0):
-    """`rows`: the CFG factors of (stage s0 + j, image b) come from its factor table and `ts` is ignored."""
+                  rows: Optional[RowParams] = None, s0: int = 0, gen: Optional[torch.Tensor] = None, gen_off: int = 0, gen_stride: int = 0):
+    """`rows`: the CFG factors of (stage s0 + j, image b) come from its factor table and `ts` is ignored.
+    `gen` (uint8, dense, on the logits' GPU): the forced entry points - token (b, i) of the chunk with gen[b * gen_stride + gen_off + i] == 0 is a forced token: it is
+    left out of counts[j], counts[17 + j] counts the sampled tokens only, a stage without any is accepted, and the optional outputs hold match 1 / corrected = the
+    draft id / argmax -1 there (include/sdvar_hip.h)."""
     lib = load_library()
     n = len(lens)
     o = lambda t: _ptr(t) if t is not None else None
     r = rule or MatchRule()
+    if gen is not None:
+        who, lsum = "verify_accept", int(sum(lens))
+        if B < 1 or lsum < 1 or gen_off < 0 or gen_stride < gen_off + lsum or ids_off < 0 or ids_stride < ids_off + lsum:
+            raise SdvarError(f"{who}: {lsum} tokens at offset {ids_off} / {gen_off} do not fit rows of stride {ids_stride} (ids) / {gen_stride} (gen)")
+        _edit_tensor(who, "gen", gen, torch.uint8, (B - 1) * gen_stride + gen_off + lsum, logits.device, 1, exact=False)
+        _edit_tensor(who, "ids", ids, torch.int64, (B - 1) * ids_stride + ids_off + lsum, logits.device, 8, exact=False)
+        p_ids, p_gen = C.c_void_p(ids.data_ptr() + 8 * ids_off), C.c_void_p(gen.data_ptr() + gen_off)
+        if rows is not None:
+            _check(lib.sdvar_verify_accept_rows_forced(_ptr(logits), B, lsum, V, n, (_I * n)(*lens), rows.fac_ptr(s0), rows.B, p_ids, ids_stride, float(thr), r.code,
+                                                       int(r.top_k), float(r.kl_thr), o(draft_logits), _ptr(counts), o(argmax_out), o(match_out), o(corrected_out), p_gen,
+                                                       gen_stride, _stream()))
+        else:
+            _check(lib.sdvar_verify_accept_forced(_ptr(logits), B, lsum, V, n, (_I * n)(*lens), (_D * n)(*[float(t) for t in ts]), p_ids, ids_stride, float(thr), r.code,
+                                                  int(r.top_k), float(r.kl_thr), o(draft_logits), _ptr(counts), o(argmax_out), o(match_out), o(corrected_out), p_gen,
+                                                  gen_stride, _stream()))
+        return
     if rows is not None:
         _check(lib.sdvar_verify_accept_rows(_ptr(logits), B, int(sum(lens)), V, n, (_I * n)(*lens), rows.fac_ptr(s0), rows.B,
                                             C.c_void_p(ids.data_ptr() + 8 * ids_off), ids_stride, float(thr), r.code, int(r.top_k), float(r.kl_thr),
@@ -1863,6 +1884,23 @@ class Sampler:
             stats["gemm_mode"] = modes
             stats["last_gemm_half"] = last_gemm_cfg()["bm"] == HALF_KERNEL_CODE
 
+    def _forced_arg(self, who: str, B: int, force_ids, gen, more_smooth: bool, trusted_ids: bool):
+        """The mask arguments of plain_ar and of the speculative loop, checked before anything is launched: (gen, force_ids), or None without a mask."""
+        if force_ids is None and gen is None:
+            return None
+        V, L = self.t.V, self.lad.L
+        if force_ids is None or gen is None:
+            raise SdvarError(f"{who}: force_ids and gen go together (both (B, L)), got only {'gen' if force_ids is None else 'force_ids'}")
+        if more_smooth:
+            raise SdvarError(f"{who}: more_smooth=True with a mask (force_ids / gen) is not supported: the gumbel mix of a forced token is undefined")
+        for name, t, dtype in (("force_ids", force_ids, torch.int64), ("gen", gen, torch.uint8)):
+            if isinstance(t, torch.Tensor) and tuple(t.shape) != (B, L):
+                raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}, expected (B, L) = {(B, L)}")
+            _edit_tensor(who, name, t, dtype, B * L, self.ids.device, 8 if dtype == torch.int64 else 1)
+        if not trusted_ids and bool(((force_ids < 0) | (force_ids >= V)).any()):
+            raise SdvarError(f"{who}: force_ids holds ids outside [0, V = {V})")
+        return (gen, force_ids)
+
     @property
     def f_snap(self):
         return self._fs[self._slot]
@@ -1880,20 +1918,7 @@ class Sampler:
         force_ids value must lie in [0, V): checked once before the first launch (one reduction, one synchronisation) unless trusted_ids=True."""
         m, qz, lad = self.t, self.q, self.lad
         B, V, S, L = labels.shape[0], m.V, lad.S, lad.L
-        forced = None
-        if force_ids is not None or gen is not None:
-            who = "plain_ar"
-            if force_ids is None or gen is None:
-                raise SdvarError(f"{who}: force_ids and gen go together (both (B, L)), got only {'gen' if force_ids is None else 'force_ids'}")
-            if more_smooth:
-                raise SdvarError(f"{who}: more_smooth=True with a mask (force_ids / gen) is not supported: the gumbel mix of a forced token is undefined")
-            for name, t, dtype in (("force_ids", force_ids, torch.int64), ("gen", gen, torch.uint8)):
-                if isinstance(t, torch.Tensor) and tuple(t.shape) != (B, L):
-                    raise SdvarError(f"{who}: {name} has shape {tuple(t.shape)}, expected (B, L) = {(B, L)}")
-                _edit_tensor(who, name, t, dtype, B * L, self.ids.device, 8 if dtype == torch.int64 else 1)
-            if not trusted_ids and bool(((force_ids < 0) | (force_ids >= V)).any()):
-                raise SdvarError(f"{who}: force_ids holds ids outside [0, V = {V})")
-            forced = (gen, force_ids)
+        forced = self._forced_arg("plain_ar", B, force_ids, gen, more_smooth, trusted_ids)
         res = SampleResult(ids=self.ids[:B], f_hat=self.f_work[:B])
         with torch.cuda.device(self.dev):
             rows = RowParams.build(B, lad, cfg, top_k, top_p, noise, self.dev)          # None for scalar arguments: the scalar launches
@@ -1972,12 +1997,14 @@ class Sampler:
 
     # ---- SDVAR.sdvar_autoregressive_infer_cfg_sd_test3 (var.py:604-865): the draft samples stages < entry_num, the target the rest
     def handoff(self, labels: torch.Tensor, cfg: float, top_k: int, top_p: float, noise: Noise, entry_num: int, sd_mask: int = 0,
-                more_smooth: bool = False) -> SampleResult:
+                more_smooth: bool = False, force_ids=None, gen=None) -> SampleResult:
         """sd_mask 0: the target starts at the entry stage with an empty KV cache - it does not condition on the draft's prefix
         (var.py:817-824).  sd_mask 3: the target first runs the whole prefix + entry stage through its blocks under the block-causal
         mask (var.py:789, 802-804: this fills its cache), then - literally as the reference does - takes the entry stage's logits from
         the INPUT token map, not from the block output (var.py:809-811).  One noise stream: draw index = stage (var.py:642, 689, 831)."""
         assert self.d is not None, "the hand-off sampler needs a draft model"
+        if force_ids is not None or gen is not None:
+            raise SdvarError("handoff: masked sampling (force_ids / gen) is not supported here: use plain_ar or spec_decode")
         scalar_arg("handoff", cfg=cfg, top_k=top_k, top_p=top_p, noise=noise)
         d, t, qz, lad = self.d, self.t, self.q, self.lad
         B, V, S, L, lens = labels.shape[0], t.V, lad.S, lad.L, lad.lens
@@ -2033,17 +2060,20 @@ class Sampler:
 
     # ---- speculative draft -> verify loop, as the reference's four steps
     def spec_begin(self, labels: torch.Tensor, cfg: float, gamma: int, top_k: int, top_p: float, noise: Noise, thr: float = 0.5,
-                   match: Optional[MatchRule] = None) -> "SpecState":
-        """SDVAR._initialize_inference_state (var.py:871-947): both prologues, empty caches, counters."""
+                   match: Optional[MatchRule] = None, force_ids: Optional[torch.Tensor] = None, gen: Optional[torch.Tensor] = None,
+                   trusted_ids: bool = False, who: str = "spec_begin") -> "SpecState":
+        """SDVAR._initialize_inference_state (var.py:871-947): both prologues, empty caches, counters.
+        `force_ids` / `gen` / `trusted_ids`: the mask of plain_ar, for spec_decode (the step-wise helpers of sdvar_amd.var.SDVAR refuse such a state)."""
         assert self.d is not None, "the speculative loop needs a draft model"
         assert 1 <= gamma <= self.t.max_chunk, f"gamma {gamma} exceeds the engine's max_chunk {self.t.max_chunk}"
+        forced = self._forced_arg(who, labels.shape[0], force_ids, gen, False, trusted_ids)
         with torch.cuda.device(self.dev):
             rows = RowParams.build(labels.shape[0], self.lad, cfg, top_k, top_p, noise, self.dev)        # per-image parameters: one table for the whole loop
             self.d.begin(labels); self.t.begin(labels)
             self.f_acc[:labels.shape[0]].zero_()
         self._row, self._slot = 0, 0
         return SpecState(sampler=self, labels=labels, B=labels.shape[0], cfg=cfg, gamma=gamma, top_k=top_k, top_p=top_p, noise=noise, thr=thr,
-                         total_stages=self.lad.S, patch_nums=self.lad.patch_nums, match=match or MatchRule(), rows=rows)
+                         total_stages=self.lad.S, patch_nums=self.lad.patch_nums, match=match or MatchRule(), rows=rows, forced=forced)
 
     def spec_draft(self, st: "SpecState") -> int:
         """SDVAR.draft_generate_batch (var.py:949-1024): g = min(gamma, S - cur) draft stages (forward, CFG, sample, quant,
@@ -2074,7 +2104,14 @@ class Sampler:
                     d.forward(self.x_d, s, 1, lg)
                 st.stats["draft_stage_calls"] += 1
                 q = st.noise.tensor(st.draw, B, lens[s], V, self.dev)
-                if st.rows is not None:
+                if st.forced is not None:                  # under a mask the draft's forced tokens are the image's own ids
+                    gen, force_ids = st.forced
+                    if st.rows is not None:
+                        cfg_sample_rows_forced(lg, B, lens[s], V, st.rows, s, q, st.draw, self.ids, lad.begin(s), L, gen, force_ids, lad.begin(s), L)
+                    else:
+                        cfg_sample_forced(lg, B, lens[s], V, lad.cfg_t(st.cfg, s), st.top_k, st.top_p, q, st.noise.seed, st.draw, st.noise.image_offset,
+                                          self.ids, lad.begin(s), L, gen, force_ids, lad.begin(s), L)
+                elif st.rows is not None:
                     cfg_sample_rows(lg, B, lens[s], V, st.rows, s, q, st.draw, self.ids, lad.begin(s), L)
                 else:
                     cfg_sample(lg, B, lens[s], V, lad.cfg_t(st.cfg, s), st.top_k, st.top_p, q, st.noise.seed, st.draw, st.noise.image_offset,
@@ -2112,9 +2149,11 @@ class Sampler:
         with torch.cuda.device(self.dev):
             corr = self._buf("ids_corr", self.t.max_batch * self.lmax_t, torch.int64) if mr.token_level else None
             verify_accept(self.logits_t, st.B, st.glen, self.t.V, st.chunk_ts(cur, g), self.ids, lad.begin(cur), lad.L, st.thr, self.counts,
-                          rule=mr, draft_logits=self._lazy.get("draft_logits") if mr.rule == "kl" else None, corrected_out=corr, rows=st.rows, s0=cur)
+                          rule=mr, draft_logits=self._lazy.get("draft_logits") if mr.rule == "kl" else None, corrected_out=corr, rows=st.rows, s0=cur,
+                          **st.gen_args(cur))
             self.counts_host.copy_(self.counts, non_blocking=False)            # the one host sync of the round
         c = self.counts_host.tolist()
+        st.totals = st.round_totals(c, st.glen)
         if st.accept_scope == "global":            # batch-wide decision across ranks (reference-literal for one big batch)
             from . import dist as D
             n, _, _ = D.global_accept(c[:g], c[17:17 + g], st.thr, self.dev)
@@ -2134,7 +2173,7 @@ class Sampler:
             self.ids[:B, lad.begin(s):lad.begin(s) + l].copy_(corr[:, off:off + l])
             last = s == lad.S - 1
             self.q.next(s, self.ids[:, lad.begin(s):], lad.L, self.f_snap[j][:B], None if last else self.nxt[j], B, f_in=self.f_acc[:B] if j == 0 else self.f_snap[j - 1][:B])
-        st.stats["corrected_tokens"] = st.stats.get("corrected_tokens", 0) + B * l - matched[j]
+        st.stats["corrected_tokens"] = st.stats.get("corrected_tokens", 0) + st.totals[j] - matched[j]          # under a mask: sampled tokens only
         st.stats["corrected_stages"] = st.stats.get("corrected_stages", 0) + 1
         return n_acc + 1
 
@@ -2161,11 +2200,16 @@ class Sampler:
         st.stats["gamma_final"] = st.gamma
 
     def spec_decode(self, labels: torch.Tensor, cfg: float, gamma: int, top_k: int, top_p: float, noise: Noise, thr: float = 0.5,
-                    trace: bool = False, run_ahead: bool = True, accept_scope: str = "shard", match: Optional[MatchRule] = None) -> SampleResult:
+                    trace: bool = False, run_ahead: bool = True, accept_scope: str = "shard", match: Optional[MatchRule] = None,
+                    force_ids: Optional[torch.Tensor] = None, gen: Optional[torch.Tensor] = None, trusted_ids: bool = False) -> SampleResult:
         """The whole loop with the policy of var.py:1318-1372 (gamma only decreases; forced accept at gamma == 1; never break).
         run_ahead: once gamma has dropped to 1 the draft no longer waits for the verifier (see _spec_run_ahead); same results.
-        accept_scope "global": the batch-wide decision is taken across ranks (one all-reduce per round), always in lock-step."""
-        st = self.spec_begin(labels, cfg, gamma, top_k, top_p, noise, thr, match)
+        accept_scope "global": the batch-wide decision is taken across ranks (one all-reduce per round), always in lock-step.
+        `force_ids` (B, L) int64 and `gen` (B, L) uint8, both or neither, checked as plain_ar checks them: masked sampling.  The draft samples token (b, i) where
+        gen[b, i] != 0 and takes force_ids[b, i] elsewhere; a forced token is no draft prediction, so the acceptance rate of a stage is matched / SAMPLED tokens of
+        the batch, a stage without a sampled token is accepted, and rounds[].total, stats["sampled_tokens"] and corrected_tokens count sampled tokens only.  The
+        overlap paths are kept.  Without a mask the launches and the results are those of the unmasked loop."""
+        st = self.spec_begin(labels, cfg, gamma, top_k, top_p, noise, thr, match, force_ids=force_ids, gen=gen, trusted_ids=trusted_ids, who="spec_decode")
         st.accept_scope = accept_scope
         run_ahead = run_ahead and st.match.basic        # the richer rules run in lock-step
         res = SampleResult(ids=self.ids[:st.B], f_hat=self.f_acc[:st.B], stats=st.stats)
@@ -2196,10 +2240,12 @@ class Sampler:
                 else:
                     n_acc, forced = 1, True
                     st.stats["forced_accepts"] += 1
-            st.stats["rounds"].append(dict(stage=cur, g=g, matched=matched, total=[st.B * n for n in st.glen], n_accept=n_acc, forced=forced))
+            st.stats["rounds"].append(dict(stage=cur, g=g, matched=matched, total=st.totals, n_accept=n_acc, forced=forced))
             optimistic = n_acc == g and not forced
             self.spec_commit(st, n_acc, forced, acc_tok)
         self.spec_end(st)
+        if st.forced is not None:              # every stage is committed by exactly one round, as one of its first n_accept stages
+            st.stats["sampled_tokens"] = sum(sum(r["total"][:r["n_accept"]]) for r in st.stats["rounds"])
         self._f16_stats(res.stats)
         if _GUARD_ON:
             res.stats["f16x2_guard"] = f16x2_guard_collect()
@@ -2243,7 +2289,7 @@ class Sampler:
                 with torch.cuda.stream(T):
                     self.t.forward(self._xt[slot], cur, g, self.logits_t)
                     verify_accept(self.logits_t, B, st.glen, V, st.chunk_ts(cur, g), self.ids, lad.begin(cur), lad.L, st.thr,
-                                  self.counts_ra[row], rows=st.rows, s0=cur)
+                                  self.counts_ra[row], rows=st.rows, s0=cur, **st.gen_args(cur))
                     self._counts_pin[row].copy_(self.counts_ra[row], non_blocking=True)
                     ev = torch.cuda.Event(); ev.record(T); t_done.append(ev)
                 st.stats["target_calls"] += 1
@@ -2271,7 +2317,7 @@ class Sampler:
         c = self._counts_pin[p["row"]].tolist()
         g, glen, n_acc, matched = p["g"], p["glen"], c[16], c[:p["g"]]
         st.stats["accepted_tokens"] += sum(glen[:n_acc])
-        st.stats["rounds"].append(dict(stage=p["cur"], g=g, matched=matched, total=[B * m for m in glen], n_accept=n_acc, forced=False))
+        st.stats["rounds"].append(dict(stage=p["cur"], g=g, matched=matched, total=st.round_totals(c, glen), n_accept=n_acc, forced=False))
         if n_acc == g:
             return True
         slot = p["slot"]
@@ -2317,7 +2363,7 @@ class Sampler:
                     else:
                         self.t.forward(self._xt[st.xt_idx], cur, 1, self.logits_t)
                     verify_accept(self.logits_t, B, st.glen, V, st.chunk_ts(cur, 1), self.ids, lad.begin(cur), lad.L, st.thr, self.counts_ra[row0 + r],
-                                  rows=st.rows, s0=cur)
+                                  rows=st.rows, s0=cur, **st.gen_args(cur))
                     ev = torch.cuda.Event(); ev.record(T); t_done.append(ev)
                 st.stats["target_calls"] += 1
                 st.target_calls += 1
@@ -2335,7 +2381,7 @@ class Sampler:
                 st.stats["forced_accepts"] += 1
             else:
                 st.stats["accepted_tokens"] += sum(glen[:n_acc])
-            st.stats["rounds"].append(dict(stage=cur, g=g, matched=matched, total=[B * n for n in glen], n_accept=n_acc, forced=forced))
+            st.stats["rounds"].append(dict(stage=cur, g=g, matched=matched, total=st.round_totals(row, glen), n_accept=n_acc, forced=forced))
 
 
 @dataclass
@@ -2367,6 +2413,19 @@ class SpecState:
     verified: bool = False
     stats: Dict[str, object] = field(default_factory=lambda: dict(target_calls=0, draft_stage_calls=0, forced_accepts=0, accepted_tokens=0, rounds=[], gamma_final=0))
     rows: Optional["RowParams"] = None            # per-image (cfg, top_k, top_p, seed, index) tables; None = the scalar fields above
+    forced: Optional[tuple] = None                # masked sampling: (gen (B, L) uint8, force_ids (B, L) int64); None = no mask
+    totals: list = field(default_factory=list)    # tokens per stage that the last spec_accept counted (under a mask: the sampled ones)
+
+    def gen_args(self, cur: int) -> dict:
+        """The mask arguments of verify_accept for a chunk that starts at stage `cur`; empty without a mask (the unforced entry points)."""
+        if self.forced is None:
+            return {}
+        lad = self.sampler.lad
+        return dict(gen=self.forced[0], gen_off=lad.begin(cur), gen_stride=lad.L)
+
+    def round_totals(self, counts: Sequence[int], glen: Sequence[int]) -> list:
+        """rounds[].total: under a mask the sampled tokens per stage, read from the counter row of the verification; B * l without one."""
+        return [int(x) for x in counts[17:17 + len(glen)]] if self.forced is not None else [self.B * n for n in glen]
 
     def chunk_ts(self, cur: int, g: int):
         """The scalar CFG factors of stages cur .. cur + g - 1 (unused when `rows` carries them per image)."""

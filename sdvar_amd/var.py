@@ -214,29 +214,8 @@ class VAR(nn.Module):
         composite=False the decoder's output is returned as it is, and kept pixels move (the decoder's receptive field, the bicubic up-sampling of coarse
         tokens).  more_smooth=True raises SdvarError (the gumbel mix of a forced token is undefined).  last_result additionally carries `gen`, the (B, L) table."""
         who = "autoregressive_infer_cfg_edit"
-        if more_smooth:
-            raise E.SdvarError(f"{who}: more_smooth=True is not supported with a mask: the gumbel mix of a forced token is undefined")
         vae = self.vae_proxy[0]
-        if not getattr(vae, "with_encoder", False):
-            raise E.SdvarError(f"{who}: image: the VQVAE was built with with_encoder=False, so it cannot encode the image to edit")
-        H = vae.downsample * self.patch_nums[-1]
-        if not isinstance(image, torch.Tensor) or image.dim() != 4 or image.shape[0] < 1 or image.shape[1] != 3 or image.dtype != torch.float32:
-            what = f"{tuple(image.shape)} {image.dtype}" if isinstance(image, torch.Tensor) else type(image).__name__
-            raise E.SdvarError(f"{who}: image must be a (B, 3, H, H) float32 tensor in [-1, 1], got {what}")
-        B = int(image.shape[0])
-        if tuple(image.shape[2:]) != (H, H):
-            raise E.SdvarError(f"{who}: image is {image.shape[2]} x {image.shape[3]}, but the ladder {self.patch_nums} generates {H} x {H} images")
-        if B > MAX_EDIT_BATCH:
-            raise E.SdvarError(f"{who}: image: a batch of {B} images is more than the sampler contexts can be built for ({MAX_EDIT_BATCH})")
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-            what = f"{mask.dtype}" if isinstance(mask, torch.Tensor) else type(mask).__name__
-            raise E.SdvarError(f"{who}: mask must be a bool or uint8 tensor (non-zero = regenerate), got {what}")
-        if tuple(mask.shape) not in ((B, H, H), (B, 1, H, H), (H, H)):
-            raise E.SdvarError(f"{who}: mask has shape {tuple(mask.shape)}, expected {(B, H, H)}, {(B, 1, H, H)} or {(H, H)}")
-        dev = self._device()
-        for name, t in (("image", image), ("mask", mask)):
-            if not t.is_cuda or t.device != dev:
-                raise E.SdvarError(f"{who}: {name} is on {t.device}, the model on {dev}: masked sampling runs on the GPU and there is no CPU path")
+        B, H = _edit_args(who, self, image, mask, more_smooth)
         g_seed = _seed_arg(g_seed, B, label_B)
         if g_seed is None or isinstance(g_seed, list):
             rng = None
@@ -244,10 +223,7 @@ class VAR(nn.Module):
             self.rng.manual_seed(g_seed); rng = self.rng
         _row_lengths(B, cfg=cfg, top_k=top_k, top_p=top_p)
         labels = self._labels(B, label_B, rng)
-        image = image.contiguous()
-        mask_px = (mask.expand(B, H, H) if mask.dim() == 2 else mask.reshape(B, H, H)).contiguous()
-        if mask_px.dtype == torch.bool:
-            mask_px = mask_px.view(torch.uint8)                      # a bool tensor is one byte per element, 0 / 1
+        image, mask_px = _edit_operands(image, mask, B, H)
         try:
             ctx = self.engine_ctx(B, 1)
             qc = self.quant_ctx(ctx.max_batch)
@@ -380,6 +356,43 @@ class VARHF(VAR, _HubMixin):
                          flash_if_available=flash_if_available, fused_if_available=fused_if_available)
 
 
+def _edit_args(who: str, model: "VAR", image, mask, more_smooth: bool):
+    """The argument contract of the edit calls (VAR.autoregressive_infer_cfg_edit, SDVAR.sdvar_autoregressive_infer_cfg_parallel_v1_edit), checked before anything
+    is built or launched; `model` is the VAR whose VQVAE encodes the image.  Returns (B, H)."""
+    if more_smooth:
+        raise E.SdvarError(f"{who}: more_smooth=True is not supported with a mask: the gumbel mix of a forced token is undefined")
+    vae = model.vae_proxy[0]
+    if not getattr(vae, "with_encoder", False):
+        raise E.SdvarError(f"{who}: image: the VQVAE was built with with_encoder=False, so it cannot encode the image to edit")
+    H = vae.downsample * model.patch_nums[-1]
+    if not isinstance(image, torch.Tensor) or image.dim() != 4 or image.shape[0] < 1 or image.shape[1] != 3 or image.dtype != torch.float32:
+        what = f"{tuple(image.shape)} {image.dtype}" if isinstance(image, torch.Tensor) else type(image).__name__
+        raise E.SdvarError(f"{who}: image must be a (B, 3, H, H) float32 tensor in [-1, 1], got {what}")
+    B = int(image.shape[0])
+    if tuple(image.shape[2:]) != (H, H):
+        raise E.SdvarError(f"{who}: image is {image.shape[2]} x {image.shape[3]}, but the ladder {model.patch_nums} generates {H} x {H} images")
+    if B > MAX_EDIT_BATCH:
+        raise E.SdvarError(f"{who}: image: a batch of {B} images is more than the sampler contexts can be built for ({MAX_EDIT_BATCH})")
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        what = f"{mask.dtype}" if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise E.SdvarError(f"{who}: mask must be a bool or uint8 tensor (non-zero = regenerate), got {what}")
+    if tuple(mask.shape) not in ((B, H, H), (B, 1, H, H), (H, H)):
+        raise E.SdvarError(f"{who}: mask has shape {tuple(mask.shape)}, expected {(B, H, H)}, {(B, 1, H, H)} or {(H, H)}")
+    dev = model._device()
+    for name, t in (("image", image), ("mask", mask)):
+        if not t.is_cuda or t.device != dev:
+            raise E.SdvarError(f"{who}: {name} is on {t.device}, the model on {dev}: masked sampling runs on the GPU and there is no CPU path")
+    return B, H
+
+
+def _edit_operands(image: torch.Tensor, mask: torch.Tensor, B: int, H: int):
+    """(image, mask_px): the dense image and the (B, H, H) uint8 pixel mask the kernels take."""
+    mask_px = (mask.expand(B, H, H) if mask.dim() == 2 else mask.reshape(B, H, H)).contiguous()
+    if mask_px.dtype == torch.bool:
+        mask_px = mask_px.view(torch.uint8)                      # a bool tensor is one byte per element, 0 / 1
+    return image.contiguous(), mask_px
+
+
 def _seed_arg(g_seed, B: int, label_B):
     """g_seed as the samplers take it: None, one int, or a list of B ints (per-image seeds; they need explicit labels)."""
     if g_seed is None:
@@ -460,6 +473,7 @@ class SDVAR(nn.Module):
     def draft_generate_batch(self, state: E.SpecState, B: int):
         """var.py:949-1024 -> list of g token tensors (B, pn^2) int64 for stages current_stage .. current_stage+g-1."""
         smp, lad = state.sampler, state.sampler.lad
+        _mask_free("draft_generate_batch", state)
         if state.rows is None:                      # a state begun with scalars samples with the scalars it carries now (var.py:937-938 sets top_k / top_p on it)
             E.scalar_arg("draft_generate_batch", cfg=state.cfg, top_k=state.top_k, top_p=state.top_p)
         g = smp.spec_draft(state)
@@ -472,6 +486,7 @@ class SDVAR(nn.Module):
         if not draft_tokens:
             return [], 0
         assert len(draft_tokens) == state.g, "target_verify_batch verifies the stages of the last draft_generate_batch"
+        _mask_free("target_verify_batch", state)
         if state.rows is None:
             E.scalar_arg("target_verify_batch", cfg=state.cfg)
         smp, lad, cur = state.sampler, state.sampler.lad, state.current_stage
@@ -515,6 +530,7 @@ class SDVAR(nn.Module):
 
     def update_state_with_accepted_tokens(self, draft_tokens, accept_length: int, state: E.SpecState, B: int):
         """var.py:1245-1282 (+ the stage advance of var.py:1349-1350 and the KV rollback the reference lacks)."""
+        _mask_free("update_state_with_accepted_tokens", state)
         state.sampler.spec_commit(state, max(int(accept_length), 0))
 
     @torch.no_grad()
@@ -532,6 +548,40 @@ class SDVAR(nn.Module):
         self.last_result = res
         return t.vae_proxy[0].fhat_to_img(res.f_hat.clone()).add_(1).mul_(0.5)
 
+    # ---- masked sampling at draft -> verify speed (an extension; the reference has no such call) ----------------------------------------
+    @torch.no_grad()
+    def sdvar_autoregressive_infer_cfg_parallel_v1_edit(self, image: torch.Tensor, mask: torch.Tensor, label_B: Optional[Union[int, torch.LongTensor]],
+                                                        g_seed: Optional[int] = None, cfg=1.5, gamma: int = 2, top_k=0, top_p=0.0, composite: bool = True,
+                                                        more_smooth: bool = False) -> torch.Tensor:
+        """VAR.autoregressive_infer_cfg_edit through the speculative loop: regenerate the masked region of `image` under `label_B` and keep the rest, (B, 3, H, H)
+        in [0, 1].  The arguments are those of VAR.autoregressive_infer_cfg_edit (same checks, same messages) plus `gamma`; cfg / top_k / top_p / g_seed may be
+        per-image sequences; more_smooth=True raises SdvarError.  The image is encoded by the target's VQVAE, engine.mask_tokens turns the pixel mask into the
+        (B, L) token table, and Sampler.spec_decode(force_ids=, gen=) runs the draft -> verify loop in which both models see the image's own ids at the kept
+        tokens and only the sampled tokens are verified: the acceptance rate of a stage is matched / sampled tokens of the batch, and a stage without a sampled
+        token is accepted.  With composite=True the kept pixels are the bits of image.add(1).mul(0.5).  last_result carries `gen`."""
+        who = "sdvar_autoregressive_infer_cfg_parallel_v1_edit"
+        t = self.target_model
+        vae = t.vae_proxy[0]
+        B, H = _edit_args(who, t, image, mask, more_smooth)
+        _row_lengths(B, cfg=cfg, top_k=top_k, top_p=top_p)
+        image, mask_px = _edit_operands(image, mask, B, H)
+        try:
+            labels, smp, noise = self._prepare(B, label_B, g_seed, gamma)
+        except torch.cuda.OutOfMemoryError as e:
+            t.invalidate_engine(); self.draft_model.invalidate_engine()
+            self._sampler = None
+            raise E.SdvarError(f"{who}: image: the sampler contexts cannot be built for a batch of {B} images: {e}") from None
+        force_ids = torch.cat(vae.img_to_idxBl(image, v_patch_nums=t.patch_nums), dim=1).contiguous()          # (B, L): the image's own ids
+        gen = E.mask_tokens(mask_px, t.patch_nums)
+        res = smp.spec_decode(labels, cfg, gamma, top_k, top_p, noise, thr=self.match_threshold, run_ahead=True, accept_scope=self.accept_scope,
+                              match=self.match_rule, force_ids=force_ids, gen=gen, trusted_ids=True)
+        res.gen = gen
+        self.last_result = res
+        out = vae.fhat_to_img(res.f_hat.clone())
+        if composite:
+            return E.img_composite(out, image, mask_px, out=out)
+        return out.add_(1).mul_(0.5)
+
     @torch.no_grad()
     def sdvar_autoregressive_infer_cfg_sd_test3(self, B: int, label_B: Optional[Union[int, torch.LongTensor]], g_seed: Optional[int] = None, cfg: float = 1.5,
                                                 top_k: int = 0, top_p: float = 0.0, more_smooth: bool = False, entry_num: int = 10, sd_mask: int = 0) -> torch.Tensor:
@@ -548,6 +598,11 @@ class SDVAR(nn.Module):
         res = smp.handoff(labels, cfg, top_k, top_p, noise, entry_num, sd_mask, more_smooth=bool(more_smooth))
         self.last_result = res
         return t.vae_proxy[0].fhat_to_img(res.f_hat.clone()).add_(1).mul_(0.5)
+
+
+def _mask_free(who: str, state: E.SpecState):
+    if state.forced is not None:
+        raise E.SdvarError(f"{who}: the step-wise helpers take no mask (force_ids / gen): run Sampler.spec_decode or sdvar_autoregressive_infer_cfg_parallel_v1_edit")
 
 
 def _factory_checks(patch_nums: Sequence[int]):
